@@ -9,9 +9,12 @@ phase) followed by one multigrid cycle on the assembled residual (the reference'
 hierarchy prepared once before the timed region (Galerkin chain + SetPenalty + smoother/coarse setup = the reference's
 "PREPARATION TIME", reported separately as prepare_ms).  Inputs are resident in HBM when the timed region starts.
 
-Prints ONE JSON line on rank 0 (contract in the task description); `roofline` is the fine-level Jacobi-sweep SpMV
-kernel, `cpu_baseline` is the oracle's C restatement timed on the host cores of this box (rank 0, N=1 only).  `roofline.traffic` comes
-from hardware counters of this run: two short child runs of femus_amd/traffic_probe.py under rocprofv3 --pmc after the timed region.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and reports the headline (`value`, `ms_per_step`)
+with what set-up measured on the way; --dump-outputs DIR also writes what the last timed step computed (dump_outputs).  --full adds,
+after the timed steps, everything else: sub-phase timings, the whole MGsolve, `roofline` (the fine-level Jacobi-sweep SpMV kernel),
+`roofline_assembly`, halo exchanges, the known-answer test and `cpu_baseline` (the oracle's C restatement timed on the host cores of
+this box, rank 0, N=1 only).  `roofline.traffic` comes from hardware counters of that run: two short child runs of
+femus_amd/traffic_probe.py under rocprofv3 --pmc.
 """
 import argparse
 import json
@@ -36,6 +39,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--coarse", type=int, default=8, help="coarse box elements per direction (8 -> 64^3 with 4 levels)")
     ap.add_argument("--levels", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else: sub-phase timings, the whole solve, the roofline kernels, halo "
+                         "exchanges, the known-answer test, hardware-counter traffic and the CPU baseline (the --no-* / --kernel-reps options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64): correction, residual and a seeded sample of the operator")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-known-answer", action="store_true", help="skip the reference's known-answer test (3 s, after the timed region)")
     ap.add_argument("--kernel-reps", type=int, default=50)
@@ -77,7 +85,6 @@ def main():
         sys.stderr.write("bench.py: --gpus %d but the launcher started %d rank(s)\n" % (args.gpus, world))
         sys.exit(2)
 
-    import numpy as np
     import femus_amd
     from femus_amd import dd
     from femus_amd.poisson import PoissonMG
@@ -179,6 +186,75 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     ndof_total = int(sum(comm.allgather_obj(int(ndof))))
     value = ndof_total * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pb)
+
+    out = {
+        "metric": "assembled DOFs/sec + V-cycle SpMV GB/s (% HBM peak), 3D Poisson Q2",
+        "value": value,
+        "unit": "DOF/s (assembly + one V(2,2) cycle per step)",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": "3D Poisson Q2 (HEX27, 64-pt Gauss) on %d^3 box per GPU, %d-level GMG V(2,2) Jacobi(2/3), Galerkin coarse "
+                        "operators, dense exact coarse solve" % (args.coarse * 2 ** (args.levels - 1), args.levels),
+            "dofs_total": ndof_total,
+            "dofs_this_gpu": ndof,
+            "elements_this_gpu": nel,
+            "nnz_fine_this_gpu": A.nnz,
+            "parallelism": parallelism,
+        },
+        "prepare_ms": pb.prepare_ms,
+        "coarse_solve": dict(zip(("dense_unknowns", "dissection_blocks", "separator", "largest_block"), pb.mg.coarse_info()),
+                             what="exact solve of the coarsest level: unknowns coupled to nothing by their diagonal, the rest dense -- dissected into interior blocks "
+                                  "inverted beside each other + a separator Schur complement (dissection_blocks 0: one dense inverse)"),
+        "runtime_libraries": femus_amd.loaded_runtimes(),
+        "prepare_first_s": pb.prepare_first_s,
+        "setup_s": setup_s,
+    }
+    if preflight is not None:
+        out["rccl_preflight"] = preflight          # what the RCCL preflight children of every rank said (ok / message / seconds)
+    if args.full:
+        full_report(out, args, ctx, comm, pb, barrier, rank, world, device, ndof_total, ms_per_step)
+
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    comm.barrier()
+    comm.close()
+
+
+def dump_outputs(d, pb):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy in float64 -- the V-cycle's correction (EPSC) and
+    the residual it cycled on (RES), whole, and a fixed seeded sample of the assembled fine-level operator (value, row, column), which is
+    too large to write whole.  About 47 MB at the default size."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "correction.npy"), pb.EPSC.to_numpy())
+    np.save(os.path.join(d, "residual.npy"), pb.RES.to_numpy())
+    A = pb.A[-1]
+    rp, col = A.pattern()
+    val = A.values()
+    pick = np.unique(np.random.default_rng(20240607).integers(0, A.nnz, min(A.nnz, 1 << 19)))
+    np.save(os.path.join(d, "operator_sample_values.npy"), val[pick])
+    np.save(os.path.join(d, "operator_sample_rows.npy"), (np.searchsorted(rp, pick, side="right") - 1).astype(np.float64))
+    np.save(os.path.join(d, "operator_sample_cols.npy"), col[pick].astype(np.float64))
+
+
+def full_report(out, args, ctx, comm, pb, barrier, rank, world, device, ndof_total, ms_per_step):
+    """--full: everything beside the headline, after the timed steps and into the same line -- sub-phase timings, the whole MGsolve, the
+    roofline kernels alone, halo exchanges (N > 1), the known-answer test, counter traffic and the CPU baseline"""
+    import numpy as np
+    ndof = pb.ndof_owned
+    nel = pb.nel_local
+    A = pb.A[-1]
+    parallelism = out["config"]["parallelism"]
 
     # ---- sub-phase timings with HIP events on the library's compute stream --------------------------------------
     reps = max(3, args.steps)
@@ -288,28 +364,7 @@ def main():
     ai = pb.asm_top.info(colors=False)
     fused = pb.asm_top.fused_info()
 
-    out = {
-        "metric": "assembled DOFs/sec + V-cycle SpMV GB/s (% HBM peak), 3D Poisson Q2",
-        "value": value,
-        "unit": "DOF/s (assembly + one V(2,2) cycle per step)",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": "3D Poisson Q2 (HEX27, 64-pt Gauss) on %d^3 box per GPU, %d-level GMG V(2,2) Jacobi(2/3), Galerkin coarse "
-                        "operators, dense exact coarse solve" % (args.coarse * 2 ** (args.levels - 1), args.levels),
-            "dofs_total": ndof_total,
-            "dofs_this_gpu": ndof,
-            "elements_this_gpu": nel,
-            "nnz_fine_this_gpu": A.nnz,
-            "parallelism": parallelism,
-        },
+    out.update({
         "assembled_dofs_per_sec": ndof_total / (asm_full_ms * 1e-3),
         "assembly_ms": asm_full_ms,
         "assembly_element_loop_ms": asm_ms,
@@ -320,16 +375,9 @@ def main():
         "vcycle_pct_hbm_peak": cyc_bytes / cyc_ms / 1e6 / HBM_PEAK_GBPS * 100.0,
         "vcycle_spmv_GBps": spmv_bytes / spmv_ms / 1e6,
         "vcycle_spmv_pct_hbm_peak": spmv_bytes / spmv_ms / 1e6 / HBM_PEAK_GBPS * 100.0,
-        "prepare_ms": pb.prepare_ms,
-        "coarse_solve": dict(zip(("dense_unknowns", "dissection_blocks", "separator", "largest_block"), pb.mg.coarse_info()),
-                             what="exact solve of the coarsest level: unknowns coupled to nothing by their diagonal, the rest dense -- dissected into interior blocks "
-                                  "inverted beside each other + a separator Schur complement (dissection_blocks 0: one dense inverse)"),
         "solve_ms": solve["solve_ms"],
         "solve": solve,
         "vcycle_host_issue_ms": host_issue_ms,
-        "runtime_libraries": femus_amd.loaded_runtimes(),
-        "prepare_first_s": pb.prepare_first_s,
-        "setup_s": setup_s,
         "roofline": {
             "kernel": "k_spmv_lx<2048,3,true> (fine-level fused Jacobi sweep x+w*Dinv*(b-Ax), LDS-staged x)",
             "bound": "hbm",
@@ -396,12 +444,10 @@ def main():
             "second_pass_traffic": TRAFFIC["asm"]["rows"] if world == 1 else None,
             "traffic_from_profile": TRAFFIC["asm"]["source"] if world == 1 else None,
         },
-    }
+    })
 
     if halo_info is not None:
         out["halo"] = halo_info
-    if preflight is not None:
-        out["rccl_preflight"] = preflight          # what the RCCL preflight children of every rank said (ok / message / seconds)
 
     # ---- the reference's own known-answer test through the device path (rank 0, N = 1; after the timed region, not part of `value`) --------
     if rank == 0 and world == 1 and not args.no_known_answer:
@@ -456,11 +502,6 @@ def main():
                 out["cpu_baseline"] = cb
         except (OSError, ValueError, KeyError):
             pass                                   # no N=1 run on this host before this one: the line carries no cpu_baseline
-
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    comm.barrier()
-    comm.close()
 
 
 def halo_report(ctx, comm, pb):
@@ -558,7 +599,7 @@ class SerialProblem:
         ctx.sync()
         self.prepare_ms = (time.time() - t0) * 1e3
         self.pb = pb
-        self.A, self.mg, self.RES = pb.A, pb.mg, pb.RES
+        self.A, self.mg, self.RES, self.EPSC = pb.A, pb.mg, pb.RES, pb.EPSC
         self.ndof_owned, self.nel_local = pb.ndof[-1], pb.meshes[-1].nel
         self.asm_top = pb.asm[-1]
         self._bdc = pb.bdc[-1]

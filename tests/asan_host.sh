@@ -10,11 +10,11 @@ make -s -C $ROOT/femus_amd/csrc -j8
 objs=""
 for f in $ROOT/femus_amd/csrc/*.cpp; do
   o=$OUT/$(basename $f).o
-  /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I$ROOT/include -fsanitize=address,undefined \
+  /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I$ROOT/include -fsanitize=address,undefined -fno-gpu-sanitize \
       -fno-sanitize=vptr -fno-omit-frame-pointer -c $f -o $o
   objs="$objs $o"
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -shared-libsan -o $OUT/libfemus_hip.so \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -fno-gpu-sanitize -shared-libsan -o $OUT/libfemus_hip.so \
     $(ls $ROOT/femus_amd/lib/obj/*.o | grep -v "\.cpp\.o$") $objs -lpthread -L/opt/rocm/lib -lrccl
 shift 0
 cd $ROOT

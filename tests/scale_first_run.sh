@@ -7,7 +7,7 @@
 #    (what tests/test_gpu_dd.py::test_config3_shape_at_full_size... checks over the host transport), N <= 2 on one GPU's memory for the reference
 #    solve, larger N at nb = 4;
 # 3  the general (native) partitioner with adaptive levels over RCCL against the single-GPU solve of the same hierarchy;
-# 4  bench.py --gpus N: the line carries halo.by_rank (exchange / exposed / all-reduce ms per rank), vcycle_host_issue_ms, rccl_preflight.
+# 4  bench.py --gpus N --full: the line carries halo.by_rank (exchange / exposed / all-reduce ms per rank), vcycle_host_issue_ms, rccl_preflight.
 N=${1:-8}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/scale_first_run
@@ -32,8 +32,8 @@ echo "general partition over RCCL: rc $? $(grep '^{' $OUT/general_rccl.log | tai
 # ---- 4: the bench, as the driver launches it ----
 for n in 1 2 4 8; do
   [ $n -gt $N ] && break
-  if [ $n -eq 1 ]; then timeout 900 python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
-  else timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((PORT + 7 + n)) bench.py --gpus $n > $OUT/bench_n$n.json 2> $OUT/bench_n$n.err; fi
+  if [ $n -eq 1 ]; then timeout 900 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+  else timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((PORT + 7 + n)) bench.py --gpus $n --full > $OUT/bench_n$n.json 2> $OUT/bench_n$n.err; fi
   python - <<PY | tee -a $OUT/summary.txt
 import json
 try:

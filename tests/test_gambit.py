@@ -9,6 +9,7 @@ from femus_amd import capi
 from oracle import femus_oracle as fo
 
 from gambit_writer import write_neu
+from reference_files import reference_file
 
 
 @pytest.mark.parametrize("box", [(3, 2, 0), (2, 3, 2)])
@@ -85,12 +86,11 @@ def test_reader_orders_elements_by_material_then_group(tmp_path):
     m.destroy()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
 def test_reader_on_the_curved_mesh_of_testNSSteadyDD():
     """unittests/testNSSteadyDD/input/nsbenc.neu (the mesh behind the reference's stored norms, main.cpp:202-244): 98 curved QUAD9
     elements around a cylinder, 3 element groups, 4 boundary sets -- every element comes out right-handed in FEMuS local order with
     edge nodes between their vertices, every node belongs to an element, and the boundary faces are exactly the faces met once"""
-    m = capi.Mesh.read_gambit(os.path.join(os.path.dirname(REF), "unittests/testNSSteadyDD/input/nsbenc.neu"))
+    m = capi.Mesh.read_gambit(reference_file("unittests/testNSSteadyDD/input/nsbenc.neu"))
     ed, xy, ff = m.arrays()
     assert (m.nel, m.nnode, m.dim) == (98, 442, 2)
     assert set(np.unique(ff).tolist()) == {-5, -4, -3, -2, -1}                        # sets 1..4 -> flags -2..-5 (GambitIO.cpp:337)

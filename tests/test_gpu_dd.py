@@ -291,7 +291,7 @@ def test_bench_contract_with_two_ranks_sharing_the_gpu(tmp_path, transport):
     env = dict(os.environ, FEMUS_BENCH_TRANSPORT=transport, FEMUS_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1", TMPDIR=str(tmp_path))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--coarse", "2", "--levels", "3", "--kernel-reps", "3"]
+           "--coarse", "2", "--levels", "3", "--kernel-reps", "3", "--full"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -321,7 +321,7 @@ def test_bench_spawns_its_own_ranks_and_never_reports_fewer(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    small = ["--steps", "2", "--warmup", "1", "--coarse", "2", "--levels", "3", "--kernel-reps", "3", "--no-live-traffic"]
+    small = ["--steps", "2", "--warmup", "1", "--coarse", "2", "--levels", "3", "--kernel-reps", "3", "--no-live-traffic", "--full"]
     env = dict(os.environ, TMPDIR=str(tmp_path))
     env.pop("WORLD_SIZE", None)
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + small, env=env, cwd=root, capture_output=True, text=True, timeout=600)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import femus_oracle_mixed as om
+from reference_files import reference_file
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 MESH = os.path.join(HERE, "golden", "cube_all_shapes_Six_boundary_groups.neu")
@@ -29,10 +30,7 @@ def volume(kind, ed, xs):
 
 
 def test_the_mesh_file_is_the_application_s():
-    ref_file = "/root/reference/applications/001_Poisson/input/cube_all_shapes_Six_boundary_groups.neu"
-    if not os.path.exists(ref_file):
-        pytest.skip("the reference tree is not here")
-    assert open(ref_file, "rb").read() == open(MESH, "rb").read()
+    assert reference_file("applications/001_Poisson/input/cube_all_shapes_Six_boundary_groups.neu") == MESH
 
 
 def test_oracle_reader_and_refinement_and_the_product_s_mesh_code():
@@ -295,9 +293,7 @@ def test_two_dimensional_gambit_files_reader_refinement_and_the_product_s_mesh_c
     doubled per level and lying on the boundary; femus_amd/mixed_mesh.py gives the oracle's integers (coordinates to rounding) on three levels"""
     from femus_amd import mixed_mesh
     path = os.path.join(HERE, "golden", name)
-    ref_file = "/root/reference/" + MESH_2D[name]
-    if os.path.exists(ref_file):
-        assert open(ref_file, "rb").read() == open(path, "rb").read()
+    assert reference_file(MESH_2D[name]) == path
     kind, ed, xs, ff, own = om.read_gambit(path)
     assert xs.shape[1] == 2 and set(kind.tolist()) <= {"quad", "tri"}
     for e in np.nonzero(kind == "tri")[0]:

@@ -5,8 +5,9 @@ import numpy as np
 import pytest
 
 from femus_amd import capi
+from reference_files import reference_file
 
-REF_INPUT = "/root/reference/applications/001_Poisson/input/cube_Hex.neu"
+REF_INPUT = reference_file("applications/001_Poisson/input/cube_Hex.neu")
 
 
 def shuffled_box(n, seed):
@@ -85,7 +86,6 @@ def test_topological_keys_agree_with_coordinates(n, nparts, nlev):
         assert len(set(ks)) == len(ks)                                     # different points, different keys
 
 
-@pytest.mark.skipif(not os.path.exists(REF_INPUT), reason="reference inputs are only present in the build container")
 def test_gambit_mesh_can_be_partitioned_and_cut():
     g = capi.Mesh.read_gambit(REF_INPUT)
     part = g.partition(2)

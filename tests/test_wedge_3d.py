@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import femus_oracle_wedge as ow
+from reference_files import reference_file
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 MESH = os.path.join(HERE, "golden", "cube_Wedge.neu")
@@ -33,10 +34,7 @@ def test_oracle_prism_basis_is_the_reference_s(fe):
 
 
 def test_the_mesh_file_is_the_application_s():
-    ref_file = "/root/reference/applications/001_Poisson/input/cube_Wedge.neu"
-    if not os.path.exists(ref_file):
-        pytest.skip("the reference tree is not here")
-    assert open(ref_file, "rb").read() == open(MESH, "rb").read()
+    assert reference_file("applications/001_Poisson/input/cube_Wedge.neu") == MESH
 
 
 def test_oracle_reader_and_refinement_and_the_product_s_mesh_code():
