@@ -72,12 +72,11 @@ class Poisson001:
         cfg = config if isinstance(config, dict) else load_config(config)
         self.cfg = cfg
         mesh_type = get(cfg, "multilevel_mesh.first.type", {})
-        self.mesh_file = None
+        self.mesh_file, self.geom = None, None            # geom: the element path of a mesh femus_amd/mixed_mesh.py builds; None: the library's mesh code
         if "filename" in mesh_type:
             self.mesh_file = os.path.join(base_dir, mesh_type["filename"]) if base_dir else mesh_type["filename"]
-            kind = self._gambit_kind(self.mesh_file)                       # cube_Tet.neu / cube_Wedge.neu of input3D_Tet_* / _Wedge_*.json: host-side mesh code
-            self.tet, self.wedge, self.mixed = kind == "tet10", kind == "wedge18", kind == "mixed"
-            if self.tet or self.wedge or self.mixed:
+            self.geom = self._gambit_kind(self.mesh_file)
+            if self.geom is not None:
                 with open(self.mesh_file) as f:
                     tok = f.read().split()
                 self.dim = int(tok[tok.index("NDFVL") + 5])
@@ -94,7 +93,8 @@ class Poisson001:
             self.dim = 1 if (self.box[1] == 0 and self.box[2] == 0) else 2 if self.box[2] == 0 else 3
             if self.dim == 2:
                 self.hi = (self.hi[0], self.hi[1], 1.0)         # the box generator ignores z in 2-D
-            self.tri = self.dim == 2 and b.get("elem_type", "Quad9") == "Tri6"            # MeshGeneration.cpp:568-: the box cut into triangles
+            if self.dim == 2 and b.get("elem_type", "Quad9") == "Tri6":                   # MeshGeneration.cpp:568-: the box cut into triangles
+                self.geom = "tri"
             if self.dim == 1:
                 assert b.get("elem_type", "Edge3") == "Edge3", "the one-dimensional box is made of EDGE3 elements (MeshGeneration.cpp:90)"
         else:
@@ -163,14 +163,8 @@ class Poisson001:
             return self.run_line(log)
         # triangles, tetrahedra, prisms, mixed shapes: multicolour Gauss-Seidel by default -- the iteration counts of the natural-order symmetric sweep the
         # application sets (SOR_PRECOND; simplex_smoother=capi.SMOOTH_SOR runs that one) at half the time on 240 k unknowns (tests/dev/probe_simplex_smoother.py)
-        if getattr(self, "tri", False):
-            return self.run_tri(log, simplex_smoother, simplex_omega)
-        if getattr(self, "tet", False):
-            return self.run_tet(log, simplex_smoother, simplex_omega)
-        if getattr(self, "wedge", False):
-            return self.run_wedge(log, simplex_smoother, simplex_omega)
-        if getattr(self, "mixed", False):
-            return self.run_mixed(log, simplex_smoother, simplex_omega)
+        if self.geom is not None:
+            return self.run_elements(log, simplex_smoother, simplex_omega)
         meshes = [capi.Mesh.box(*self.box, self.lo, self.hi) if self.box is not None else capi.Mesh.read_gambit(self.mesh_file)]
         for _ in range(1, self.nlevels):
             meshes.append(meshes[-1].refine())
@@ -219,94 +213,67 @@ class Poisson001:
         pb.destroy()
         return result
 
-    # ---- a two-dimensional box of triangles ("elem_type" : "Tri6") ---------------------------------------------------------------------------------
-    def run_tri(self, log=None, smoother=capi.SMOOTH_GS_COLOR, omega=1.0):
-        """a TRI6 box (TRI7 inside, femus_amd/tri_mesh.py): all three Lagrange families; boundary conditions and source as for the quadrilateral box"""
-        from . import tri_mesh
-        levels = [tri_mesh.box(self.box[0], self.box[1], self.lo[:2], self.hi[:2])]
-        for _ in range(1, self.nlevels):
-            levels.append(tri_mesh.refine(*levels[-1][:3]))
-        fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
-        return self._run_simplex("tri", levels, (3, 6, 7)[fam], [own[fam] for (_, _, _, own) in levels], log, smoother, omega)
+    # the element path as flags: the TRI6 box, a file of TET10 alone, of WEDGE18 alone, any other file mixed_mesh.py reads
+    tri, tet, wedge, mixed = (property(lambda self, g=g: self.geom == g) for g in ("tri", "tet", "wedge", "mixed"))
 
     @staticmethod
     def _gambit_kind(path):
-        """the elements of the file's ELEMENTS/CELLS section: Gambit type 6 with 10 nodes (TET10), type 5 with 18 (WEDGE18), more than one shape or TRI6
-        ("mixed": cube_all_shapes*.neu, the two-dimensional files with triangles); None: the hexahedral / quadrilateral files the library's reader takes"""
+        """the element path of a Gambit file: None for HEX27 alone or QUAD9 alone (the library's reader); otherwise femus_amd/mixed_mesh.py reads it, and
+        "tet" / "wedge" (TET10 / WEDGE18 alone: that shape's kernel) or "mixed" (every other file: several shapes, the two-dimensional files with triangles; an
+        element the reader does not serve is named there and refused)"""
+        from . import mixed_mesh
         with open(path) as f:
             tok = f.read().split()
         if "ELEMENTS/CELLS" not in tok or "NDFVL" not in tok:
             return None
-        nel, ngroup = int(tok[tok.index("NDFVL") + 2]), int(tok[tok.index("NDFVL") + 3])
+        nel = int(tok[tok.index("NDFVL") + 2])
         p = tok.index("ELEMENTS/CELLS") + 2
         seen = set()
         for _ in range(nel):
-            seen.add((tok[p + 1], tok[p + 2]))
+            seen.add(mixed_mesh.GAMBIT.get((int(tok[p + 1]), int(tok[p + 2]))))
             p += 3 + int(tok[p + 2])
-        if len(seen) > 1:
-            return "mixed"
-        kind = {("6", "10"): "tet10", ("5", "18"): "wedge18", ("3", "6"): "mixed"}.get(seen.pop())         # (TRI6 files go through the mixed-shape reader)
-        return "mixed" if (kind is not None and ngroup > 1) else kind       # (and so do files with several element groups: it orders the elements by them)
+        if seen in ({"hex"}, {"quad"}):
+            return None
+        return seen.pop() if seen in ({"tet"}, {"wedge"}) else "mixed"
 
-    def run_mixed(self, log=None, smoother=capi.SMOOTH_GS_COLOR, omega=1.0):
-        """a Gambit mesh of mixed shapes (input3D.json / input3D_All_first.json with input/cube_all_shapes_Six_boundary_groups.neu: tetrahedra, prisms and
-        hexahedra; two-dimensional files of QUAD9 and TRI6 elements, or TRI6 alone; femus_amd/mixed_mesh.py): the three Lagrange families; the boundary
-        conditions of the application's SetBoundaryCondition"""
+    def run_elements(self, log=None, smoother=capi.SMOOTH_GS_COLOR, omega=1.0):
+        """LinearImplicitSystem::MGsolve on the meshes femus_amd/mixed_mesh.py builds, in all three Lagrange families: the TRI6 box (TRI7 inside; the box's
+        boundary conditions and source), Gambit files of TET10 (input3D_Tet_*.json with input/cube_Tet.neu; TET15 inside), of WEDGE18 (input3D_Wedge_*.json with
+        input/cube_Wedge.neu; WEDGE21 inside), of mixed shapes (input3D.json / input3D_All_first.json with input/cube_all_shapes_Six_boundary_groups.neu:
+        tetrahedra, prisms and hexahedra) and the two-dimensional files of QUAD9 and / or TRI6 (the boundary conditions of the application's SetBoundaryCondition:
+        Dirichlet 0, flux 0.2 on face name 3).  The Poisson callback through the generic kernel on the finest level (fh_assemble_poisson_rows for the box and
+        the tetrahedral / prism files, fh_assemble_poisson_mixed on the mixed path, elem_dof rows padded with -1), transfers from the element prolongators,
+        Galerkin operators below.
+        result["levels"]: (ed, xs, ff) of every level; ed and ff as wide as the shape, or padded to 27 and 6 on the mixed path"""
         from . import mixed_mesh
-        levels = [mixed_mesh.read_gambit(self.mesh_file)]
+        ctx = self.ctx
+        levels = [mixed_mesh.tri_box(self.box[0], self.box[1], self.lo[:2], self.hi[:2]) if self.box is not None else mixed_mesh.read_gambit(self.mesh_file)]
         for _ in range(1, self.nlevels):
             levels.append(mixed_mesh.refine(*levels[-1][:4]))
+        if not self.mixed:
+            g = self.geom
+            levels = [(kind, ed[:, :mixed_mesh.NLOC[g]], xs, ff[:, :mixed_mesh.NFACES[g]], own) for kind, ed, xs, ff, own in levels]
+        shapes = sorted(set(levels[0][0].tolist()))
+        dim = levels[0][2].shape[1]
         fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
-        return self._run_simplex("mixed", [l[1:] for l in levels], None, [l[4][fam] for l in levels], log, smoother, omega, kinds=[l[0] for l in levels])
-
-    def run_wedge(self, log=None, smoother=capi.SMOOTH_GS_COLOR, omega=1.0):
-        """a Gambit mesh of WEDGE18 elements (input3D_Wedge_first / _second / _serendipity.json with input/cube_Wedge.neu; femus_amd/wedge_mesh.py: WEDGE21
-        inside): the three Lagrange families; the boundary conditions of the application's SetBoundaryCondition"""
-        from . import wedge_mesh
-        levels = [wedge_mesh.read_gambit(self.mesh_file)]
-        for _ in range(1, self.nlevels):
-            levels.append(wedge_mesh.refine(*levels[-1][:3]))
-        fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
-        return self._run_simplex("wedge", levels, (6, 15, 21)[fam], [own[fam] for (_, _, _, own) in levels], log, smoother, omega)
-
-    def run_tet(self, log=None, smoother=capi.SMOOTH_GS_COLOR, omega=1.0):
-        """a Gambit mesh of TET10 elements (input3D_Tet_first / _serendipity / _second.json with input/cube_Tet.neu; femus_amd/tet_mesh.py): P1, P2 and P2 with
-        face and volume bubbles (TET15); the boundary conditions of the application's SetBoundaryCondition (Dirichlet 0, flux 0.2 on face name 3)"""
-        from . import tet_mesh
-        levels = [tet_mesh.read_gambit(self.mesh_file)]
-        for _ in range(1, self.nlevels):
-            levels.append(tet_mesh.refine(*levels[-1][:3]))
-        fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
-        return self._run_simplex("tet", levels, (4, 10, 15)[fam], [own[fam] for (_, _, _, own) in levels], log, smoother, omega)
-
-    def _run_simplex(self, geom, levels, nc, ndofs, log, smoother, omega, kinds=None):
-        """LinearImplicitSystem::MGsolve on meshes this module keeps (triangles, tetrahedra, prisms, mixed shapes): the Poisson callback through the generic kernel
-        on the finest level (fh_assemble_poisson_rows / _mixed), transfers from the element prolongator, Galerkin operators below, V-cycles under GMRES limited to
-        4 iterations per linear iteration.  kinds[l][e] (mixed meshes): the shape of every element of level l; elem_dof rows padded with -1"""
-        ctx = self.ctx
-        dim = levels[0][1].shape[1]
-        fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
-        NF = {"tri": 3, "tet": 4, "wedge": 5, "hex": 6, "quad": 4}
-        CL = {"tri": (3, 6, 7), "tet": (4, 10, 15), "wedge": (6, 15, 21), "hex": (8, 20, 27), "quad": (4, 8, 9)}
-        shapes = [geom] if kinds is None else sorted(set(kinds[0].tolist()))
-        fn_by = {s: [capi.fe_face_nodes(s, self.fe, f) for f in range(NF[s])] for s in shapes}
-        shape_of = (lambda l, e: geom) if kinds is None else (lambda l, e: kinds[l][e])
-        groups = [[(geom, np.arange(lv[0].shape[0]))] if kinds is None else [(s, np.nonzero(kinds[l] == s)[0]) for s in shapes] for l, lv in enumerate(levels)]
+        fn_by = {s: [capi.fe_face_nodes(s, self.fe, f) for f in range(mixed_mesh.NFACES[s])] for s in shapes}
+        groups = [[(s, np.nonzero(lv[0] == s)[0], mixed_mesh.CLASSES[s][fam]) for s in shapes] for lv in levels]     # (shape, its elements, dofs per element)
+        ndofs = [lv[4][fam] for lv in levels]
         top = self.nlevels - 1
-        ed, xs, ff, _ = levels[top]
+        kind, ed, xs, ff, _ = levels[top]
         ndof = ndofs[top]
-        K = self._pattern_from_elements([ed[idx][:, :CL[s][fam]] for s, idx in groups[top]], ndof)
-        SOL, RES, EPS = ctx.vector(ndof), ctx.vector(ndof), ctx.vector(ndof)
+        K = self._pattern_from_elements([ed[idx][:, :nc] for _, idx, nc in groups[top]], ndof)
+        SOL, RES = ctx.vector(ndof), ctx.vector(ndof)
         sol0 = np.zeros(ndof)
         bdc = []
         flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals = [], [], [], [], []
-        for l, (edl, xl, ffl, _) in enumerate(levels):
+        for l, (kl, edl, xl, ffl, _) in enumerate(levels):
             val = {}
             for iel, f in zip(*np.nonzero(ffl < -1)):               # elements and faces in order; a later face overwrites an earlier one (GenerateBdc)
                 flag = int(ffl[iel, f])
-                kind, fn = self.face_bc(flag)
-                nodes = edl[iel, fn_by[shape_of(l, iel)][f]]
-                if kind == "dirichlet":
+                kind_bc, fn = self.face_bc(flag)
+                nodes = edl[iel, fn_by[kl[iel]][f]]
+                if kind_bc == "dirichlet":
                     for node in nodes:
                         x4 = np.zeros(4)
                         x4[:dim] = xl[node]
@@ -324,24 +291,14 @@ class Poisson001:
             bdc.append(idx)
             if l == top:
                 sol0[idx] = [val[i] for i in idx]
-        P = [None] + [self._prolongator_from_children([(s, idx, CL[s][fam]) for s, idx in groups[l - 1]], levels[l - 1][0], levels[l][0], ndofs[l - 1], ndofs[l])
-                      for l in range(1, self.nlevels)]
-        for l in range(1, self.nlevels):
-            if bdc[l].size:
-                P[l].mat_zero_rows(bdc[l], 0.0)
-            if bdc[l - 1].size:
-                P[l].zero_cols(bdc[l - 1])
+        P = [None] + [self._prolongator_from_children(groups[l - 1], levels[l - 1][1], levels[l][1], ndofs[l - 1], ndofs[l]) for l in range(1, self.nlevels)]
         SOL.upload(sol0)
-        mg = capi.Multigrid(ctx, self.nlevels)
-        A = [None] * self.nlevels
-        A[top] = K
-        history = []
-        its = 0
-        for it in range(self.max_linear + 1):
-            if kinds is None:
-                capi.assemble_poisson_rows(ctx, geom, self.fe, ed, xs, K, RES, sol=SOL, source=self.source, scale=1.0)
+
+        def assemble():
+            if not self.mixed:
+                capi.assemble_poisson_rows(ctx, self.geom, self.fe, ed, xs, K, RES, sol=SOL, source=self.source, scale=1.0)
             else:
-                capi.assemble_poisson_mixed(ctx, self.fe, kinds[top], ed, xs, K, RES, sol=SOL, source=self.source, scale=1.0)
+                capi.assemble_poisson_mixed(ctx, self.fe, kind, ed, xs, K, RES, sol=SOL, source=self.source, scale=1.0)
             if flux_faces:
                 capi.assemble_neumann_edges(ctx, self.fe, np.array(flux_faces), np.array(flux_idx), flux_exprs, xs, RES)
             if tau_faces:                                             # by kind of face (a prism has quadrilaterals and triangles): the face element named
@@ -349,6 +306,31 @@ class Poisson001:
                     sel = [k for k, f in enumerate(tau_faces) if len(f) == nn]
                     fgeom = "lineface" if dim == 2 else "triface" if nn in (3, 6, 7) else "quadface"
                     capi.assemble_neumann_faces(ctx, fgeom, self.fe, np.array([tau_faces[k] for k in sel]), np.array([tau_vals[k] for k in sel]), xs, RES)
+
+        history = self._mgsolve(K, P, bdc, SOL, RES, assemble, log, smoother, omega)
+        return {"solution": SOL.to_numpy(), "coords": xs[:ndof], "history": history, "converged": history[-1][1] < self.abs_tol, "dofs": ndof,
+                "levels": [lv[1:4] for lv in levels]}
+
+    def _mgsolve(self, K, P, bdc, SOL, RES, assemble, log, smoother, omega):
+        """LinearImplicitSystem::MGsolve on a hierarchy built here: K the finest level's matrix, P[l] the transfer into level l (P[0] None), bdc[l] the Dirichlet
+        dofs of level l, assemble() the callback that fills K and RES at SOL.  Rows of fine Dirichlet dofs and columns of coarse ones carry nothing in P
+        (ZeroInterpolatorDirichletNodes).  Every linear iteration: the callback, the boundary rows, ||RES||_2 (stop below abs_conv_tol after the first, or after
+        max_number_linear_iteration), the Galerkin chain PP^T KK PP and the boundary rows of every level, V-cycles under GMRES limited to 4 iterations (one level:
+        the exact solve), SOL += EPS.  Returns the history [(Krylov steps, ||RES||_2)]; K and P are destroyed"""
+        top = self.nlevels - 1
+        for l in range(1, self.nlevels):
+            if bdc[l].size:
+                P[l].mat_zero_rows(bdc[l], 0.0)
+            if bdc[l - 1].size:
+                P[l].zero_cols(bdc[l - 1])
+        EPS = self.ctx.vector(RES.n_global)
+        mg = capi.Multigrid(self.ctx, self.nlevels)
+        A = [None] * self.nlevels
+        A[top] = K
+        history = []
+        its = 0
+        for it in range(self.max_linear + 1):
+            assemble()
             if bdc[top].size:
                 K.mat_zero_rows(bdc[top], 1.0)
                 RES.set(bdc[top], np.zeros(bdc[top].size))
@@ -373,12 +355,10 @@ class Poisson001:
             its, _ = mg.solve(RES, EPS, outer="gmres" if self.nlevels > 1 else "preonly", rtol=1e-12, atol=1e-20, maxit=4)
             SOL.add(1.0, EPS)
         mg.destroy()
-        result = {"solution": SOL.to_numpy(), "coords": xs[:ndof], "history": history, "converged": history[-1][1] < self.abs_tol, "dofs": ndof,
-                  "levels": [(l[0], l[1], l[2]) for l in levels]}
         for m in A + P:
             if m is not None:
                 m.destroy()
-        return result
+        return history
 
     def _pattern_from_elements(self, eds, ndof):
         """CSR pattern holding every (i, j) of every element; eds: one elem_dof array per shape.  Built on the device (fh_mat_create_from_elements) from one table
@@ -474,27 +454,10 @@ class Poisson001:
         ffaces = {flag: (2 * e + f, f) for flag, (e, f) in faces.items()}
         return new[raw], xf, ffaces, nel * 2 + 1
 
-    def line_prolongator(self, ed_c, ed_f, ndof_c, ndof_f):
-        """PP of a level (Mesh / FE prolongator, ElemType.cpp:439-532 on the line): row of fine dof = coarse shape functions at its reference point in the father"""
-        nc = 2 if self.fe == "linear" else 3
-        EP = capi.fe_elem_prolongator("line", self.fe)
-        P = {}
-        for e in range(ed_c.shape[0]):
-            for j in range(2):
-                for n in range(nc):
-                    row = int(ed_f[2 * e + j, n])
-                    for k in range(nc):
-                        if EP[j, n, k] != 0.0:
-                            P[(row, int(ed_c[e, k]))] = EP[j, n, k]
-        keys = sorted(P)
-        rows = np.array([q[0] for q in keys])
-        indptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=ndof_f))])
-        return capi.Mat.from_csr(self.ctx, ndof_f, ndof_c, indptr, np.array([q[1] for q in keys]), np.array([P[q] for q in keys]))
-
     def run_line(self, log=None, smoother=capi.SMOOTH_SOR, omega=1.0):
         """LinearImplicitSystem::MGsolve on the EDGE3 box with the callback's one-dimensional form (fh_assemble_advdiff_line) on the finest level, Galerkin
-        operators below it (PP^T KK PP), V-cycles under GMRES limited to 4 iterations per linear iteration; one level (the shipped input): the exact solve.
-        smoother / omega: Richardson + SOR_PRECOND as main.cpp:240-242 sets them (scale 1 here: the natural-order sweep of a one-dimensional operator)"""
+        operators below it, transfers from the line's element prolongator; one level (the shipped input): the exact solve.  smoother / omega: Richardson +
+        SOR_PRECOND as main.cpp:240-242 sets them (scale 1 here: the natural-order sweep of a one-dimensional operator)"""
         ctx = self.ctx
         levels = [self.line_mesh()]
         for _ in range(1, self.nlevels):
@@ -508,7 +471,7 @@ class Poisson001:
         rows = np.array([p[0] for p in pairs])
         indptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=ndof))])
         K = capi.Mat.from_csr(ctx, ndof, ndof, indptr, np.array([p[1] for p in pairs]))
-        SOL, RES, EPS = ctx.vector(ndof), ctx.vector(ndof), ctx.vector(ndof)
+        SOL, RES = ctx.vector(ndof), ctx.vector(ndof)
         sol0 = np.zeros(ndof)
         bdc, point_flux = [[] for _ in levels], []
         for flag in faces:
@@ -525,54 +488,21 @@ class Poisson001:
                     elif fn is not None:                      # non-homogeneous Neumann: the side "element" is a point, F[node] += g(x) (main.cpp:540-549)
                         point_flux.append((node, fn(x4)))
         bdc = [np.array(sorted(b), dtype=np.int32) for b in bdc]
-        P = [None] + [self.line_prolongator(levels[l - 1][0], levels[l][0], ndofs[l - 1], ndofs[l]) for l in range(1, self.nlevels)]
-        for l in range(1, self.nlevels):                      # rows of fine Dirichlet dofs and columns of coarse ones carry nothing (ZeroInterpolatorDirichletNodes)
-            if bdc[l].size:
-                P[l].mat_zero_rows(bdc[l], 0.0)
-            if bdc[l - 1].size:
-                P[l].zero_cols(bdc[l - 1])
+        P = [None] + [self._prolongator_from_children([("line", np.arange(levels[l - 1][0].shape[0]), nc)], levels[l - 1][0], levels[l][0], ndofs[l - 1], ndofs[l])
+                      for l in range(1, self.nlevels)]
         SOL.upload(sol0)
-        mg = capi.Multigrid(ctx, self.nlevels)
-        A = [None] * self.nlevels
-        A[top] = K
-        history = []
-        for it in range(self.max_linear + 1):
+
+        def assemble():
             capi.assemble_advdiff_line(ctx, self.fe, ed, xs, K, RES, self.NU_1D, self.V_1D, sol=SOL, source=self.source)
             if point_flux:
                 r = RES.to_numpy()
                 for node, g in point_flux:
                     r[node] += g
                 RES.upload(r)
-            if bdc[top].size:
-                K.mat_zero_rows(bdc[top], 1.0)
-                RES.set(bdc[top], np.zeros(bdc[top].size))
-            rn = RES.l2_norm()
-            history.append((0, rn) if it == 0 else (its, rn))
-            if log:
-                log("linear iteration %d: Linear Res L2norm = %.6e" % (it, rn))
-            if (it > 0 and rn < self.abs_tol) or it == self.max_linear:
-                break
-            for l in range(top, 0, -1):                       # Galerkin chain, then the boundary rows of every level
-                if A[l - 1] is None:
-                    A[l - 1] = capi.Mat.ptap(P[l], A[l])
-                else:
-                    A[l - 1].ptap_numeric(P[l], A[l])
-            for l in range(top):
-                if bdc[l].size:
-                    A[l].mat_zero_rows(bdc[l], 1.0)
-            for l in range(self.nlevels):
-                mg.set_level(l, A[l], P[l], None, smoother, omega, self.npre if l > 0 else 1, self.npost if l > 0 else 0)
-            mg.setup()
-            EPS.zero()
-            its, _ = mg.solve(RES, EPS, outer="gmres" if self.nlevels > 1 else "preonly", rtol=1e-12, atol=1e-20, maxit=4)
-            SOL.add(1.0, EPS)
-        mg.destroy()
-        result = {"solution": SOL.to_numpy(), "coords": xs[:ndof].reshape(-1, 1), "history": history, "converged": history[-1][1] < self.abs_tol, "dofs": ndof,
-                  "elem_dof": ed, "nodes": xs, "levels": [(l[0], l[1]) for l in levels]}
-        for m in A + P:
-            if m is not None:
-                m.destroy()
-        return result
+
+        history = self._mgsolve(K, P, bdc, SOL, RES, assemble, log, smoother, omega)
+        return {"solution": SOL.to_numpy(), "coords": xs[:ndof].reshape(-1, 1), "history": history, "converged": history[-1][1] < self.abs_tol, "dofs": ndof,
+                "elem_dof": ed, "nodes": xs, "levels": [(l[0], l[1]) for l in levels]}
 
     def destroy(self):
         for e in list(self.bc_func.values()) + [self.source]:

@@ -1,19 +1,21 @@
-"""Meshes of MIXED shapes of applications/001_Poisson (input/cube_all_shapes*.neu: hexahedra, tetrahedra and prisms in one Gambit file) and the two-dimensional
-Gambit files of quadrilaterals and / or triangles the reference tree holds (QUAD9 + TRI6 in one file, TRI6 alone) on the host -- integers and coordinates only; all
-numerics run in libfemus_hip.so.  A mesh is (kind[nel] of "hex" / "tet" / "wedge" / "quad" / "tri", ed[nel, 27] padded with -1, xs[nnode, dim], ff[nel, 6] padded
-with -1, own[3]).
+"""The meshes of applications/001_Poisson that the library's own mesh code does not build, on the host -- integers and coordinates only; all numerics run in
+libfemus_hip.so: Gambit files of tetrahedra, prisms, triangles, or of several shapes (input/cube_Tet.neu, cube_Wedge.neu, cube_all_shapes*.neu: hexahedra,
+tetrahedra and prisms in one file; the two-dimensional files of quadrilaterals and / or triangles the reference tree holds), and the TRI6 box.  A mesh is
+(kind[nel] of "hex" / "tet" / "wedge" / "quad" / "tri", ed[nel, 27] padded with -1, xs[nnode, dim], ff[nel, 6] padded with -1, own[3]).
 
     read_gambit   GambitIO.cpp:101-330: HEX27 (type 4), TET10 (type 6), WEDGE18 (type 5), QUAD9 (type 2), TRI6 (type 3) ordered by (material, group, file index) as Mesh.cpp:626-690 orders them, nodes through
                   GambitToFemusVertexIndex (:55-69), faces through GambitToFemusFaceIndex (:84-86), flag = -(set name) - 1;
                   Mesh::AddBiquadraticNodesNotInMeshFile (Mesh.cpp:1207-1333): a node per TRIANGLE face -- shared between a tetrahedron and a prism as well --,
                   created by the first element that holds it, then a centre per tetrahedron / prism / triangle; coordinates with the weights of Mesh.cpp:105-122
+    tri_box       MeshGeneration.cpp:283-650 (case 2, TRI6: lattice node i + j (2 nx + 1), two triangles per cell, faces named bottom / right / top / left = flags
+                  -2 .. -5), the centre Mesh::AddBiquadraticNodesNotInMeshFile adds (-1/9 of the vertices + 4/9 of the middles, Mesh.cpp:124)
     refine        MeshRefinement::RefineMesh: children 8 e + j (4 e + j in two dimensions) of the father's shape, vertices through each shape's fine2CoarseVertexMapping (read off the element
                   prolongator), new edge / face nodes shared between neighbours of any shape, coordinates by the creating child's element prolongator
     numbering     vertices, then edge middles, then the rest, each class in order of first appearance walking the elements
 """
 import numpy as np
 
-from . import _mesh_keys, capi
+from . import capi
 
 SHAPES = ("hex", "tet", "wedge", "quad", "tri")
 NLOC = {"hex": 27, "tet": 15, "wedge": 21, "quad": 9, "tri": 7}
@@ -23,7 +25,7 @@ GAMBIT = {(4, 27): "hex", (6, 10): "tet", (5, 18): "wedge", (2, 9): "quad", (3, 
 G2F = {"hex": (4, 16, 0, 15, 23, 11, 7, 19, 3, 12, 20, 8, 25, 26, 24, 14, 22, 10, 5, 17, 1, 13, 21, 9, 6, 18, 2), "tet": (0, 4, 1, 6, 5, 2, 7, 8, 9, 3),
        "wedge": (3, 11, 5, 9, 10, 4, 12, 17, 14, 15, 16, 13, 0, 8, 2, 6, 7, 1), "quad": (0, 4, 1, 5, 2, 6, 3, 7, 8), "tri": (0, 3, 1, 4, 2, 5)}
 GFACE = {"hex": (0, 4, 2, 5, 3, 1), "tet": (0, 1, 2, 3), "wedge": (2, 1, 0, 4, 3), "quad": (0, 1, 2, 3), "tri": (0, 1, 2)}
-# Mesh.cpp:105-122: weights of the file's nodes in the nodes the file does not hold (tetrahedron: four faces and the centre; prism: two triangles and the centre;
+# Mesh.cpp:105-124: weights of the file's nodes in the nodes the file does not hold (tetrahedron: four faces and the centre; prism: two triangles and the centre;
 # triangle: the centre)
 ADDED = {"tet": np.array([[-1. / 9., -1. / 9., -1. / 9., 0, 4. / 9., 4. / 9., 4. / 9., 0, 0, 0], [-1. / 9., -1. / 9., 0, -1. / 9., 4. / 9., 0, 0, 4. / 9., 4. / 9., 0],
                           [0, -1. / 9., -1. / 9., -1. / 9., 0, 4. / 9., 0, 0, 4. / 9., 4. / 9.], [-1. / 9., 0, -1. / 9., -1. / 9., 0, 0, 4. / 9., 4. / 9., 0, 4. / 9.],
@@ -32,6 +34,7 @@ ADDED = {"tet": np.array([[-1. / 9., -1. / 9., -1. / 9., 0, 4. / 9., 4. / 9., 4.
                             [0.] * 12 + [-1. / 9.] * 3 + [4. / 9.] * 3]),
          "tri": np.array([[-1. / 9.] * 3 + [4. / 9.] * 3])}
 COMPLETE = ("hex", "quad")                 # shapes whose file elements hold every biquadratic node
+_CLASSES = np.array([CLASSES[s] for s in SHAPES])         # [shape code][class]: the end of the class's local nodes
 _T = {}
 
 
@@ -49,21 +52,69 @@ def tables(shape):
     return _T[shape]
 
 
-_first_touch = _mesh_keys.first_touch
+def first_touch(keys):
+    """keys[n, w] integers (>= -2: -1 / -2 pad a short key).  Returns (id per row, index of the creating row per id): one id per distinct key row, numbered in
+    order of first appearance.  The columns are packed into as few 64-bit words as their range allows (an edge or a triangle of a mesh below two million nodes
+    is one word) and the words sorted; equal keys keep their order."""
+    keys = np.asarray(keys, dtype=np.int64)
+    n, w = keys.shape
+    base = int(keys.max()) + 3 if n else 3
+    words, cur, room = [], None, 1
+    for c in range(w):
+        col = keys[:, c] + 2
+        if cur is not None and room * base < (1 << 62):
+            cur = cur * base + col
+            room *= base
+        else:
+            if cur is not None:
+                words.append(cur)
+            cur, room = col, base
+    words.append(cur)
+    if len(words) == 1 and room * n < (1 << 63):             # the row index fits beside the key: one sort of distinct values
+        order = np.sort(words[0] * n + np.arange(n)) % n
+    else:
+        order = np.lexsort(words[::-1])
+    new = np.ones(n, dtype=bool)
+    new[1:] = False
+    for wd in words:
+        sw = wd[order]
+        new[1:] |= sw[1:] != sw[:-1]
+    group = np.cumsum(new) - 1
+    first = order[new]                                   # the creating row of every group (equal keys in row order: the smallest index of the group)
+    isfirst = np.zeros(n, dtype=bool)
+    isfirst[first] = True
+    rank = (np.cumsum(isfirst) - 1)[first]
+    ids = np.empty(n, dtype=np.int64)
+    ids[order] = rank[group]
+    owner = np.empty(first.size, dtype=np.int64)
+    owner[rank] = first
+    return ids, owner
 
 
-def _renumber(kind, raw, nnode):
+def _codes(kind):
+    """the index in SHAPES of every element's shape"""
+    code = np.zeros(len(kind), dtype=np.int64)
+    for i, s in enumerate(SHAPES):
+        code[kind == s] = i
+    return code
+
+
+def _renumber(code, raw, nnode):
     new = np.full(nnode, -1, dtype=np.int64)
-    col = np.arange(27)[None, :]
     lo = np.zeros((raw.shape[0], 1), dtype=np.int64)
     k, own = 0, []
     for c in range(3):
-        hi = np.array([CLASSES[s][c] for s in kind])[:, None]
-        seq = raw[(col >= lo) & (col < hi)]                   # element by element, local order
+        hi = _CLASSES[code, c][:, None]
+        w = int(hi.max())
+        col = np.arange(w)[None, :]
+        seq = raw[:, :w][(col >= lo) & (col < hi)]            # element by element, local order
         seq = seq[new[seq] < 0]
-        uniq, first = np.unique(seq, return_index=True)
-        order = np.argsort(first, kind="stable")
-        new[uniq[order]] = k + np.arange(uniq.size)
+        first = np.full(nnode, seq.size, dtype=np.int64)      # the position of every node's first appearance in seq
+        np.minimum.at(first, seq, np.arange(seq.size))
+        hit = np.zeros(seq.size + 1, dtype=bool)
+        hit[first] = True
+        uniq = seq[hit[:-1]]                                  # the class's nodes in order of first appearance
+        new[uniq] = k + np.arange(uniq.size)
         k += uniq.size
         own.append(k)
         lo = hi
@@ -115,7 +166,7 @@ def read_gambit(path, Lref=1.0, groups=False):
                 keys.append(sorted(raw[e, T["faces"][f][:3]].tolist()))
     nn = nvt
     if keys:
-        ids, _ = _first_touch(np.array(keys))
+        ids, _ = first_touch(np.array(keys))
         raw[ent_e, ent_l] = nn + ids
         nn += int(ids.max()) + 1
     for e in range(nel):
@@ -145,67 +196,114 @@ def read_gambit(path, Lref=1.0, groups=False):
         q += 10 + ngel
     order = np.lexsort((np.arange(nel), group, material))
     kind, raw, ff, group, material = kind[order], raw[order], ff[order], group[order], material[order]
-    new, own = _renumber(kind, raw, nn)
+    new, own = _renumber(_codes(kind), raw, nn)
     xs = np.empty_like(coords)
     xs[new] = coords
     out = (kind, _apply(new, raw), xs, ff, own)
     return out + (group, material) if groups else out
 
 
+def tri_box(nx, ny, lo, hi):
+    px = 2 * nx + 1
+    jj, ii = np.meshgrid(np.arange(2 * ny + 1), np.arange(px), indexing="ij")
+    xy = np.stack([(ii.ravel() / (2.0 * nx)) * (hi[0] - lo[0]) + lo[0], (jj.ravel() / (2.0 * ny)) * (hi[1] - lo[1]) + lo[1]], axis=1)
+    idx = lambda i, j: i + j * px
+    ed, ff = [], []
+    for j in range(0, 2 * ny, 2):
+        for i in range(0, 2 * nx, 2):
+            ed.append([idx(i, j), idx(i + 2, j), idx(i + 2, j + 2), idx(i + 1, j), idx(i + 2, j + 1), idx(i + 1, j + 1)])
+            ff.append([-2 if j == 0 else -1, -3 if i == 2 * (nx - 1) else -1, -1])
+            ed.append([idx(i, j), idx(i + 2, j + 2), idx(i, j + 2), idx(i + 1, j + 1), idx(i + 1, j + 2), idx(i, j + 1)])
+            ff.append([-1, -4 if j == 2 * (ny - 1) else -1, -5 if i == 0 else -1])
+    nel, n6 = len(ed), xy.shape[0]
+    raw = np.full((nel, 27), -1, dtype=np.int64)
+    raw[:, :6] = ed
+    raw[:, 6] = n6 + np.arange(nel)
+    centres = np.zeros((nel, 2))
+    for i in range(6):                                        # the sum in the order of Mesh.cpp:1316-1324
+        centres += xy[raw[:, i]] * ADDED["tri"][0][i]
+    coords = np.concatenate([xy, centres])
+    new, own = _renumber(np.full(nel, SHAPES.index("tri")), raw, coords.shape[0])
+    xs = np.empty_like(coords)
+    xs[new] = coords
+    fp = np.full((nel, 6), -1, dtype=np.int64)
+    fp[:, :3] = ff
+    return np.full(nel, "tri"), _apply(new, raw), xs, fp, own
+
+
 def refine(kind, ed, xs, ff):
     nel, dim = ed.shape[0], xs.shape[1]
     nch = 8 if dim == 3 else 4
-    ck = np.repeat(kind, nch)
+    code = _codes(kind)
+    cc = np.repeat(code, nch)
     raw = np.full((nch * nel, 27), -1, dtype=np.int64)
     fff = np.full((nch * nel, 6), -1, dtype=np.int64)
-    ent = []                                                  # (child, local node, key[4]) of every shared new node
-    for s in SHAPES:
-        sel = np.nonzero(kind == s)[0]
+    ent = {2: [], 3: [], 4: []}                               # (child, local node, key) of the shared new nodes by family: edges, triangles, quadrilaterals
+    for i, s in enumerate(SHAPES):
+        sel = np.nonzero(code == i)[0]
         if sel.size == 0:
             continue
         T = tables(s)
-        nv, ne, nl = CLASSES[s]
+        nv = CLASSES[s][0]
+        es = ed[sel]
         for j in range(nch):
             rows = nch * sel + j
-            raw[rows, :nv] = ed[sel][:, T["f2c"][j]]
+            raw[rows, :nv] = es[:, T["f2c"][j]]
             for lf in range(NFACES[s]):
                 for f in range(NFACES[s]):
                     if T["nvf"][lf] == T["nvf"][f] and all(int(T["f2c"][j][v]) in T["faces"][f].tolist() for v in T["faces"][lf][:T["nvf"][lf]]):
                         fff[rows, lf] = ff[sel, f]
         rows = (nch * sel[:, None] + np.arange(nch)[None, :]).ravel()
-        for m, (a, b) in enumerate(T["edges"]):
-            va, vb = raw[rows, a], raw[rows, b]
-            key = np.stack([np.minimum(va, vb), np.maximum(va, vb), np.full(rows.size, -1), np.full(rows.size, -1)], axis=1)
-            ent.append((rows, np.full(rows.size, nv + m), key))
-        for f in range(NFACES[s] if dim == 3 else 0):         # (in two dimensions the faces ARE the edges)
-            n = T["nvf"][f]
-            key = np.sort(raw[rows][:, T["faces"][f][:n]], axis=1)
-            if n == 3:                                        # (a, b, c, -2): apart from an edge (a, b, -1, -1) and from a quadrilateral
-                key = np.concatenate([key, np.full((rows.size, 1), -2)], axis=1)
-            ent.append((rows, np.full(rows.size, T["face_local"][f]), key))
-    c = np.concatenate([t[0] for t in ent])
-    loc = np.concatenate([t[1] for t in ent])
-    key = np.concatenate([t[2] for t in ent])
-    order = np.lexsort((loc, c))                              # child by child, local order
-    c, loc, key = c[order], loc[order], key[order]
-    ids, owner = _first_touch(key)
-    nold = xs.shape[0]
-    raw[c, loc] = nold + ids
-    nshared = owner.size
-    centre = np.array([NLOC[s] - 1 for s in ck])
+        v = raw[rows, :nv]
+        E = np.array(T["edges"])
+        a, b = v[:, E[:, 0]], v[:, E[:, 1]]
+        ent[2].append((np.repeat(rows, len(E)), np.tile(nv + np.arange(len(E)), rows.size),
+                       np.stack([np.minimum(a, b), np.maximum(a, b)], axis=2).reshape(-1, 2)))
+        for n in ((3, 4) if dim == 3 else ()):                # (in two dimensions the faces ARE the edges)
+            fs = [f for f in range(NFACES[s]) if T["nvf"][f] == n]
+            if fs:
+                key = np.sort(v[:, np.array([T["faces"][f][:n] for f in fs])], axis=2).reshape(-1, n)
+                ent[n].append((np.repeat(rows, len(fs)), np.tile([T["face_local"][f] for f in fs], rows.size), key))
+    # one key family at a time (an edge, a triangle and a quadrilateral never share a node): the first child that holds a key, in child-major order, creates its
+    # node; the ids stand until _renumber numbers the nodes by their first appearance
+    nxt = xs.shape[0]
+    oc, ol = [], []
+    for part in ent.values():
+        if not part:
+            continue
+        c, loc, key = (np.concatenate(t) for t in zip(*part))
+        if len(part) > 1:                                     # child by child (each shape's entries are in child, local order already)
+            order = np.argsort(c, kind="stable")
+            c, loc, key = c[order], loc[order], key[order]
+        ids, owner = first_touch(key)
+        raw[c, loc] = nxt + ids
+        nxt += owner.size
+        oc.append(c[owner])
+        ol.append(loc[owner])
     allc = np.arange(nch * nel)
-    raw[allc, centre] = nold + nshared + allc
-    oc, ol = np.concatenate([c[owner], allc]), np.concatenate([loc[owner], centre])         # creating (child, local node) of every new node
-    pos = np.zeros((oc.size, dim))
-    for s in SHAPES:
-        m = np.nonzero(ck[oc] == s)[0]
+    centre = _CLASSES[cc, 2] - 1
+    raw[allc, centre] = nxt + allc
+    oc, ol = np.concatenate(oc + [allc]), np.concatenate(ol + [centre])       # creating (child, local node) of every new node
+    pos = np.zeros((dim, oc.size))
+    occ = cc[oc]
+    xt = np.ascontiguousarray(xs.T)
+    for i, s in enumerate(SHAPES):
+        m = np.nonzero(occ == i)[0]
         if m.size:
-            EP = tables(s)["EP"]
-            for k in range(NLOC[s]):
-                pos[m] += EP[oc[m] % nch, ol[m], k][:, None] * xs[ed[oc[m] // nch, k]]
-    coords = np.concatenate([xs, pos])
-    new, own = _renumber(ck, raw, coords.shape[0])
+            nl = NLOC[s]
+            e, j = np.divmod(oc[m], nch)
+            jl = j * nl + ol[m]
+            EPt = tables(s)["EP"].transpose(2, 0, 1).reshape(nl, -1)        # [coarse function][child * nl + local node]
+            edt = np.ascontiguousarray(ed[:, :nl].T)
+            acc = np.zeros((dim, m.size))
+            for k in range(nl):                                             # the sum over the father's nodes in their order
+                w, node = EPt[k][jl], edt[k][e]
+                for d in range(dim):
+                    acc[d] += w * xt[d][node]
+            pos[:, m] = acc
+    coords = np.concatenate([xs, pos.T])
+    new, own = _renumber(cc, raw, coords.shape[0])
     used = new >= 0
     xf = np.empty((own[2], dim))
     xf[new[used]] = coords[used]
-    return ck, _apply(new, raw), xf, fff, own
+    return np.repeat(kind, nch), _apply(new, raw), xf, fff, own

@@ -4,14 +4,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import numpy as np
 import femus_amd
-from femus_amd import capi, tet_mesh, mixed_mesh
+from femus_amd import capi, mixed_mesh
 ctx = femus_amd.Context(0)
 g = os.path.join(os.path.dirname(HERE), "golden")
-lv = tet_mesh.read_gambit(os.path.join(g, "cube_Tet.neu"))
+lv = mixed_mesh.read_gambit(os.path.join(g, "cube_Tet.neu"))
 for _ in range(3):
-    lv = tet_mesh.refine(*lv[:3])
-for nc, ndof in ((4, lv[3][0]), (10, lv[3][1]), (15, lv[3][2])):
-    ed = np.ascontiguousarray(lv[0][:, :nc])
+    lv = mixed_mesh.refine(*lv[:4])
+for nc, ndof in ((4, lv[4][0]), (10, lv[4][1]), (15, lv[4][2])):
+    ed = np.ascontiguousarray(lv[1][:, :nc])
     t0 = time.perf_counter()
     r = np.repeat(ed, nc, axis=1).ravel().astype(np.int64); c = np.tile(ed, (1, nc)).ravel().astype(np.int64)
     key = np.unique(r * ndof + c); rows, cols = key // ndof, key % ndof

@@ -232,21 +232,23 @@ def test_mixed_kernel_in_two_dimensions_a_quadrilateral_beside_two_triangles(ctx
     K.destroy()
 
 
-def test_the_application_tells_the_mesh_files_apart(tmp_path):
-    """Poisson001._gambit_kind on the four Gambit files of the application: the hexahedral file goes to the library's reader (None), the others to the host-side
-    mesh modules; a file with an element the readers do not serve is refused by the mixed reader with the element named"""
+def test_the_application_routes_the_mesh_files_to_their_element_paths(tmp_path):
+    """Poisson001._gambit_kind on the Gambit files of tests/golden: the hexahedral and quadrilateral files go to the library's reader (None), the tetrahedral and
+    prism files to their shape's kernel, the others (three shapes; quadrilaterals and triangles; triangles alone) to the mixed path -- all but the first through
+    femus_amd/mixed_mesh.py, which refuses a file with an element it does not serve and names the element"""
     from femus_amd import app_poisson as app, mixed_mesh
     g = os.path.join(HERE, "golden")
-    kinds = {f: app.Poisson001._gambit_kind(os.path.join(g, f)) for f in ("cube_Hex.neu", "cube_Tet.neu", "cube_Wedge.neu", os.path.basename(MESH))}
-    assert kinds == {"cube_Hex.neu": None, "cube_Tet.neu": "tet10", "cube_Wedge.neu": "wedge18", os.path.basename(MESH): "mixed"}
+    kinds = {f: app.Poisson001._gambit_kind(os.path.join(g, f)) for f in ("cube_Hex.neu", "nsbenc.neu", "cube_Tet.neu", "cube_Wedge.neu", os.path.basename(MESH),
+                                                                         "square_mixed.neu", "tri2.neu", "triAMR.neu")}
+    assert kinds == {"cube_Hex.neu": None, "nsbenc.neu": None, "cube_Tet.neu": "tet", "cube_Wedge.neu": "wedge", os.path.basename(MESH): "mixed",
+                     "square_mixed.neu": "mixed", "tri2.neu": "mixed", "triAMR.neu": "mixed"}
     text = open(MESH).read().replace("       1  6 10 ", "       1  7  5 ", 1)          # a pyramid where the first tetrahedron was
     bad = tmp_path / "bad.neu"
     bad.write_text(text)
+    assert app.Poisson001._gambit_kind(str(bad)) == "mixed"
     with pytest.raises(ValueError, match="element 1 of Gambit type 7"):
         mixed_mesh.read_gambit(str(bad))
-    # several element groups: the single-shape readers refuse (they keep the file's order), the application sends such a file to the mixed reader, which orders
-    # the elements by (material, group, index)
-    from femus_amd import tet_mesh
+    # several element groups: mixed_mesh.py orders the elements by (material, group, index), so such a file keeps its shape's path
     tet = os.path.join(g, "cube_Tet.neu")
     lines = open(tet).read().split("\n")
     k = [i for i, l in enumerate(lines) if "NGRPS" in l][0] + 1
@@ -255,9 +257,7 @@ def test_the_application_tells_the_mesh_files_apart(tmp_path):
     lines[k] = " ".join(t)
     two = tmp_path / "two_groups.neu"
     two.write_text("\n".join(lines))
-    with pytest.raises(ValueError, match="2 element groups"):
-        tet_mesh.read_gambit(str(two))
-    assert app.Poisson001._gambit_kind(str(two)) == "mixed"
+    assert app.Poisson001._gambit_kind(str(two)) == "tet"
 
 
 def test_element_groups_order_the_elements():

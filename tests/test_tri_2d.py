@@ -47,6 +47,19 @@ def test_oracle_triangle_box_and_its_refinement():
             assert xf[ef[e, a], 1] == 0.0 and xf[ef[e, b], 1] == 0.0
 
 
+def test_the_product_s_triangle_box_and_refinement_are_the_oracle_s():
+    """femus_amd/mixed_mesh.py's TRI6 box and its refinement (arrays cut to the TRI7 widths, -1 beyond): the oracle's integers exactly, its coordinates to
+    rounding, on three levels"""
+    from femus_amd import mixed_mesh
+    a, b = mixed_mesh.tri_box(4, 3, (0., 0.), (1., 1.)), ot.box_mesh(4, 3, (0., 0.), (1., 1.))
+    for level in range(3):
+        assert (a[0] == "tri").all() and np.all(a[1][:, 7:] == -1) and np.all(a[3][:, 3:] == -1)
+        assert np.array_equal(a[1][:, :7], b[0]) and np.array_equal(a[3][:, :3], b[2]) and a[4] == b[3] and np.abs(a[2] - b[1]).max() < 1e-14
+        if level == 2:
+            break
+        a, b = mixed_mesh.refine(*a[:4]), ot.refine(*b[:3])
+
+
 @pytest.mark.parametrize("fe,rate", [("linear", 2.0), ("serendipity", 3.0), ("biquadratic", 3.0)])
 def test_oracle_triangles_converge_to_a_manufactured_solution(fe, rate):
     errs = []

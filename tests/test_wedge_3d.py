@@ -37,10 +37,11 @@ def test_the_mesh_file_is_the_application_s():
     assert reference_file("applications/001_Poisson/input/cube_Wedge.neu") == MESH
 
 
-def test_oracle_reader_and_refinement_and_the_product_s_mesh_code():
+def test_oracle_reader_and_refinement_and_mixed_mesh_py():
     """cube_Wedge.neu: 16 WEDGE18 prisms filling the unit cube, the triangle-face nodes shared by stacked prisms and the centres added (WEDGE21: 165 nodes);
-    refined: eight times the elements, the same volume, four times the faces per set; femus_amd/wedge_mesh.py gives the same integers on three levels"""
-    from femus_amd import wedge_mesh
+    refined: eight times the elements, the same volume, four times the faces per set; femus_amd/mixed_mesh.py gives the same integers on three levels (its arrays
+    cut to the WEDGE21 widths, -1 beyond)"""
+    from femus_amd import mixed_mesh
     ed, xs, ff, own = ow.read_gambit(MESH)
     assert ed.shape == (16, 21) and own == [27, 93, 165] and np.isclose(volume(ed, xs), 1.0)
     for m, (a, b) in enumerate(ow.EDGE):
@@ -48,12 +49,13 @@ def test_oracle_reader_and_refinement_and_the_product_s_mesh_code():
     assert np.allclose(xs[ed[:, 18]], xs[ed[:, :3]].mean(axis=1)) and np.allclose(xs[ed[:, 20]], xs[ed[:, :6]].mean(axis=1))
     counts = [(ff == f).sum() for f in range(-7, -1)]
     assert sum(counts) == 32 and min(counts) == 4          # four quadrilateral sets of 4, two triangle sets of 8
-    a, b = wedge_mesh.read_gambit(MESH), (ed, xs, ff, own)
+    a, b = mixed_mesh.read_gambit(MESH), (ed, xs, ff, own)
     for level in range(3):
-        assert np.array_equal(a[0], b[0]) and np.abs(a[1] - b[1]).max() < 1e-14 and np.array_equal(a[2], b[2]) and a[3] == b[3]
+        assert (a[0] == "wedge").all() and np.all(a[1][:, 21:] == -1) and np.all(a[3][:, 5:] == -1)
+        assert np.array_equal(a[1][:, :21], b[0]) and np.abs(a[2] - b[1]).max() < 1e-14 and np.array_equal(a[3][:, :5], b[2]) and a[4] == b[3]
         if level == 2:
             break
-        a, b = wedge_mesh.refine(*a[:3]), ow.refine(*b[:3])
+        a, b = mixed_mesh.refine(*a[:4]), ow.refine(*b[:3])
         ef, xf, fff, _ = b
         assert ef.shape[0] == 16 * 8 ** (level + 1) and [(fff == f).sum() for f in range(-7, -1)] == [c * 4 ** (level + 1) for c in counts]
         if level == 0:
