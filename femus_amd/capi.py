@@ -834,6 +834,18 @@ def assemble_neumann_edges(ctx, fe, face_nodes, face_expr, exprs, coords, res, o
                                               res.h))
 
 
+def assemble_neumann_faces_expr(ctx, geom, fe, face_nodes, face_expr, exprs, coords, res, order="seventh"):
+    """assemble_neumann_faces with a parsed flux: face_expr[nfaces] an index into exprs, each evaluated at the face Gauss points
+    (fh_assemble_neumann_faces_expr)"""
+    fn, fx, xy = _i32(face_nodes), _i32(face_expr), _f64(coords)
+    if fn.shape[0] == 0:
+        return
+    g = {"quadface": 101, "lineface": 102, "triface": 103}.get(geom)
+    hs = (ctypes.c_void_p * len(exprs))(*[e.h for e in exprs])
+    _chk(ctx.L.fh_assemble_neumann_faces_expr(ctx.h, GEOM[geom] if g is None else g, FE[fe], GAUSS_ORDER[order], fn.shape[0], _p(fn), _p(fx), len(exprs), hs,
+                                              xy.shape[0], _p(xy), res.h))
+
+
 def assemble_neumann_faces(ctx, geom, fe, face_nodes, tau, coords, res, order="seventh"):
     """face integrals of a constant flux per face on explicitly listed faces of a mesh the caller keeps (tetrahedra: TRI3 / TRI6 faces in the face element's
     order, vertices then middles): res[node] += int phi tau dS (fh_assemble_neumann_faces)"""

@@ -265,6 +265,44 @@ def assemble(kind, ed, xs, fe, source, sol=None, order="seventh"):
     return K, F
 
 
+def assemble_batched(kind, ed, xs, fe, source, sol=None, order="seventh", chunk=4096):
+    """assemble with the same tables and the same sums, vectorised over up to `chunk` elements of one shape at a time (the loop above stays the plain
+    statement).  kind: one shape name per element, or one name for all (the tri / tet / wedge oracles' element tables); source(x) gets x[d] as arrays
+    [elements, Gauss points]"""
+    import scipy.sparse as sp
+    kind = np.broadcast_to(np.asarray(kind), ed.shape[:1])
+    shapes = sorted(set(kind.tolist()))
+    ndof = max(int(ed[kind == s, :NDOF[s][fe]].max()) for s in shapes) + 1
+    rows, cols, vals = [], [], []
+    F = np.zeros(ndof)
+    u = np.zeros(ndof) if sol is None else np.asarray(sol)
+    for s in shapes:
+        nc = NDOF[s][fe]
+        w, PHI, DPHI = tables(s, fe, order)
+        ng, dim = w.size, DPHI.shape[2]
+        elems = np.nonzero(kind == s)[0]
+        for c in range(0, elems.size, chunk):
+            dof = ed[elems[c:c + chunk], :nc]
+            ne = dof.shape[0]
+            x = xs[dof]                                                        # [e, n, dim]
+            J = np.swapaxes(DPHI, 1, 2)[None] @ x[:, None]                    # [e, g]: J[a][b] = sum_n dphi_n/dxi_a x_n[b]
+            weight = np.linalg.det(J) * w                                      # [e, g]
+            grad = DPHI[None] @ np.swapaxes(np.linalg.inv(J), 2, 3)            # grad phi_n [b] = sum_a Jinv[b][a] dphi_n/dxi_a
+            f = np.broadcast_to(source(np.moveaxis(PHI[None] @ x, 2, 0)), (ne, ng))
+            gu = np.swapaxes(grad, 2, 3) @ u[dof][:, None, :, None]            # [e, g, dim, 1]
+            Ke = np.zeros((ne, nc, nc))
+            Fe = np.zeros((ne, nc))
+            for g in range(ng):                                                # the loop's order of the sums over Gauss points
+                Ke += (grad[:, g] @ np.swapaxes(grad[:, g], 1, 2)) * weight[:, g, None, None]
+                Fe += (f[:, g, None] * PHI[g] - (grad[:, g] @ gu[:, g])[:, :, 0]) * weight[:, g, None]
+            rows.append(np.repeat(dof, nc, axis=1).ravel())
+            cols.append(np.tile(dof, (1, nc)).ravel())
+            vals.append(Ke.ravel())
+            np.add.at(F, dof.ravel(), Fe.ravel())
+    K = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(ndof, ndof))
+    return K, F
+
+
 def _face_tables(nv, fe, order):
     if nv == 2:                                              # line elements: ends, then middle
         w, xg = fo.gauss_table("line", order)

@@ -243,6 +243,9 @@ def test_affine_fast_path_matches_oracle(ctx, shape):
     asm = capi.Assembler(ctx, m, "biquadratic", A)
     na, ng = asm.affine_count()
     assert na + ng == m.nel and (ng == 0) == (shape != "mixed") and na > 0
+    asm5 = capi.Assembler(ctx, m, "biquadratic", A, order="fifth")     # the affine path and the fused plan serve 64 points only: at 27 they refuse
+    assert asm5.affine_count()[0] == 0 and not asm5.fused_info()["active"]
+    asm5.destroy()
     u = fo.lcg_fill(n, 11)
     sol, res = ctx.vector_from(u), ctx.vector(n)
     ctx.set_option("assemble_affine", 1)

@@ -58,6 +58,9 @@ def test_fused_assembly_matches_oracle_and_two_pass(ctx, args, nl, kind, with_so
             asm = capi.Assembler(ctx, m, "biquadratic", A, elem_dof=ed, coords=xy)
             info = asm.fused_info()
             assert info["active"] == bool(fused) and (not fused or info["clusters"] == m.nel // 8)
+            asm9 = capi.Assembler(ctx, m, "biquadratic", A, order="ninth", elem_dof=ed, coords=xy)      # 125 points: no fused plan
+            assert not asm9.fused_info()["active"]
+            asm9.destroy()
             sol = ctx.vector_from(u) if with_sol else None
             asm.assemble(A, res, sol, kind, params)
             v1, f1 = A.values().copy(), res.to_numpy().copy()

@@ -413,3 +413,10 @@ def test_the_reader_on_the_small_gambit_files_of_the_reference_tree():
             assert int((m1[3] < -1).sum()) == int((m[3] < -1).sum()) * (4 if m[2].shape[1] == 3 else 2), p
             done += 1
     assert done >= 20
+
+
+@gpu
+def test_input3d_json_on_four_levels_against_the_batched_oracle(ctx, tmp_path):
+    """input3D.json (second order, 10 240 elements of three shapes): four_level.parity"""
+    from four_level import parity
+    parity(ctx, tmp_path, MESH, _shipped("second", 4), "biquadratic", om, "mixed")

@@ -173,3 +173,11 @@ def test_the_shipped_quadratic_inputs_on_all_of_their_four_levels(ctx, tmp_path,
     assert np.abs(out4["solution"][idx] - out3["solution"]).max() < 0.1 * np.abs(out3["solution"]).max()         # (5 % where the flux face meets the Dirichlet faces)
     p3.destroy()
     p4.destroy()
+
+
+@gpu
+@pytest.mark.parametrize("fe_order,fe", [("serendipity", "serendipity"), ("second", "biquadratic")])
+def test_the_shipped_quadratic_inputs_on_four_levels_against_the_batched_oracle(ctx, tmp_path, fe_order, fe):
+    """input3D_Tet_serendipity.json / input3D_Tet_second.json as shipped (four levels): four_level.parity"""
+    from four_level import parity
+    parity(ctx, tmp_path, MESH, _shipped(fe_order, 4), fe, oq, "tet")

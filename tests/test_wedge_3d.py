@@ -161,3 +161,11 @@ def test_the_shipped_prism_inputs_on_all_of_their_four_levels(ctx, tmp_path, fe_
     out = p.run()
     assert out["converged"] and len(out["history"]) <= 7 and out["levels"][-1][0].shape[0] == 16 * 8 ** 3, out["history"]
     p.destroy()
+
+
+@gpu
+@pytest.mark.parametrize("fe_order,fe", [("serendipity", "serendipity"), ("second", "biquadratic")])
+def test_the_shipped_quadratic_inputs_on_four_levels_against_the_batched_oracle(ctx, tmp_path, fe_order, fe):
+    """input3D_Wedge_serendipity.json / input3D_Wedge_second.json as shipped (four levels): four_level.parity"""
+    from four_level import parity
+    parity(ctx, tmp_path, MESH, _shipped(fe_order, 4), fe, ow, "wedge")
