@@ -1232,7 +1232,7 @@ class Multigrid:
         _chk(self.L.fh_mg_set_level_distributed(self.h, int(level), None if halo is None else halo.h, 1 if replicated_below else 0))
 
     def coarse_info(self):
-        """(unknowns in the dense coarse problem, interior blocks of its dissection -- 0: one dense inverse --, separator size, largest block)"""
+        """(unknowns in the dense coarse problem, interior blocks of its dissection -- 0: one dense inverse, -1: the sparse exact solve instead --, separator size, largest block)"""
         v = [ctypes.c_int() for _ in range(4)]
         _chk(self.L.fh_mg_coarse_info(self.h, *[ctypes.byref(x) for x in v]))
         return tuple(x.value for x in v)

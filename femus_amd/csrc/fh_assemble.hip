@@ -76,7 +76,7 @@ struct fh_assembler_s {
   unsigned short* d_cl_gtab = nullptr;      // [8][27 * 27] template entry that child j OWNS at (local row, local column), 0xffff = another child's (fh_assembler_galerkin from the macro rows)
   bool cl_all_rows = false;                 // every row of every cluster lies in the matrix (no ghost rows, no sink): the macro rows can be read back
   bool macro_valid = false;                 // the matrix cl_val_base and the partial-row buffer hold the macro rows of the last assembly
-  fh_mat_t cl_mat_of_macro = nullptr;       // the matrix of that assembly
+  uint64_t macro_uid = 0;                   // the matrix of that assembly (fh_mat_s::uid, not its address: it may be destroyed, and a later one may get the address)
   uint64_t macro_val_gen = 0;               // ... as long as nobody but SetPenalty has written the matrix since (fh_mat_s::val_gen)
   double* d_Pbuf = nullptr;
   int* d_cl_prow = nullptr;                 // rows of the second pass
@@ -3584,10 +3584,10 @@ static int assemble_poisson_core(fh_assembler_t as, fh_vec_t sol, int source_kin
       // fused cluster assembly: complete rows straight into the CSR arrays, the others through the partial-row buffer (the element-row buffer is not written)
       as->kbuf_valid = false;
       FH_TRY(launch_cluster(as, P, A, res->d));
-      A->at_valid = false;
+      fh_mat_values_written(A);
       as->macro_valid = !(as->ctx->asm_debug & (2 | 4 | 8));     // (timing aids leave rows unwritten)
-      as->macro_val_gen = ++A->val_gen;
-      as->cl_mat_of_macro = A;
+      as->macro_val_gen = A->val_gen;
+      as->macro_uid = A->uid;
       return 0;
     }
     as->kbuf_valid = true;
@@ -3633,12 +3633,12 @@ static int assemble_poisson_core(fh_assembler_t as, fh_vec_t sol, int source_kin
       }
       FH_CHECK_HIP(hipEventRecord(e1, s2));
       FH_CHECK_HIP(hipStreamWaitEvent(s1, e1, 0));
-      A->at_valid = false;
+      fh_mat_values_written(A);
       return 0;
     }
     FH_TRY(dispatch_assemble(as, P));
     if (!(as->ctx->asm_debug & (2 | 8))) FH_TRY(dispatch_rows(as, A, res->d, false));   // bit 3: element matrices only (timing)
-    A->at_valid = false;
+    fh_mat_values_written(A);
     return 0;
   }
   // KK->zero(); RES->zero();  (separate.hpp:106-107)
@@ -3662,7 +3662,7 @@ static int assemble_poisson_core(fh_assembler_t as, fh_vec_t sol, int source_kin
     P.nelems = as->color_ptr[c + 1] - as->color_ptr[c];
     FH_TRY(dispatch_assemble(as, P));
   }
-  A->at_valid = false;
+  fh_mat_values_written(A);
   return 0;
 }
 
@@ -4308,9 +4308,11 @@ extern "C" int fh_assembler_galerkin(fh_assembler_t fas, fh_assembler_t cas, con
   // the fused path stays the path of the next assembly), or the element-row buffer of the two-pass path
   // (the macro rows live in the user-visible fine matrix: any writer of its values since the assembly other than the Dirichlet-row replacement -- a scaling, an
   //  in-place product, staged adds -- sends the product back to the element rows, which are re-created from the arguments of the last assembly)
+  //  -- and so does the destruction of that matrix: the kernel reads it through addresses, which must still be the ones of a live matrix with the assembly's values)
+  const fh_mat_t fine_mat = fas->macro_valid ? fh_mat_alive(fas->macro_uid) : nullptr;
   const bool from_macro = nc == 27 && c->galerkin_mfma && c->galerkin_macro && fas->fused && fas->last_path == 1 && fas->macro_valid && fas->cl_all_rows &&
-                          fas->d_cl_gtab && cas->gal_children_in_order && fas->cl_ncl == cas->nel && fas->cl_mat_of_macro != nullptr &&
-                          fas->cl_mat_of_macro->d_val == fas->cl_val_base && fas->cl_mat_of_macro->val_gen == fas->macro_val_gen;
+                          fas->d_cl_gtab && cas->gal_children_in_order && fas->cl_ncl == cas->nel && fine_mat != nullptr &&
+                          fine_mat->d_val == fas->cl_val_base && fine_mat->val_gen == fas->macro_val_gen;
   if (!from_macro) {
     fas->rows_used_since = true;                              // (the next assembly of this level keeps its element rows)
     if (!fas->kbuf_valid) FH_TRY(element_rows_again(fas));     // the fused assembly kept no element rows: pass 1 of the two-pass path with the last arguments
@@ -4377,7 +4379,8 @@ extern "C" int fh_assembler_galerkin(fh_assembler_t fas, fh_assembler_t cas, con
   FH_CHECK_HIP(hipMemsetAsync(cas->d_Fbuf, 0, std::max<size_t>(cas->nadj, 1) * sizeof(double), c->stream));
   FH_TRY(dispatch_rows(cas, Ac, cas->d_gal_res, false));
   cas->kbuf_valid = true;     // the coarse element rows this product wrote (the next coarser product reads them)
-  Ac->at_valid = false;       // new values: a cached explicit transpose is stale
+  cas->macro_valid = false;   // ... and not the macro rows an earlier fused assembly of the coarse level may have left in Ac: this product has overwritten Ac
+  fh_mat_values_written(Ac);
   return 0;
   FH_GUARD_END("fh_assembler_galerkin")
 }
@@ -4955,8 +4958,7 @@ extern "C" int fh_assemble_advdiff_line(fh_ctx_t ctx, int fe, int order, int nel
       fh_set_error("fh_assemble_advdiff_line: launch failed");
       rc = 2;
     }
-    KK->val_gen++;
-    KK->at_valid = false;
+    fh_mat_values_written(KK);
   }
   hipStreamSynchronize(st);
   for (void* q : dv) hipFree(q);
@@ -5254,8 +5256,7 @@ static int poisson_rows_impl(fh_ctx_t ctx, int ns, const int* shapes, const int*
       fh_set_error("fh_assemble_poisson_rows: launch failed");
       rc = 2;
     }
-    KK->val_gen++;
-    KK->at_valid = false;
+    fh_mat_values_written(KK);
   }
   hipStreamSynchronize(st);
   for (void* q : dv) hipFree(q);

@@ -198,6 +198,16 @@ struct InvDesc {
 size_t fh_inv_work_doubles(int n);
 int fh_inv_sym_batched(fh_ctx_t c, const InvDesc* d_desc, int k, int nmax);
 
+// every writer of a matrix's values ends here (the Dirichlet-row replacement, fh_mat_zero_rows*, calls fh_mat_rows_replaced instead): one place, so that a new
+// writer cannot tell one kind of derived state and forget the other
+static inline void fh_mat_values_written(fh_mat_t A) {
+  A->val_gen++;           // macro rows of a fused assembly that live in this matrix are no longer the assembly's (fh_assembler_galerkin)
+  A->at_valid = false;    // a cached explicit transpose is stale
+}
+static inline void fh_mat_rows_replaced(fh_mat_t A) { A->at_valid = false; }
+// the live matrix with this uid, or null when it has been destroyed (an address may be reused by a later matrix, a uid never is)
+fh_mat_t fh_mat_alive(uint64_t uid);
+
 // host copy of the column indices: matrices whose pattern was built on the device (fh_mat_create_from_elements) fetch it at the first host use
 int fh_mat_fetch_host_cols(fh_mat_t A);
 int fh_mat_alloc_device_pattern(fh_ctx_t c, int m, int n, std::vector<int>&& rp, fh_mat_t* out);   // columns left to the caller's kernels

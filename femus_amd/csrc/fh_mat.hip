@@ -11,6 +11,8 @@
 // x lines) run on the same XCD and hit the same 4 MiB L2.
 #include "fh_internal.h"
 #include <atomic>
+#include <mutex>
+#include <unordered_map>
 #include <algorithm>
 #include <cmath>
 #include <thread>
@@ -18,16 +20,42 @@
 // ------------------------------------------------------------------------------------------------
 // creation / destruction
 // ------------------------------------------------------------------------------------------------
+// the live matrices by uid: whoever remembers a matrix beyond the call that named it (the macro rows of a fused assembly) keeps the uid and asks here
+// (both live in one object that is made at the first use and never destroyed: a matrix may be destroyed from a finaliser that runs after the library's
+//  static destructors)
+struct LiveMats {
+  std::mutex mutex;
+  std::unordered_map<uint64_t, fh_mat_t> map;
+};
+static LiveMats& live_mats() {
+  static LiveMats* const l = new LiveMats();
+  return *l;
+}
+// the one place a matrix object is made: a uid of its own, and an entry among the live matrices until fh_mat_destroy
+static fh_mat_t mat_new(fh_ctx_t c) {
+  static std::atomic<uint64_t> next_uid{1};
+  fh_mat_t A = new fh_mat_s();
+  A->uid = next_uid++;
+  A->ctx = c;
+  LiveMats& L = live_mats();
+  std::lock_guard<std::mutex> g(L.mutex);
+  L.map[A->uid] = A;
+  return A;
+}
+fh_mat_t fh_mat_alive(uint64_t uid) {
+  LiveMats& L = live_mats();
+  std::lock_guard<std::mutex> g(L.mutex);
+  auto it = L.map.find(uid);
+  return it == L.map.end() ? nullptr : it->second;
+}
+
 extern "C" int fh_mat_create_csr(fh_ctx_t c, int m, int n, const int* rowptr, const int* col, const double* val, fh_mat_t* out) {
   FH_GUARD_BEGIN
   FH_REQUIRE(c && out && rowptr, "fh_mat_create_csr: null argument");
   FH_REQUIRE(m >= 0 && n >= 0 && rowptr[0] == 0, "fh_mat_create_csr: bad sizes");
   const int nnz = rowptr[m];
   FH_REQUIRE(nnz == 0 || col != nullptr, "fh_mat_create_csr: null column array");
-  fh_mat_t A = new fh_mat_s();
-  static std::atomic<uint64_t> next_uid{1};
-  A->uid = next_uid++;
-  A->ctx = c;
+  fh_mat_t A = mat_new(c);
   A->m = m;
   A->n = n;
   A->nnz = nnz;
@@ -72,10 +100,7 @@ int fh_mat_fetch_host_cols(fh_mat_t A) {
 // the caller's kernels; values start at zero.  The host column copy is fetched only if host code asks for it (fh_hcol).  The caller
 // finishes with fh_mat_build_rowblocks once the columns are written.
 int fh_mat_alloc_device_pattern(fh_ctx_t c, int m, int n, std::vector<int>&& rp, fh_mat_t* out) {
-  fh_mat_t A = new fh_mat_s();
-  static std::atomic<uint64_t> next_uid{(uint64_t)1 << 40};        // (apart from the counter of fh_mat_create_csr)
-  A->uid = next_uid++;
-  A->ctx = c;
+  fh_mat_t A = mat_new(c);
   A->m = m;
   A->n = n;
   A->h_rowptr = std::move(rp);
@@ -299,6 +324,11 @@ extern "C" int fh_mat_create_from_mesh(fh_ctx_t c, fh_mesh_t mesh, int fe, fh_ma
 
 extern "C" int fh_mat_destroy(fh_mat_t A) {
   if (!A) return 0;
+  {
+    LiveMats& L = live_mats();
+    std::lock_guard<std::mutex> g(L.mutex);
+    L.map.erase(A->uid);
+  }
   hipStreamSynchronize(A->ctx->stream);
   fh_stage_free(A->stage);
   if (A->plan && A->plan_destroy) A->plan_destroy(A->plan);
@@ -386,17 +416,17 @@ int fh_mat_build_rowblocks(fh_mat_t A, int tile) {
 }
 
 extern "C" int fh_mat_zero(fh_mat_t A) {
-  if (A) A->val_gen++;
+  FH_REQUIRE(A, "fh_mat_zero: null matrix");
   FH_CHECK_HIP(hipMemsetAsync(A->d_val, 0, (size_t)A->nnz * sizeof(double), A->ctx->stream));
-  A->at_valid = false;
+  fh_mat_values_written(A);
   return 0;
 }
 
 extern "C" int fh_mat_set_values_csr(fh_mat_t A, const double* val) {
-  if (A) A->val_gen++;
+  FH_REQUIRE(A && (val || A->nnz == 0), "fh_mat_set_values_csr: null argument");
+  fh_mat_values_written(A);
   FH_CHECK_HIP(hipMemcpyAsync(A->d_val, val, (size_t)A->nnz * sizeof(double), hipMemcpyHostToDevice, A->ctx->stream));
   FH_CHECK_HIP(hipStreamSynchronize(A->ctx->stream));
-  A->at_valid = false;
   return 0;
 }
 
@@ -446,19 +476,18 @@ static int apply_entries(fh_mat_t A, const std::vector<int>& pos, const double* 
   FH_CHECK_HIP(hipStreamSynchronize(c->stream));
   hipFree(d_pos);
   hipFree(d_v);
-  A->at_valid = false;
+  fh_mat_values_written(A);
   return 0;
 }
 
 // immediate form of the staged add (fh_stage.hip): the block is on the device when the call returns
 extern "C" int fh_mat_add_block(fh_mat_t A, int nrow, const int* rows, int ncol, const int* cols, const double* vals) {
-  if (A) A->val_gen++;
   FH_TRY(fh_mat_stage_block(A, nrow, rows, ncol, cols, vals));
   return fh_mat_flush(A);
 }
 
 extern "C" int fh_mat_insert_row(fh_mat_t A, int row, int ncols, const int* cols, const double* vals) {
-  if (A) A->val_gen++;
+  FH_REQUIRE(A, "fh_mat_insert_row: null matrix");
   FH_REQUIRE(row >= 0 && row < A->m, "fh_mat_insert_row: row %d out of range", row);
   std::vector<int> pos(ncols);
   for (int j = 0; j < ncols; j++) {
@@ -514,7 +543,7 @@ extern "C" int fh_mat_zero_rows(fh_mat_t A, int n, const int* rows, double diag)
   FH_CHECK_HIP(hipGetLastError());
   FH_CHECK_HIP(hipStreamSynchronize(c->stream));
   hipFree(d_rows);
-  A->at_valid = false;
+  fh_mat_rows_replaced(A);
   return 0;
 }
 
@@ -559,7 +588,7 @@ extern "C" int fh_mat_zero_rows_index(fh_mat_t A, fh_index_t rows, double diag) 
   if (rows->n == 0) return 0;
   hipLaunchKernelGGL(k_zero_rows, dim3(fh_div_up(rows->n, 8)), dim3(256), 0, A->ctx->stream, A->d_rowptr, A->d_col, A->d_val, rows->d, rows->n, diag);
   FH_CHECK_HIP(hipGetLastError());
-  A->at_valid = false;
+  fh_mat_rows_replaced(A);
   return 0;
 }
 
@@ -588,7 +617,6 @@ __global__ __launch_bounds__(256) void k_gather_map(double* __restrict__ dst, co
 }
 
 extern "C" int fh_mat_gather_values(fh_mat_t dst, fh_mat_t src, fh_index_t map) {
-  if (dst) dst->val_gen++;
   FH_REQUIRE(dst && src && map, "fh_mat_gather_values: null argument");
   FH_REQUIRE(map->n == dst->nnz && map->max_index < src->nnz, "fh_mat_gather_values: map has %d entries (target nnz %d), largest source %d (source nnz %d)",
              map->n, dst->nnz, map->max_index, src->nnz);
@@ -596,7 +624,7 @@ extern "C" int fh_mat_gather_values(fh_mat_t dst, fh_mat_t src, fh_index_t map) 
   const int nb = std::min(fh_div_up(dst->nnz, 256), dst->ctx->num_cu * 16);
   hipLaunchKernelGGL(k_gather_map, dim3(nb), dim3(256), 0, dst->ctx->stream, dst->d_val, src->d_val, map->d, dst->nnz);
   FH_CHECK_HIP(hipGetLastError());
-  dst->at_valid = false;
+  fh_mat_values_written(dst);
   return 0;
 }
 
@@ -758,7 +786,7 @@ extern "C" int fh_vec_gather(fh_vec_t dst, fh_vec_t src, fh_index_t map) {
 }
 
 extern "C" int fh_mat_zero_cols(fh_mat_t A, int n, const int* cols) {
-  if (A) A->val_gen++;
+  FH_REQUIRE(A, "fh_mat_zero_cols: null matrix");
   if (n <= 0 || A->nnz == 0) return 0;
   fh_ctx_t c = A->ctx;
   for (int i = 0; i < n; i++) FH_REQUIRE(cols[i] >= 0 && cols[i] < A->n, "fh_mat_zero_cols: column %d out of range", cols[i]);
@@ -775,7 +803,7 @@ extern "C" int fh_mat_zero_cols(fh_mat_t A, int n, const int* cols) {
   FH_CHECK_HIP(hipStreamSynchronize(c->stream));
   hipFree(d_idx);
   hipFree(d_mask);
-  A->at_valid = false;
+  fh_mat_values_written(A);
   return 0;
 }
 
@@ -926,10 +954,7 @@ static int build_transpose(fh_mat_t A, fh_mat_t* out, int** d_perm_out) {
     hipFree(d_cnt);
     return build_transpose_host(A, out, d_perm_out);
   }
-  fh_mat_t At = new fh_mat_s();
-  static std::atomic<uint64_t> next_uid{(uint64_t)1 << 41};
-  At->uid = next_uid++;
-  At->ctx = c;
+  fh_mat_t At = mat_new(c);
   At->m = n;
   At->n = m;
   At->nnz = nnz;

@@ -3343,9 +3343,9 @@ extern "C" int fh_mg_set_level_coords(fh_mg_t mg, int level, int dim, int n, con
 
 extern "C" int fh_mg_coarse_info(fh_mg_t mg, int* n_dense, int* nd_blocks, int* nd_separator, int* nd_largest_block) {
   FH_REQUIRE(mg && mg->setup_done, "fh_mg_coarse_info: fh_mg_setup has not been called");
-  const int k = mg->nd_active ? (int)mg->nd_off.size() - 2 : 0;
+  const int k = (mg->nd_active && !mg->direct0_active) ? (int)mg->nd_off.size() - 2 : 0;
   if (n_dense) *n_dense = mg->na;
-  if (nd_blocks) *nd_blocks = k;
+  if (nd_blocks) *nd_blocks = mg->direct0_active ? -1 : k;      // -1: no dense inverse at all, the sparse exact solve serves level 0
   if (nd_separator) *nd_separator = k ? mg->na - mg->nd_off[k] : 0;
   int big = 0;
   for (int i = 0; i < k; i++) big = std::max(big, mg->nd_off[i + 1] - mg->nd_off[i]);

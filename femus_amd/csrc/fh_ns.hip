@@ -704,7 +704,7 @@ extern "C" int fh_assemble_advection_diffusion(fh_ns_assembler_t as, fh_vec_t so
     hipLaunchKernelGGL(k_sys_row_gather, dim3(as->ndof), dim3(64), (size_t)as->max_row * sizeof(double), as->ctx->stream, as->d_adj_ptr, as->d_adj_ei,
                        as->d_elem_sys, as->d_K, as->d_F, as->nd, A->d_rowptr, A->d_col, A->d_val, res->d, as->ndof);
   FH_CHECK_HIP(hipGetLastError());
-  A->at_valid = false;
+  fh_mat_values_written(A);
   return 0;
 }
 
@@ -867,7 +867,7 @@ extern "C" int fh_assemble_navier_stokes_stab(fh_ns_assembler_t as, fh_vec_t sol
     hipLaunchKernelGGL(k_sys_row_gather, dim3(as->ndof), dim3(64), (size_t)as->max_row * sizeof(double), as->ctx->stream, as->d_adj_ptr, as->d_adj_ei,
                        as->d_elem_sys, as->d_K, as->d_F, as->nd, A->d_rowptr, A->d_col, A->d_val, res->d, as->ndof);
   FH_CHECK_HIP(hipGetLastError());
-  A->at_valid = false;
+  fh_mat_values_written(A);
   return 0;
 }
 
@@ -880,7 +880,7 @@ extern "C" int fh_assemble_navier_stokes(fh_ns_assembler_t as, fh_vec_t sol, dou
     hipLaunchKernelGGL(k_sys_row_gather, dim3(as->ndof), dim3(64), (size_t)as->max_row * sizeof(double), as->ctx->stream, as->d_adj_ptr, as->d_adj_ei,
                        as->d_elem_sys, as->d_K, as->d_F, as->nd, A->d_rowptr, A->d_col, A->d_val, res->d, as->ndof);
   FH_CHECK_HIP(hipGetLastError());
-  A->at_valid = false;
+  fh_mat_values_written(A);
   return 0;
 }
 

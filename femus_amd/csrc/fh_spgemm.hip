@@ -325,13 +325,13 @@ static int spgemm_numeric_map(fh_mat_t A, fh_mat_t B, fh_mat_t C, const SlotMap&
     hipLaunchKernelGGL(k_spgemm_numeric_slots, dim3(fh_div_up(C->m, 4)), dim3(256), (size_t)4 * M.max_crow * sizeof(double), C->ctx->stream,
                        A->d_rowptr, A->d_col, A->d_val, B->d_rowptr, B->d_val, C->d_rowptr, C->d_val, M.rowbase, M.slot, C->m, M.max_crow);
     FH_CHECK_HIP(hipGetLastError());
-    C->at_valid = false;
+    fh_mat_values_written(C);
     return 0;
   }
   hipLaunchKernelGGL(k_spgemm_numeric_map, dim3(fh_div_up(C->m, 4)), dim3(256), (size_t)4 * M.max_arow * sizeof(double), C->ctx->stream, A->d_rowptr,
                      A->d_val, B->d_val, C->d_rowptr, C->d_val, M.rowbase, M.segptr, M.pa, M.pb, C->m, M.max_arow);
   FH_CHECK_HIP(hipGetLastError());
-  C->at_valid = false;
+  fh_mat_values_written(C);
   return 0;
 }
 
@@ -370,7 +370,7 @@ static int spgemm_numeric(fh_mat_t A, fh_mat_t B, fh_mat_t C) {
   hipLaunchKernelGGL(k_spgemm_numeric, dim3(fh_div_up(C->m, 4)), dim3(256), 0, C->ctx->stream, A->d_rowptr, A->d_col, A->d_val, B->d_rowptr,
                      B->d_col, B->d_val, C->d_rowptr, C->d_col, C->d_val, C->m);
   FH_CHECK_HIP(hipGetLastError());
-  C->at_valid = false;
+  fh_mat_values_written(C);
   return 0;
 }
 
@@ -615,7 +615,6 @@ static int triple_product(fh_mat_t R, fh_mat_t A, fh_mat_t P, fh_mat_t* Cio, con
   }
   if (plan->map_ap.pa || plan->map_ap.slot) FH_TRY(spgemm_numeric_map(A, P, plan->AP, plan->map_ap)); else FH_TRY(spgemm_numeric(A, P, plan->AP));
   if (plan->map_c.pa || plan->map_c.slot) FH_TRY(spgemm_numeric_map(R, plan->AP, C, plan->map_c)); else FH_TRY(spgemm_numeric(R, plan->AP, C));
-  C->val_gen++;
   return 0;
 }
 

@@ -236,7 +236,7 @@ static int mat_issue(fh_mat_t A) {
   else
     hipLaunchKernelGGL(k_stage_flush_rows<false>, dim3(nt), dim3(64), 0, st, A->d_rowptr, A->d_col, A->d_val, r.d_i, r.d_d, (int)trow_off,
                        (int)tptr_off, (int)tlist_off, s->d_err);
-  A->at_valid = false;
+  fh_mat_values_written(A);
   return ring_issued(s, r);
 }
 
@@ -301,7 +301,6 @@ static int stage_finish(fh_stage_s* s, const char* who) {
 }
 
 extern "C" int fh_mat_flush(fh_mat_t A) {
-  if (A) A->val_gen++;
   FH_REQUIRE(A, "fh_mat_flush: null matrix");
   if (!A->stage || !A->stage->pending) return 0;
   FH_TRY(mat_issue(A));

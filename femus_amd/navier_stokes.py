@@ -143,6 +143,7 @@ class NavierStokesMG:
             self.P.append(P)
         self.A = {}          # (level-max, level) -> operator of the cycle
         self.mg = {}         # level-max -> multigrid
+        self.mg_coarse = {}  # level-max -> the coarsest level that multigrid was built for
         return self
 
     # ---- one Newton iteration at level-max ig ----------------------------------------------------------------------------
@@ -162,8 +163,11 @@ class NavierStokesMG:
             self.A[(ig, l)].mat_zero_rows(self.bdc[l], 1.0)
         if self.bdc[ig].size:                                          # ZerosBoundaryResiduals
             self.RES[ig].set(self.bdc[ig], np.zeros(self.bdc[ig].size))
+        if ig in self.mg and self.mg_coarse[ig] != c:                  # coarse_level was changed since: another level count, patches at other indices
+            self.mg.pop(ig).destroy()
         if ig not in self.mg:
             self.mg[ig] = capi.Multigrid(ctx, ig - c + 1)
+            self.mg_coarse[ig] = c
             for l in range(c + 1, ig + 1):
                 self.mg[ig].set_level_patches(l - c, *self.patches[l])
         mg = self.mg[ig]
