@@ -144,6 +144,11 @@ def _declare(L):
     sig("fh_assemble_advdiff_line", c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p)
     sig("fh_assemble_poisson_rows", c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p)
     sig("fh_assemble_poisson_mixed", c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p)
+    sig("fh_generic_assembler_create", c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, P(c_void_p))
+    sig("fh_generic_assembler_set_coords", c_void_p, c_int, c_void_p)
+    sig("fh_generic_assembler_assemble", c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p)
+    sig("fh_generic_assembler_info", c_void_p, P(c_int), P(ctypes.c_int64), P(ctypes.c_int64), P(ctypes.c_int64))
+    sig("fh_generic_assembler_destroy", c_void_p)
     sig("fh_assemble_pressure_faces", c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_double, c_void_p)
     sig("fh_fe_face_normals", c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p)
     sig("fh_mesh_read_gambit", c_char_p, c_double, P(c_void_p))

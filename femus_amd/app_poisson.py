@@ -294,11 +294,11 @@ class Poisson001:
         P = [None] + [self._prolongator_from_children(groups[l - 1], levels[l - 1][1], levels[l][1], ndofs[l - 1], ndofs[l]) for l in range(1, self.nlevels)]
         SOL.upload(sol0)
 
+        # the plan of the element loop, made once: every linear iteration assembles on the same mesh and pattern
+        gen = capi.GenericAssembler(ctx, kind if self.mixed else self.geom, self.fe, ed, xs, K)
+
         def assemble():
-            if not self.mixed:
-                capi.assemble_poisson_rows(ctx, self.geom, self.fe, ed, xs, K, RES, sol=SOL, source=self.source, scale=1.0)
-            else:
-                capi.assemble_poisson_mixed(ctx, self.fe, kind, ed, xs, K, RES, sol=SOL, source=self.source, scale=1.0)
+            gen.assemble(K, RES, sol=SOL, source=self.source, scale=1.0)
             if flux_faces:
                 capi.assemble_neumann_edges(ctx, self.fe, np.array(flux_faces), np.array(flux_idx), flux_exprs, xs, RES)
             if tau_faces:                                             # by kind of face (a prism has quadrilaterals and triangles): the face element named
@@ -307,7 +307,10 @@ class Poisson001:
                     fgeom = "lineface" if dim == 2 else "triface" if nn in (3, 6, 7) else "quadface"
                     capi.assemble_neumann_faces(ctx, fgeom, self.fe, np.array([tau_faces[k] for k in sel]), np.array([tau_vals[k] for k in sel]), xs, RES)
 
-        history = self._mgsolve(K, P, bdc, SOL, RES, assemble, log, smoother, omega)
+        try:
+            history = self._mgsolve(K, P, bdc, SOL, RES, assemble, log, smoother, omega)
+        finally:
+            gen.destroy()
         return {"solution": SOL.to_numpy(), "coords": xs[:ndof], "history": history, "converged": history[-1][1] < self.abs_tol, "dofs": ndof,
                 "levels": [lv[1:4] for lv in levels]}
 

@@ -780,6 +780,51 @@ def assemble_poisson_mixed(ctx, fe, elem_geom, elem_dof, coords, K, res, sol=Non
                                          sol.h if sol is not None else None, source.h if source is not None else None, float(scale), K.h, res.h))
 
 
+class GenericAssembler:
+    """assemble_poisson_rows / assemble_poisson_mixed as an object for repeated assemblies on one mesh and one pattern (fh_generic_assembler_*): the adjacency,
+    the element table, coordinates, FE tables, the CSR position of every element entry and all work buffers are made once and stay on the device; assemble()
+    only enqueues kernels and gives the bits of the one-shot calls.  geom: one name of GEOM for all elements, or one name per element (mixed shapes, elem_dof
+    padded; the padding is not read).  K is the matrix every assemble() writes: a pattern that misses an element pair is refused here."""
+
+    def __init__(self, ctx, geom, fe, elem_dof, coords, K, order="seventh"):
+        self.ctx, self.L = ctx, ctx.L
+        x = _f64(coords)
+        if isinstance(geom, str):
+            self.shapes = [geom]
+            eg, g, ed = None, GEOM[geom], _i32(elem_dof)
+        else:
+            self.shapes = list(dict.fromkeys(str(s) for s in geom))           # in the order of their first elements, as info() reports them
+            eg, g = _i32(np.array([GEOM[s] for s in geom])), -1
+            ed = _i32(np.where(np.asarray(elem_dof) < 0, 0, elem_dof))
+        self.h = ctypes.c_void_p()
+        _chk(self.L.fh_generic_assembler_create(ctx.h, FE[fe], GAUSS_ORDER[order], ed.shape[0], ed.shape[1], None if eg is None else _p(eg), g, _p(ed),
+                                                x.shape[0], _p(x), K.h, ctypes.byref(self.h)))
+
+    def set_coords(self, coords):
+        """other coordinates for the same nodes (the rest of the plan does not depend on them)"""
+        x = _f64(coords)
+        _chk(self.L.fh_generic_assembler_set_coords(self.h, x.shape[0], _p(x)))
+
+    def assemble(self, K, res, sol=None, source=None, scale=1.0):
+        """K and res are overwritten as by the one-shot calls; K must be the matrix this object was created on"""
+        _chk(self.L.fh_generic_assembler_assemble(self.h, sol.h if sol is not None else None, source.h if source is not None else None, float(scale),
+                                                  K.h if K is not None else None, res.h))
+
+    def info(self):
+        """elements per 256-thread workgroup of the element pass by shape, bytes held on the device, bytes one assembly cannot avoid moving, device
+        allocations made so far"""
+        epw = (ctypes.c_int * 3)()
+        db, ab, na = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _chk(self.L.fh_generic_assembler_info(self.h, epw, ctypes.byref(db), ctypes.byref(ab), ctypes.byref(na)))
+        return {"elems_per_workgroup": {s: epw[k] for k, s in enumerate(self.shapes[:3])}, "device_bytes": db.value, "algorithmic_bytes": ab.value,
+                "device_allocations": na.value}
+
+    def destroy(self):
+        if self.h:
+            self.L.fh_generic_assembler_destroy(self.h)
+            self.h = None
+
+
 def assemble_advdiff_line(ctx, fe, elem_dof, coords, K, res, nu, velocity, sol=None, source=None, order="seventh"):
     """the 001_Poisson callback on a one-dimensional EDGE3 mesh (main.cpp:355-480 with dim == 1: advection-diffusion with its streamline-upwind terms):
     K <- Jacobian, res <- residual.  elem_dof[nel, 3] node ids (ends, then middle; vertices numbered first), coords[nnode]"""

@@ -4973,8 +4973,9 @@ extern "C" int fh_assemble_advdiff_line(fh_ctx_t ctx, int fe, int order, int nel
 // matrix over the Gauss points (elem_type::Jacobian: Jac[a][b] = sum_n dphi_n/dxi_a x_n[b], grad phi_n = Jac^-1 dphi_n, w = det w_g) into a buffer, with the place of every entry in the matrix beside it; one thread per
 // ROW then adds the rows of its node's elements in ascending element order (first version: the row thread formed them itself -- 80 ms per call on 54 k TET15 elements, host preparation included):
 //   K_ij += grad phi_i . grad phi_j w,   RES_i += (scale f phi_i - grad phi_i . grad u) w        (main.cpp:430-470 with V = 0)
-// The grouping of the reference's add_matrix_blocked / add_vector_blocked, no atomics; meant for the sizes such meshes have here, not for the bench (the
-// hexahedral paths above are the fast ones).
+// The grouping of the reference's add_matrix_blocked / add_vector_blocked, no atomics.  These one-shot calls prepare everything on every call (adjacency on the
+// host, uploads, allocations, a search per entry): they are the yardstick of the resident object in fh_generic.hip (fh_generic_assembler_*), which keeps the plan
+// on the device and gives the same bits, and which repeated assemblies -- the application's linear iterations -- go through.
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int GEN_NC = 27;
 struct GenTab {              // the tables of one element shape: a mesh of mixed shapes (hexahedra, tetrahedra, prisms; quadrilaterals, triangles) names one per element

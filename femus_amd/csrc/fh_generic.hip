@@ -1,0 +1,591 @@
+// Resident plan for the generic (dim, nc, ng) Poisson assembly (fh_generic_assembler_*): what fh_assemble_poisson_rows / fh_assemble_poisson_mixed
+// (fh_assemble.hip: poisson_rows_impl) rebuild on every call -- the dof -> element adjacency, the uploaded element table, coordinates and FE tables, a dozen
+// allocations, a linear search of every (i, j) in its CSR row -- is made ONCE here and kept on the device; an assembly then only enqueues kernels.
+//
+// Plan, per shape k of the mesh (at most three of one dimension, in the order of their first element):
+//   d_ed[k]     [nslot_k][nc_k]  the dofs of the shape's elements, slot = rank of the element among the elements of its shape (ascending element order)
+//   Kb / Pos    element row (slot, i) of shape k starts at kb_base[k] + (slot nc_k + i) nc_k: its nc_k values, and beside them the CSR position of every
+//               one, found at create by a binary search of the (sorted) row on the device; a pair the pattern does not hold fails create
+//   Fb / adj    the element row's residual entry at row_base[k] + slot nc_k + i = the row's id; adj lists the ids of a dof in ascending ELEMENT order
+//
+// Element pass, one launch per shape (uniform waves on mixed meshes): workgroups of 256 threads, L = 64 / 32 / 16 lanes per element (1 / 2 / 4 elements per wave)
+// from the shape's nc (nc + 1) / 2 pairs; dynamic LDS sized by the shape's nc and Gauss chunk, w / phi / dphi staged once per workgroup where they fit.
+// Every value is formed by the expressions of k_poisson_pairs_generic in their order (Gauss points ascending, nodes ascending inside a point, K_ji the bits of
+// K_ij); the library is built with -ffp-contract=on, so the same source expression contracts the same way, and the results are bitwise the one-shot call's.
+// The length of the Gauss chunk only moves barriers, not one operation: the accumulators run through all points in ascending order whatever it is.
+//
+// Row pass: lpr lanes per row (a group never leaves its wave), the row's sums in LDS: element rows in ascending element order, the lanes of the group split one
+// element row's entries (distinct positions), LDS operations of one wave complete in order -- so every entry sees its additions in ascending element order,
+// starting from 0.0 as the one-shot row thread does.  No search, no atomics, no read-modify-write of global memory.
+#include "fh_internal.h"
+#include "fh_fe.h"
+#include "fh_expr_device.h"
+#include <algorithm>
+#include <climits>
+
+namespace {
+constexpr int GP_THREADS = 256;
+constexpr size_t GP_LDS_BUDGET = 64 * 1024;   // per workgroup: two workgroups and more per CU (160 KB of LDS), and no opt-in to large dynamic LDS needed
+constexpr size_t GP_PROG_BYTES = 4096;        // first size of the source program's buffer
+
+// doubles of LDS one element needs: X[nc][3], U[nc], JI[gc][9], WG[gc], FS[gc], GU[gc][3], G[gc][nc][3]
+inline size_t gp_elem_doubles(int nc, int gc) { return (size_t)nc * 4 + (size_t)gc * 14 + (size_t)gc * nc * 3; }
+inline int gp_lanes_per_element(int nc, int pack) {
+  const int npair = nc * (nc + 1) / 2;
+  if (!pack) return 64;
+  return npair <= 32 ? 16 : npair <= 64 ? 32 : 64;     // two pairs per lane at most where elements share a wave
+}
+}  // namespace
+
+// Element pass.  L lanes per element, 256 / L elements per workgroup; TL: the shape's tables in LDS.  Phases (A)-(D) of k_poisson_pairs_generic, lane loops
+// strided by L where the one-shot kernel has `lane < gc` of 64.
+template <int L, bool TL>
+__global__ __launch_bounds__(GP_THREADS) void k_gen_pairs(int nslot, int nc, int ng, int gcm, int dim, const double* __restrict__ gw, const double* __restrict__ gphi,
+                                                          const double* __restrict__ gdphi, const int* __restrict__ ed, const double* __restrict__ coords,
+                                                          const double* __restrict__ sol, double scale, const int* __restrict__ prog, int nprog,
+                                                          const double* __restrict__ pconst, double* __restrict__ Kb, double* __restrict__ Fb) {
+  extern __shared__ __attribute__((aligned(16))) double gen_smem[];
+  constexpr int EPG = GP_THREADS / L;
+  constexpr int NPL = L == 64 ? 6 : 2;           // 27 * 28 / 2 = 378 pairs on 64 lanes; at most 2 L pairs where L < 64
+  const int ntab = TL ? ng + ng * nc + ng * nc * dim : 0;
+  const int per = nc * 4 + gcm * 14 + gcm * nc * 3;
+  const int sub = threadIdx.x / L, lane = threadIdx.x % L;
+  const int slot = blockIdx.x * EPG + sub;
+  const bool active = slot < nslot;              // tail sub-groups keep the barriers and touch nothing
+  const double *w, *phi, *dphi;
+  if (TL) {
+    double* tw = gen_smem;
+    double* tphi = tw + ng;
+    double* tdphi = tphi + ng * nc;
+    for (int t = threadIdx.x; t < ng; t += GP_THREADS) tw[t] = gw[t];
+    for (int t = threadIdx.x; t < ng * nc; t += GP_THREADS) tphi[t] = gphi[t];
+    for (int t = threadIdx.x; t < ng * nc * dim; t += GP_THREADS) tdphi[t] = gdphi[t];
+    w = tw, phi = tphi, dphi = tdphi;
+  } else {
+    w = gw, phi = gphi, dphi = gdphi;
+  }
+  double* X = gen_smem + ntab + (size_t)sub * per;   // [nc][3]
+  double* U = X + nc * 3;                            // [nc]
+  double* JI = U + nc;                               // [gcm][9]
+  double* WG = JI + gcm * 9;                         // [gcm] det w
+  double* FS = WG + gcm;                             // [gcm] scale f(x_g)
+  double* GU = FS + gcm;                             // [gcm][3]
+  double* G = GU + gcm * 3;                          // [gcm][nc][3]
+  if (active && lane < nc) {
+    const int dof = ed[(size_t)slot * nc + lane];
+    for (int d = 0; d < 3; d++) X[lane * 3 + d] = d < dim ? coords[(size_t)dof * dim + d] : 0.0;
+    U[lane] = sol ? sol[dof] : 0.0;
+  }
+  const int npair = nc * (nc + 1) / 2;
+  int pi[NPL], pj[NPL];
+  double acc[NPL];
+#pragma unroll
+  for (int k = 0; k < NPL; k++) {
+    int p = lane + L * k, i = 0;
+    if (active && p < npair) {
+      while (p >= nc - i) {
+        p -= nc - i;
+        i++;
+      }
+      pi[k] = i;
+      pj[k] = i + p;
+    } else {
+      pi[k] = pj[k] = -1;
+    }
+    acc[k] = 0.0;
+  }
+  double F = 0.0;
+  __syncthreads();
+  for (int g0 = 0; g0 < ng; g0 += gcm) {
+    const int gc = min(gcm, ng - g0);
+    if (active)
+      for (int l = lane; l < gc; l += L) {             // (A)
+        const int g = g0 + l;
+        const double* dp = dphi + (size_t)g * nc * dim;
+        double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, Ji[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, det;
+        for (int n = 0; n < nc; n++)
+          for (int p = 0; p < dim; p++)
+            for (int q = 0; q < dim; q++) J[p][q] += dp[n * dim + p] * X[n * 3 + q];
+        if (dim == 1) {
+          det = J[0][0];
+          Ji[0][0] = 1 / det;
+        } else if (dim == 2) {
+          det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+          Ji[0][0] = J[1][1] / det;
+          Ji[0][1] = -J[0][1] / det;
+          Ji[1][0] = -J[1][0] / det;
+          Ji[1][1] = J[0][0] / det;
+        } else {
+          det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) + J[0][1] * (J[1][2] * J[2][0] - J[1][0] * J[2][2]) + J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+          Ji[0][0] = (-J[1][2] * J[2][1] + J[1][1] * J[2][2]) / det;
+          Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
+          Ji[0][2] = (-J[0][2] * J[1][1] + J[0][1] * J[1][2]) / det;
+          Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) / det;
+          Ji[1][1] = (-J[0][2] * J[2][0] + J[0][0] * J[2][2]) / det;
+          Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
+          Ji[2][0] = (-J[1][1] * J[2][0] + J[1][0] * J[2][1]) / det;
+          Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
+          Ji[2][2] = (-J[0][1] * J[1][0] + J[0][0] * J[1][1]) / det;
+        }
+        for (int q = 0; q < 3; q++)
+          for (int p = 0; p < 3; p++) JI[l * 9 + q * 3 + p] = Ji[q][p];
+        WG[l] = det * w[g];
+        double xq[4] = {0, 0, 0, 0};
+        for (int n = 0; n < nc; n++) {
+          const double ph = phi[(size_t)g * nc + n];
+          for (int q = 0; q < dim; q++) xq[q] += X[n * 3 + q] * ph;
+        }
+        FS[l] = prog ? scale * fh_expr_device_eval(prog, nprog, pconst, xq) : 0.0;
+      }
+    __syncthreads();
+    if (active)
+      for (int t = lane; t < gc * nc; t += L) {        // (B)
+        const int l = t / nc, n = t - l * nc;
+        const double* dp = dphi + ((size_t)(g0 + l) * nc + n) * dim;
+        for (int q = 0; q < dim; q++) {
+          double sacc = 0.0;
+          for (int p = 0; p < dim; p++) sacc += JI[l * 9 + q * 3 + p] * dp[p];
+          G[(l * nc + n) * 3 + q] = sacc;
+        }
+      }
+    __syncthreads();
+    if (active)
+      for (int l = lane; l < gc; l += L) {             // (C)
+        double gu[3] = {0, 0, 0};
+        for (int n = 0; n < nc; n++)
+          for (int q = 0; q < dim; q++) gu[q] += G[(l * nc + n) * 3 + q] * U[n];
+        for (int q = 0; q < 3; q++) GU[l * 3 + q] = gu[q];
+      }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NPL; k++)                      // (D)
+      if (pi[k] >= 0) {
+        double a = acc[k];
+        for (int l = 0; l < gc; l++) {
+          const double *gi = G + (l * nc + pi[k]) * 3, *gj = G + (l * nc + pj[k]) * 3;
+          double sacc = 0.0;
+          for (int q = 0; q < dim; q++) sacc += gi[q] * gj[q];
+          a += sacc * WG[l];
+        }
+        acc[k] = a;
+      }
+    if (active && lane < nc)
+      for (int l = 0; l < gc; l++) {
+        const double* gi = G + (l * nc + lane) * 3;
+        double lap = 0.0;
+        for (int q = 0; q < dim; q++) lap += gi[q] * GU[l * 3 + q];
+        F += (FS[l] * phi[(size_t)(g0 + l) * nc + lane] - lap) * WG[l];
+      }
+    __syncthreads();
+  }
+  if (!active) return;
+  double* out = Kb + (size_t)slot * nc * nc;
+#pragma unroll
+  for (int k = 0; k < NPL; k++)
+    if (pi[k] >= 0) {
+      out[(size_t)pi[k] * nc + pj[k]] = acc[k];
+      if (pi[k] != pj[k]) out[(size_t)pj[k] * nc + pi[k]] = acc[k];
+    }
+  if (lane < nc) Fb[(size_t)slot * nc + lane] = F;
+}
+
+// create: the CSR position of every entry of every element row of one shape, by binary search in the sorted row; the smallest entry the pattern misses -> *miss
+__global__ __launch_bounds__(256) void k_gen_positions(long long nent, int nc, const int* __restrict__ ed, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                       int* __restrict__ Pos, unsigned long long* __restrict__ miss, unsigned long long tag) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= nent) return;
+  const long long row = idx / nc;                // slot * nc + i
+  const int j = (int)(idx - row * nc);
+  const long long slot = row / nc;
+  const int r = ed[row], c = ed[slot * nc + j];
+  int lo = rowptr[r], hi = rowptr[r + 1] - 1, at = -1;
+  while (lo <= hi) {
+    const int mid = lo + (hi - lo) / 2, v = col[mid];
+    if (v == c) {
+      at = mid;
+      break;
+    }
+    if (v < c) lo = mid + 1;
+    else hi = mid - 1;
+  }
+  Pos[idx] = at;
+  if (at < 0) atomicMin(miss, tag | (unsigned long long)idx);
+}
+
+struct GenRowShapes {
+  int row_base[3];        // first element-row id of the shape (INT_MAX: no such shape)
+  int nc[3];
+  long long kb_base[3];   // where its element rows start in Kb / Pos
+};
+
+// Row pass: lpr lanes (a power of two <= 64) per row, the row's sums in LDS (maxrow doubles per group).
+__global__ __launch_bounds__(GP_THREADS) void k_gen_rows(int ndof, int lpr, int maxrow, GenRowShapes sh, const int* __restrict__ adj_ptr, const int* __restrict__ adj,
+                                                         const double* __restrict__ Kb, const int* __restrict__ Pos, const double* __restrict__ Fb,
+                                                         const int* __restrict__ rowptr, double* __restrict__ val, double* __restrict__ res) {
+  extern __shared__ __attribute__((aligned(16))) double gen_racc[];
+  const int grp = threadIdx.x / lpr, t = threadIdx.x % lpr;
+  const int r = blockIdx.x * (GP_THREADS / lpr) + grp;
+  if (r >= ndof) return;                         // no workgroup barrier below
+  double* acc = gen_racc + (size_t)grp * maxrow;
+  const int rs = rowptr[r], n = rowptr[r + 1] - rs;
+  for (int k = t; k < n; k += lpr) acc[k] = 0.0;
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  double racc = 0.0;
+  for (int a = adj_ptr[r], ae = adj_ptr[r + 1]; a < ae; a++) {
+    const int erow = adj[a];
+    const int k = erow >= sh.row_base[2] ? 2 : erow >= sh.row_base[1] ? 1 : 0;
+    const int nc = sh.nc[k];
+    const long long off = sh.kb_base[k] + (long long)(erow - sh.row_base[k]) * nc;
+    if (t == 0) racc += Fb[erow];
+    for (int j = t; j < nc; j += lpr) acc[Pos[off + j] - rs] += Kb[off + j];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  for (int k = t; k < n; k += lpr) val[rs + k] = acc[k];
+  if (t == 0) res[r] = racc;
+}
+
+struct fh_generic_assembler_s {
+  fh_ctx_t ctx = nullptr;
+  uint64_t mat_uid = 0;          // the matrix of create: its uid and non-zero count, never its address
+  int mat_nnz = 0;
+  int ndof = 0, nnode = 0, dim = 0, ns = 0, nel = 0;
+  int nc[3] = {0, 0, 0}, ng[3] = {0, 0, 0}, lanes[3] = {0, 0, 0}, gcm[3] = {0, 0, 0}, nslot[3] = {0, 0, 0};
+  bool tl[3] = {false, false, false};
+  size_t lds[3] = {0, 0, 0};
+  GenRowShapes rows;
+  int* d_ed[3] = {nullptr, nullptr, nullptr};
+  double *d_w[3] = {nullptr, nullptr, nullptr}, *d_phi[3] = {nullptr, nullptr, nullptr}, *d_dphi[3] = {nullptr, nullptr, nullptr};
+  double* d_coords = nullptr;
+  int *d_adj_ptr = nullptr, *d_adj = nullptr, *d_Pos = nullptr;
+  double *d_Kb = nullptr, *d_Fb = nullptr;
+  unsigned long long* d_miss = nullptr;
+  int lpr = 1, maxrow = 1;
+  size_t row_lds = 0;
+  // the source program: consts (doubles) then code (ints) in one buffer, staged through pinned memory; uploaded only when it differs from the last one
+  char* d_prog = nullptr;
+  char* h_prog = nullptr;
+  size_t prog_cap = 0;
+  hipEvent_t prog_ev = nullptr;
+  bool prog_copied = false;
+  std::vector<int> code;
+  std::vector<double> consts;
+  bool have_prog = false;
+  int64_t device_bytes = 0, algorithmic_bytes = 0, device_allocations = 0;
+  std::vector<void*> dv;         // every device allocation but d_prog
+};
+
+static void* gp_alloc(fh_generic_assembler_t as, size_t bytes) {
+  void* d = nullptr;
+  bytes = std::max<size_t>(bytes, 8);
+  if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
+  as->dv.push_back(d);
+  as->device_bytes += (int64_t)bytes;
+  as->device_allocations++;
+  return d;
+}
+
+static void gp_free(fh_generic_assembler_t as) {
+  if (!as) return;
+  if (as->ctx) hipStreamSynchronize(as->ctx->stream);     // no copy or kernel of this object in flight
+  for (void* q : as->dv) hipFree(q);
+  if (as->d_prog) hipFree(as->d_prog);
+  if (as->h_prog) hipHostFree(as->h_prog);
+  if (as->prog_ev) hipEventDestroy(as->prog_ev);
+  delete as;
+}
+
+template <int L, bool TL>
+static void gp_launch_pairs_t(fh_generic_assembler_t as, int k, const double* sol, double scale, const int* prog, int nprog, const double* pconst) {
+  hipLaunchKernelGGL((k_gen_pairs<L, TL>), dim3(fh_div_up(as->nslot[k], GP_THREADS / L)), dim3(GP_THREADS), as->lds[k], as->ctx->stream, as->nslot[k], as->nc[k],
+                     as->ng[k], as->gcm[k], as->dim, as->d_w[k], as->d_phi[k], as->d_dphi[k], as->d_ed[k], as->d_coords, sol, scale, prog, nprog, pconst,
+                     as->d_Kb + as->rows.kb_base[k], as->d_Fb + as->rows.row_base[k]);
+}
+static void gp_launch_pairs(fh_generic_assembler_t as, int k, const double* sol, double scale, const int* prog, int nprog, const double* pconst) {
+  const bool tl = as->tl[k];
+  switch (as->lanes[k]) {
+    case 16: tl ? gp_launch_pairs_t<16, true>(as, k, sol, scale, prog, nprog, pconst) : gp_launch_pairs_t<16, false>(as, k, sol, scale, prog, nprog, pconst); break;
+    case 32: tl ? gp_launch_pairs_t<32, true>(as, k, sol, scale, prog, nprog, pconst) : gp_launch_pairs_t<32, false>(as, k, sol, scale, prog, nprog, pconst); break;
+    default: tl ? gp_launch_pairs_t<64, true>(as, k, sol, scale, prog, nprog, pconst) : gp_launch_pairs_t<64, false>(as, k, sol, scale, prog, nprog, pconst); break;
+  }
+}
+
+extern "C" int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int order, int nel, int nloc, const int* elem_geom, int geom, const int* elem_dof, int nnode,
+                                           const double* coords, fh_mat_t KK, fh_generic_assembler_t* out) {
+  FH_GUARD_BEGIN
+  FH_REQUIRE(ctx && elem_dof && coords && KK && out && nel >= 1 && nnode >= 1 && nloc >= 1, "fh_generic_assembler_create: null or empty argument");
+  FH_REQUIRE(fe == fhfe::FE_LINEAR || fe == fhfe::FE_SERENDIPITY || fe == fhfe::FE_BIQUADRATIC, "fh_generic_assembler_create: fe must be 0, 1 or 2");
+  *out = nullptr;
+  // ---- every check first: nothing is allocated on the device before the last of them ----
+  int shapes[3] = {0, 0, 0}, ns = 0;
+  std::vector<unsigned char> eshape(nel, 0);
+  if (elem_geom) {
+    for (int e = 0; e < nel; e++) {
+      int k = 0;
+      while (k < ns && shapes[k] != elem_geom[e]) k++;
+      if (k == ns) {
+        FH_REQUIRE(ns < 3, "fh_generic_assembler_create: more than three shapes in one mesh (element %d)", e);
+        FH_REQUIRE(elem_geom[e] >= 0 && elem_geom[e] <= 5, "fh_generic_assembler_create: element %d: shape %d", e, elem_geom[e]);
+        shapes[ns++] = elem_geom[e];
+      }
+      eshape[e] = (unsigned char)k;
+    }
+  } else {
+    FH_REQUIRE(geom >= 0 && geom <= 5, "fh_generic_assembler_create: geom must be 0 (hex), 1 (quad), 2 (line), 3 (triangle), 4 (tetrahedron) or 5 (prism)");
+    shapes[ns++] = geom;
+  }
+  const int dim = fhfe::dim_of(shapes[0]), ndof = KK->m;
+  int ncs[3] = {0, 0, 0}, nslot[3] = {0, 0, 0};
+  std::vector<double> w[3], phi[3], dphi[3];
+  for (int k = 0; k < ns; k++) {
+    FH_REQUIRE(fhfe::dim_of(shapes[k]) == dim, "fh_generic_assembler_create: the shapes of one mesh have one dimension (shapes %d and %d)", shapes[0], shapes[k]);
+    ncs[k] = fhfe::ndofs_of(shapes[k], fe);
+    FH_REQUIRE(ncs[k] >= 1 && ncs[k] <= 27 && nloc >= ncs[k], "fh_generic_assembler_create: %d nodes per element given, the family has %d", nloc, ncs[k]);
+    FH_REQUIRE(fhfe::shape_tables(shapes[k], fe, order, w[k], phi[k], dphi[k]) == 0, "fh_generic_assembler_create: unsupported Gauss rule");
+  }
+  FH_REQUIRE(KK->n == ndof && (int)KK->h_rowptr.size() == ndof + 1, "fh_generic_assembler_create: the matrix is not square with a host row table");
+  for (int e = 0; e < nel; e++) nslot[eshape[e]]++;
+  int64_t nrows = 0, nent = 0;
+  for (int k = 0; k < ns; k++) {
+    nrows += (int64_t)nslot[k] * ncs[k];
+    nent += (int64_t)nslot[k] * ncs[k] * ncs[k];
+  }
+  FH_REQUIRE(nrows < 2147483647ll && nent < (1ll << 40), "fh_generic_assembler_create: too many elements");
+  std::vector<int> cnt(ndof + 1, 0);
+  for (int e = 0; e < nel; e++)
+    for (int n = 0; n < ncs[eshape[e]]; n++) {
+      const int d = elem_dof[(size_t)e * nloc + n];
+      FH_REQUIRE(d >= 0 && d < ndof && d < nnode, "fh_generic_assembler_create: element %d, node %d: dof %d outside the system (the classes are numbered one after the other)", e, n, d);
+      cnt[d + 1]++;
+    }
+  int maxrow = 1;
+  for (int r = 0; r < ndof; r++) maxrow = std::max(maxrow, KK->h_rowptr[r + 1] - KK->h_rowptr[r]);
+  const int ncmax = std::max(ncs[0], std::max(ncs[1], ncs[2]));
+  int lpr = ncmax <= 6 ? 4 : ncmax <= 10 ? 8 : 16;
+  while (lpr < 64 && (size_t)(GP_THREADS / lpr) * maxrow * sizeof(double) > GP_LDS_BUDGET) lpr *= 2;
+  FH_REQUIRE((size_t)(GP_THREADS / lpr) * maxrow * sizeof(double) <= GP_LDS_BUDGET, "fh_generic_assembler_create: a row of %d entries is longer than the row pass holds (%d)",
+             maxrow, (int)(GP_LDS_BUDGET / sizeof(double) / (GP_THREADS / 64)));
+
+  // ---- host side of the plan ----
+  fh_generic_assembler_t as = new fh_generic_assembler_s();
+  as->ctx = ctx;
+  as->mat_uid = KK->uid;
+  as->mat_nnz = KK->nnz;
+  as->ndof = ndof, as->nnode = nnode, as->dim = dim, as->ns = ns, as->nel = nel;
+  as->lpr = lpr, as->maxrow = maxrow;
+  as->row_lds = (size_t)(GP_THREADS / lpr) * maxrow * sizeof(double);
+  for (int k = 0; k < 3; k++) {
+    as->rows.row_base[k] = INT_MAX;
+    as->rows.nc[k] = 0;
+    as->rows.kb_base[k] = 0;
+  }
+  {
+    int rb = 0;
+    long long kb = 0;
+    for (int k = 0; k < ns; k++) {
+      as->nc[k] = ncs[k], as->ng[k] = (int)w[k].size(), as->nslot[k] = nslot[k];
+      as->rows.row_base[k] = rb, as->rows.nc[k] = ncs[k], as->rows.kb_base[k] = kb;
+      rb += nslot[k] * ncs[k];
+      kb += (long long)nslot[k] * ncs[k] * ncs[k];
+      const int L = gp_lanes_per_element(ncs[k], ctx->generic_pack);
+      const int epg = GP_THREADS / L;
+      int gcm = std::min(as->ng[k], 32);
+      while (gcm > 1 && epg * gp_elem_doubles(ncs[k], gcm) * sizeof(double) > GP_LDS_BUDGET) gcm = (gcm + 1) / 2;
+      const size_t base = epg * gp_elem_doubles(ncs[k], gcm) * sizeof(double);
+      const size_t tab = ((size_t)as->ng[k] * (1 + ncs[k] + ncs[k] * dim)) * sizeof(double);
+      as->lanes[k] = L, as->gcm[k] = gcm;
+      as->tl[k] = base + tab <= GP_LDS_BUDGET;
+      as->lds[k] = base + (as->tl[k] ? tab : 0);
+      if (as->lds[k] > GP_LDS_BUDGET) {
+        delete as;
+        fh_set_error("fh_generic_assembler_create: shape %d does not fit the LDS of a workgroup", shapes[k]);
+        return 2;
+      }
+    }
+  }
+  for (int d = 0; d < ndof; d++) cnt[d + 1] += cnt[d];
+  // slot of every element inside its shape, the compact dof tables, the adjacency (ids of element rows, ascending element order per dof)
+  std::vector<int> ed[3], slot_elem[3];
+  for (int k = 0; k < ns; k++) {
+    ed[k].reserve((size_t)nslot[k] * ncs[k]);
+    slot_elem[k].reserve(nslot[k]);
+  }
+  std::vector<int> adj(cnt[ndof]), fill(cnt.begin(), cnt.end() - 1);
+  for (int e = 0; e < nel; e++) {
+    const int k = eshape[e], s = (int)slot_elem[k].size();
+    slot_elem[k].push_back(e);
+    for (int n = 0; n < ncs[k]; n++) {
+      const int d = elem_dof[(size_t)e * nloc + n];
+      ed[k].push_back(d);
+      adj[fill[d]++] = as->rows.row_base[k] + s * ncs[k] + n;
+    }
+  }
+
+  // ---- device side: every buffer the object will ever need but a longer source program ----
+  hipStream_t st = ctx->stream;
+  bool bad = false;
+  auto up = [&](const void* h, size_t bytes) -> void* {
+    void* d = bad ? nullptr : gp_alloc(as, bytes);
+    if (!d) {
+      bad = true;
+      return nullptr;
+    }
+    if (h && bytes && hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st) != hipSuccess) bad = true;
+    return d;
+  };
+  as->d_adj_ptr = (int*)up(cnt.data(), cnt.size() * sizeof(int));
+  as->d_adj = (int*)up(adj.data(), adj.size() * sizeof(int));
+  as->d_coords = (double*)up(coords, (size_t)nnode * dim * sizeof(double));
+  for (int k = 0; k < ns; k++) {
+    as->d_ed[k] = (int*)up(ed[k].data(), ed[k].size() * sizeof(int));
+    as->d_w[k] = (double*)up(w[k].data(), w[k].size() * sizeof(double));
+    as->d_phi[k] = (double*)up(phi[k].data(), phi[k].size() * sizeof(double));
+    as->d_dphi[k] = (double*)up(dphi[k].data(), dphi[k].size() * sizeof(double));
+  }
+  as->d_Kb = (double*)up(nullptr, (size_t)nent * sizeof(double));
+  as->d_Fb = (double*)up(nullptr, (size_t)nrows * sizeof(double));
+  as->d_Pos = (int*)up(nullptr, (size_t)nent * sizeof(int));
+  as->d_miss = (unsigned long long*)up(nullptr, sizeof(unsigned long long));
+  if (!bad) {
+    if (hipMalloc((void**)&as->d_prog, GP_PROG_BYTES) == hipSuccess) {
+      as->prog_cap = GP_PROG_BYTES;
+      as->device_bytes += (int64_t)GP_PROG_BYTES;
+      as->device_allocations++;
+    } else {
+      bad = true;
+    }
+  }
+  if (!bad && (hipHostMalloc((void**)&as->h_prog, GP_PROG_BYTES) != hipSuccess || hipEventCreateWithFlags(&as->prog_ev, hipEventDisableTiming) != hipSuccess)) bad = true;
+  if (bad) {
+    hipGetLastError();
+    gp_free(as);
+    fh_set_error("fh_generic_assembler_create: out of device memory (%.2f GB of element rows and positions)", (double)nent * 12 / 1e9);
+    return 2;
+  }
+  if (ctx->debug_poison) {   // tests: the row pass must read nothing the element pass has not written
+    hipMemsetAsync(as->d_Kb, 0xFF, (size_t)nent * sizeof(double), st);
+    hipMemsetAsync(as->d_Fb, 0xFF, (size_t)nrows * sizeof(double), st);
+  }
+  hipMemsetAsync(as->d_miss, 0xFF, sizeof(unsigned long long), st);
+  for (int k = 0; k < ns; k++) {
+    const long long ne = (long long)nslot[k] * ncs[k] * ncs[k];
+    hipLaunchKernelGGL(k_gen_positions, dim3(fh_div_up(ne, 256)), dim3(256), 0, st, ne, ncs[k], as->d_ed[k], KK->d_rowptr, KK->d_col, as->d_Pos + as->rows.kb_base[k],
+                       as->d_miss, (unsigned long long)k << 56);
+  }
+  unsigned long long miss = 0;
+  if (hipMemcpyAsync(&miss, as->d_miss, sizeof(miss), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
+    gp_free(as);
+    fh_set_error("fh_generic_assembler_create: the position kernel failed");
+    return 1;
+  }
+  if (miss != ~0ull) {
+    const int k = (int)(miss >> 56);
+    const long long idx = (long long)(miss & ((1ull << 56) - 1));
+    const int nc = ncs[k], j = (int)(idx % nc), i = (int)((idx / nc) % nc);
+    const long long s = idx / ((long long)nc * nc);
+    const int e = slot_elem[k][s];
+    gp_free(as);
+    fh_set_error("fh_generic_assembler_create: element %d: the pair (%d, %d) = dofs (%d, %d) is not in the pattern of the matrix", e, i, j, ed[k][s * nc + i], ed[k][s * nc + j]);
+    return 2;
+  }
+  // what one assembly cannot avoid moving: element tables, coordinates and state in; values and residual out
+  as->algorithmic_bytes = nrows * 4 + (int64_t)nnode * dim * 8 + (int64_t)ndof * 8 + (int64_t)KK->nnz * 8 + (int64_t)ndof * 8;
+  *out = as;
+  return 0;
+  FH_GUARD_END("fh_generic_assembler_create")
+}
+
+extern "C" int fh_generic_assembler_set_coords(fh_generic_assembler_t as, int nnode, const double* coords) {
+  FH_REQUIRE(as && coords, "fh_generic_assembler_set_coords: null argument");
+  FH_REQUIRE(nnode == as->nnode, "fh_generic_assembler_set_coords: %d nodes given, the object was created on %d", nnode, as->nnode);
+  FH_CHECK_HIP(hipMemcpyAsync(as->d_coords, coords, (size_t)nnode * as->dim * sizeof(double), hipMemcpyHostToDevice, as->ctx->stream));
+  FH_CHECK_HIP(hipStreamSynchronize(as->ctx->stream));     // the caller's array is free again
+  return 0;
+}
+
+// the source program into the object's buffer, when it is not the one already there
+static int gp_stage_program(fh_generic_assembler_t as, fh_expr_t source) {
+  int nv = 0, ncode = 0, nk = 0;
+  FH_TRY(fh_expr_nvars(source, &nv));
+  FH_REQUIRE(nv <= 4, "fh_generic_assembler_assemble: the source expression has %d variables, at most 4 (x, y, z, t) are served", nv);
+  FH_TRY(fh_expr_program(source, &ncode, &nk, nullptr, nullptr));
+  std::vector<int> code(ncode);
+  std::vector<double> consts(std::max(nk, 1), 0.0);
+  FH_TRY(fh_expr_program(source, &ncode, &nk, code.data(), consts.data()));
+  if (as->have_prog && code == as->code && consts == as->consts) return 0;
+  const size_t bytes = consts.size() * sizeof(double) + code.size() * sizeof(int);
+  hipStream_t st = as->ctx->stream;
+  if (bytes > as->prog_cap) {          // a longer program than any before: the one place an assembly allocates (and waits for the kernels that read the old buffer)
+    const size_t cap = std::max(bytes, 2 * as->prog_cap);
+    char *d = nullptr, *h = nullptr;
+    FH_CHECK_HIP(hipStreamSynchronize(st));
+    FH_CHECK_HIP(hipMalloc((void**)&d, cap));
+    if (hipHostMalloc((void**)&h, cap) != hipSuccess) {
+      hipFree(d);
+      fh_set_error("fh_generic_assembler_assemble: out of pinned host memory");
+      return 2;
+    }
+    hipFree(as->d_prog);
+    hipHostFree(as->h_prog);
+    as->device_bytes += (int64_t)cap - (int64_t)as->prog_cap;
+    as->device_allocations++;
+    as->d_prog = d, as->h_prog = h, as->prog_cap = cap;
+    as->prog_copied = false;
+  }
+  if (as->prog_copied) FH_CHECK_HIP(hipEventSynchronize(as->prog_ev));     // the staging area is read by the last upload only
+  memcpy(as->h_prog, consts.data(), consts.size() * sizeof(double));
+  memcpy(as->h_prog + consts.size() * sizeof(double), code.data(), code.size() * sizeof(int));
+  as->have_prog = false;
+  FH_CHECK_HIP(hipMemcpyAsync(as->d_prog, as->h_prog, bytes, hipMemcpyHostToDevice, st));
+  FH_CHECK_HIP(hipEventRecord(as->prog_ev, st));
+  as->prog_copied = true;
+  as->code.swap(code);
+  as->consts.swap(consts);
+  as->have_prog = true;
+  return 0;
+}
+
+extern "C" int fh_generic_assembler_assemble(fh_generic_assembler_t as, fh_vec_t sol, fh_expr_t source, double scale, fh_mat_t KK, fh_vec_t RES) {
+  FH_GUARD_BEGIN
+  FH_REQUIRE(as && RES, "fh_generic_assembler_assemble: null argument");
+  FH_REQUIRE(fh_mat_alive(as->mat_uid) != nullptr, "fh_generic_assembler_assemble: the matrix this object was created on has been destroyed");
+  FH_REQUIRE(KK != nullptr, "fh_generic_assembler_assemble: null matrix");
+  FH_REQUIRE(KK->uid == as->mat_uid && KK->nnz == as->mat_nnz, "fh_generic_assembler_assemble: not the matrix this object was created on (uid %llu, %d non-zeros; created on uid %llu, %d)",
+             (unsigned long long)KK->uid, KK->nnz, (unsigned long long)as->mat_uid, as->mat_nnz);
+  FH_REQUIRE(RES->n_local >= as->ndof && (!sol || sol->n_local >= as->ndof), "fh_generic_assembler_assemble: size mismatch");
+  const int* d_code = nullptr;
+  const double* d_k = nullptr;
+  int ncode = 0;
+  if (source) {
+    FH_TRY(gp_stage_program(as, source));
+    d_k = (const double*)as->d_prog;
+    d_code = (const int*)(as->d_prog + as->consts.size() * sizeof(double));
+    ncode = (int)as->code.size();
+  }
+  for (int k = 0; k < as->ns; k++)
+    if (as->nslot[k]) gp_launch_pairs(as, k, sol ? sol->d : nullptr, scale, d_code, ncode, d_k);
+  hipLaunchKernelGGL(k_gen_rows, dim3(fh_div_up(as->ndof, GP_THREADS / as->lpr)), dim3(GP_THREADS), as->row_lds, as->ctx->stream, as->ndof, as->lpr, as->maxrow, as->rows,
+                     as->d_adj_ptr, as->d_adj, as->d_Kb, as->d_Pos, as->d_Fb, KK->d_rowptr, KK->d_val, RES->d);
+  const bool ok = hipGetLastError() == hipSuccess;
+  fh_mat_values_written(KK);
+  FH_REQUIRE(ok, "fh_generic_assembler_assemble: launch failed");
+  return 0;
+  FH_GUARD_END("fh_generic_assembler_assemble")
+}
+
+extern "C" int fh_generic_assembler_info(fh_generic_assembler_t as, int elems_per_workgroup[3], int64_t* device_bytes, int64_t* algorithmic_bytes,
+                                         int64_t* device_allocations) {
+  FH_REQUIRE(as, "fh_generic_assembler_info: null argument");
+  if (elems_per_workgroup)
+    for (int k = 0; k < 3; k++) elems_per_workgroup[k] = k < as->ns ? GP_THREADS / as->lanes[k] : 0;
+  if (device_bytes) *device_bytes = as->device_bytes;
+  if (algorithmic_bytes) *algorithmic_bytes = as->algorithmic_bytes;
+  if (device_allocations) *device_allocations = as->device_allocations;
+  return 0;
+}
+
+extern "C" int fh_generic_assembler_destroy(fh_generic_assembler_t as) {
+  gp_free(as);
+  return 0;
+}

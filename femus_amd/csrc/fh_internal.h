@@ -91,7 +91,8 @@ struct fh_ctx_s {
   int assemble_sf = 8;               // HEX27/Q2, 64 Gauss points, tensor-product tables: element matrices by sum factorisation on the vector ALU, value = waves per workgroup (0 = off: matrix-core kernel)
   int assemble_sumfac = 1;           // matrix-core element kernel: map Jacobian by sum factorisation (tensor-product tables)
   int assemble_rows2 = 1;            // row pass: two rows per 32-lane group when no row has more than 128 entries
-  int assemble_kpad = 1;             // HEX27/Q2 two-pass assembly: element rows padded to 32 doubles (whole 64-byte lines per row)
+  int generic_pack = 1;              // generic assembler object (fh_generic.hip): 2 / 4 elements per wave for the narrow families; 0 = one element per wave for every shape (the A/B of the probe), read at create
+  int assemble_kpad = 1;            // HEX27/Q2 two-pass assembly: element rows padded to 32 doubles (whole 64-byte lines per row)
   int assemble_sym = 1;              // symmetric-tile HEX27/Q2 element kernel (2 elements per wave)
   int assemble_two_pass = 1;         // 1: element matrices + row gather (default), 0: coloured scatter
   int assemble_fused = 1;            // HEX27/Q2 meshes whose elements come in sibling groups of eight: fused cluster assembly (rows complete inside a group go straight to the CSR arrays)

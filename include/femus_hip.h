@@ -403,6 +403,27 @@ int fh_assemble_poisson_rows(fh_ctx_t ctx, int geom, int fe, int gauss_order, in
  * elem_dof padded to nloc.  A row's entries are summed in ascending element order whatever the shapes. */
 int fh_assemble_poisson_mixed(fh_ctx_t ctx, int fe, int gauss_order, int nel, int nloc, const int* elem_geom, const int* elem_dof, int nnode, const double* coords,
                               fh_vec_t sol, fh_expr_t source, double scale, fh_mat_t KK, fh_vec_t RES);
+/* The two calls above as an OBJECT for repeated assemblies on one mesh and one pattern (the callback of LinearImplicitSystem::MGsolve runs once per linear
+ * iteration on unchanged inputs).  create does once what depends on the mesh and the pattern only and keeps it on the device: the dof -> element adjacency in
+ * ascending element order, the element table, coordinates and FE tables, the CSR position of every entry of every element row (binary search of the sorted rows,
+ * on the device) and all work buffers.  elem_geom NULL: every element is `geom`; otherwise the geom id of every element as in fh_assemble_poisson_mixed (at most
+ * three different ones, of one dimension).  An element pair that KK's pattern does not hold fails create (the message names the element and the pair); every
+ * size check runs before the first allocation, a failing create leaves nothing behind.
+ * assemble only enqueues kernels on the context's stream -- no host loop over the mesh, no allocation, no synchronisation (a source program longer than any
+ * before grows the object's program buffer: the one exception) -- and OVERWRITES KK and RES with, bit for bit, what the one-shot calls give.  KK must be the
+ * matrix of create (same uid and non-zero count, still alive).  sol NULL = 0, source NULL = 0.
+ * set_coords replaces the coordinates (same nnode); nothing else of the plan depends on them.
+ * info: elems_per_workgroup[k] = elements one 256-thread workgroup of the element pass takes for the k-th shape (in the order of the shapes' first elements;
+ * 0 beyond the last shape; 4 = one element per wave, 8 / 16 = two / four), bytes the object holds on the device, the bytes one assembly cannot avoid moving
+ * (element table, coordinates, state in; values, residual out), and the device allocations the object has made in its life.
+ * fh_set_option(ctx, "generic_pack", 0) before create: one element per wave for every shape (measurements). */
+typedef struct fh_generic_assembler_s* fh_generic_assembler_t;
+int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int gauss_order, int nel, int nloc, const int* elem_geom /* NULL: every element is `geom` */, int geom,
+                                const int* elem_dof, int nnode, const double* coords, fh_mat_t KK, fh_generic_assembler_t* out);
+int fh_generic_assembler_set_coords(fh_generic_assembler_t as, int nnode, const double* coords);
+int fh_generic_assembler_assemble(fh_generic_assembler_t as, fh_vec_t sol, fh_expr_t source, double scale, fh_mat_t KK, fh_vec_t RES);
+int fh_generic_assembler_info(fh_generic_assembler_t as, int elems_per_workgroup[3], int64_t* device_bytes, int64_t* algorithmic_bytes, int64_t* device_allocations);
+int fh_generic_assembler_destroy(fh_generic_assembler_t as);
 /* Open-boundary pressure term of the steady Navier-Stokes residual (src/08_equations/assemble/03_navier_stokes.hpp:185-290): on every listed boundary
  * face  aResV[k][node_i] += phi_i * tau * normal[k] * weight  for the dim velocity components (Q2 face nodes), tau = the prescribed pressure -- one
  * number per face (tau) or expression face_expr[f] of the nexpr expressions evaluated at the face Gauss point, as the bdc callback is (:280) -- and
