@@ -1119,6 +1119,14 @@ class Expr:
         _chk(self.L.fh_expr_eval_many(self.h, x.shape[0], _p(x), _p(out)))
         return out
 
+    def eval_device(self, ctx, points):
+        """the values at points[npoints, nvars] from the device compilation of the evaluator, one thread per point (fh_expr_eval_device)"""
+        x = _f64(points).reshape(-1, self.nvars) if self.nvars else _f64(points)
+        n = x.shape[0]
+        out = np.empty(n)
+        _chk(self.L.fh_expr_eval_device(ctx.h, self.h, n, _p(x), _p(out)))
+        return out
+
     def program(self):
         """(code, consts): the postfix program the device evaluator runs (fh_expr_program)"""
         nc, nk = ctypes.c_int(), ctypes.c_int()

@@ -56,7 +56,7 @@ __host__ __device__ inline double fh_expr_device_eval(const int* code, int ncode
           case FHF_EXP: r = exp(a); break;
           case FHF_EXP2: r = exp2(a); break;
           case FHF_FLOOR: r = floor(a); break;
-          case FHF_INT: r = floor(a + 0.5); break;
+          case FHF_INT: r = a < 0.0 ? ceil(a - 0.5) : floor(a + 0.5); break;   // the parser library's int(): nearest, halves away from zero
           case FHF_LOG: r = log(a); break;
           case FHF_LOG10: r = log10(a); break;
           case FHF_LOG2: r = log2(a); break;

@@ -371,6 +371,9 @@ typedef struct fh_expr_s* fh_expr_t;
 int fh_expr_compile(const char* expression, const char* variables, fh_expr_t* expr);
 int fh_expr_eval(fh_expr_t expr, const double* x, double* value);
 int fh_expr_eval_many(fh_expr_t expr, int npts, const double* x /* [npts*nvars] */, double* values);
+/* fh_expr_eval_many through the DEVICE compilation of the evaluator (one thread per point; x and values are host arrays): what the assembly kernels compute
+ * at a Gauss point, one value per point instead of inside a quadrature sum.  Any number of variables. */
+int fh_expr_eval_device(fh_ctx_t ctx, fh_expr_t expr, int npts, const double* x /* [npts*nvars] */, double* values);
 int fh_expr_program(fh_expr_t expr, int* ncode, int* nconst, int* code /* or NULL */, double* consts /* or NULL */);
 int fh_expr_nvars(fh_expr_t expr, int* nvars);      /* number of variables the expression was compiled over */
 int fh_expr_destroy(fh_expr_t expr);

@@ -8,6 +8,8 @@ import pytest
 
 from femus_amd import capi
 
+import expr_fixture as fx
+
 PTS = np.array([[0.3, 0.8, -0.2, 0.5], [1.7, -0.4, 0.9, 0.0], [0.0, 0.0, 0.0, 0.0], [-1.25, 2.5, 0.75, 3.0]])
 
 CASES = [
@@ -38,6 +40,34 @@ def test_expression_matches_python(text, fn):
     assert np.allclose(got, ref, rtol=1e-15, atol=1e-15)
     assert np.array_equal(e(PTS), got)                    # batch entry point: identical
     e.destroy()
+
+
+@pytest.mark.parametrize("text", fx.TEXTS)
+def test_host_build_matches_the_correctly_rounded_fixture(text):
+    """the host compilation of fh_expr_device_eval against tests/golden/expr_vectors.npz (mpmath at 60 digits, rounded once): the fixture's bits for
+    what IEEE 754 rounds correctly or what is exact, 1 ulp for a libm function, one more for the division in cot / sec / csc.  The same table pins the
+    device compilation (test_gpu_expr_device.py), so the two are tied to one reference and not to each other"""
+    x, want = fx.vectors(text)
+    e = capi.Expr(text, fx.VARIABLES)
+    got = e(x)
+    e.destroy()
+    if text in fx.EXACT:
+        bad = ~fx.same_bits(got, want)
+        assert not bad.any(), (text, x[bad][:4], got[bad][:4], want[bad][:4])
+    else:
+        err = fx.ulps(got, want)
+        bound = 2 if text in ("cot(x)", "sec(x)", "csc(x)") else 1
+        assert err.max() <= bound, (text, err.max(), x[err.argmax()])
+
+
+@pytest.mark.parametrize("text", fx.SPECIAL_TEXTS)
+def test_host_build_special_arguments_give_the_class_numpy_gives(text):
+    """zeros, infinities, NaN, 1e308 and 5e-324: NaN, +inf, -inf or a finite value as numpy on the CPU has it (signs of zero are not compared)"""
+    x, cls = fx.special_vectors(text)
+    e = capi.Expr(text, fx.VARIABLES)
+    got = e(x)
+    e.destroy()
+    assert np.array_equal(fx.classes(got), cls), (text, x[fx.classes(got) != cls], got[fx.classes(got) != cls])
 
 
 @pytest.mark.parametrize("bad", ["1+", "foo(x)", "x+q", "(x", "1 2", "if(x,1)", "x,y"])
