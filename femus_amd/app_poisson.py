@@ -248,8 +248,16 @@ class Poisson001:
         from . import mixed_mesh
         ctx = self.ctx
         levels = [mixed_mesh.tri_box(self.box[0], self.box[1], self.lo[:2], self.hi[:2]) if self.box is not None else mixed_mesh.read_gambit(self.mesh_file)]
-        for _ in range(1, self.nlevels):
-            levels.append(mixed_mesh.refine(*levels[-1][:4]))
+        # level 0 goes up once and is refined on the device (capi.ElementMesh: the arrays of mixed_mesh.refine, integer for integer and bit for bit); every
+        # level comes down once for the host-side Dirichlet lists and transfers below
+        resident = [capi.ElementMesh.from_arrays(ctx, *levels[0])]
+        try:
+            for _ in range(1, self.nlevels):
+                resident.append(resident[-1].refine())
+                levels.append(resident[-1].arrays())
+        finally:
+            for m in resident:
+                m.destroy()
         if not self.mixed:
             g = self.geom
             levels = [(kind, ed[:, :mixed_mesh.NLOC[g]], xs, ff[:, :mixed_mesh.NFACES[g]], own) for kind, ed, xs, ff, own in levels]

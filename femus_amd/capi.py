@@ -731,6 +731,59 @@ def fe_jacobian(ctx, mesh, fe, order="seventh", hessians=False, elem_dof=None, c
     return (w, g, n) if hessians else (w, g)
 
 
+class ElementMesh:
+    """an element mesh of any mix of hexahedra, tetrahedra and prisms (or quadrilaterals and triangles) resident on the device (fh_elem_mesh_*): the tuple
+    (kind, ed, xs, ff, own) of femus_amd/mixed_mesh.py, uploaded once; refine() is mixed_mesh.refine on the device, integer for integer and bit for bit, and
+    leaves the fine mesh there; arrays() downloads"""
+    _NAMES = np.array([{v: k for k, v in GEOM.items()}[c] for c in range(6)])
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.L, self.h = ctx, ctx.L, handle
+        dim, nel, nnode, lev = [ctypes.c_int() for _ in range(4)]
+        own = (ctypes.c_int * 3)()
+        _chk(self.L.fh_elem_mesh_info(self.h, ctypes.byref(dim), ctypes.byref(nel), ctypes.byref(nnode), own, ctypes.byref(lev)))
+        self.dim, self.nel, self.nnode, self.level, self.own = dim.value, nel.value, nnode.value, lev.value, [int(k) for k in own]
+
+    @classmethod
+    def from_arrays(cls, ctx, kind, ed, xs, ff, own):
+        """kind[nel] names of GEOM, ed[nel, 27] and ff[nel, 6] padded with -1, xs[nnode, dim], own[3]; refused with a message when the input is not a mesh"""
+        kind, xs = np.asarray(kind), _f64(xs)
+        unknown = sorted(set(kind.tolist()) - set(GEOM))
+        if unknown:
+            raise FemusHipError("ElementMesh.from_arrays: unknown shapes %s" % unknown)
+        code = np.zeros(kind.shape[0], dtype=np.int32)
+        for name, c in GEOM.items():
+            code[kind == name] = c
+        for name, a, w in (("ed", ed, 27), ("ff", ff, 6)):
+            if np.ndim(a) != 2 or np.shape(a) != (kind.shape[0], w):
+                raise FemusHipError("ElementMesh.from_arrays: %s must be [%d, %d], not %s" % (name, kind.shape[0], w, np.shape(a)))
+            if np.size(a) and (np.min(a) < -2 ** 31 or np.max(a) >= 2 ** 31):
+                raise FemusHipError("ElementMesh.from_arrays: %s does not fit 32-bit integers" % name)
+        if xs.ndim != 2 or len(own) != 3:
+            raise FemusHipError("ElementMesh.from_arrays: xs must be [nnode, dim] and own three numbers")
+        ed, ff, own = _i32(ed), _i32(ff), _i32(own)
+        h = ctypes.c_void_p()
+        _chk(ctx.L.fh_elem_mesh_create(ctx.h, int(xs.shape[1]), int(kind.shape[0]), int(xs.shape[0]), _p(code), _p(ed), _p(xs), _p(ff), _p(own), ctypes.byref(h)))
+        return cls(ctx, h)
+
+    def refine(self):
+        h = ctypes.c_void_p()
+        _chk(self.L.fh_elem_mesh_refine(self.h, ctypes.byref(h)))
+        return ElementMesh(self.ctx, h)
+
+    def arrays(self):
+        """(kind, ed, xs, ff, own) as mixed_mesh holds them"""
+        code, ed, ff = np.empty(self.nel, np.int32), np.empty((self.nel, 27), np.int32), np.empty((self.nel, 6), np.int32)
+        xs = np.empty((self.nnode, self.dim))
+        _chk(self.L.fh_elem_mesh_get(self.h, _p(code), _p(ed), _p(xs), _p(ff)))
+        return self._NAMES[code], ed.astype(np.int64), xs, ff.astype(np.int64), list(self.own)
+
+    def destroy(self):
+        if self.h:
+            _chk(self.L.fh_elem_mesh_destroy(self.h))
+            self.h = None
+
+
 def fe_elem_prolongator(geom, fe):
     L = load_library()
     nch, nc = ctypes.c_int(), ctypes.c_int()

@@ -1,0 +1,498 @@
+// A device-resident ELEMENT mesh of any mix of the five shapes (HEX27, QUAD9, TRI7, TET15, WEDGE21) and its uniform refinement on the device: what
+// femus_amd/mixed_mesh.py: refine does on the host with sorts, integer for integer and, for the coordinates, bit for bit (tests/test_gpu_element_mesh.py).
+//
+// MeshRefinement::RefineMesh for all shapes + the renumbering of Mesh.cpp:517-559, nprocs = 1.  The scheme is fh_meshdev.hip's: the final id of a node is
+// the rank of its first touch in the order (class, fine element, local node), an integer `occ`.
+//   1. children: fine element nch * e + j is child j of e and has its shape; vertices through the shape's fine-to-coarse vertex table, face flags through a
+//      [shape][child][face] table of the father's face a child face lies in (both built on the host from fhfe's element prolongator and face nodes).
+//   2. every (fine element, local node) names the node it touches: a coarse node (child vertices), an EDGE (two vertex ids), a TRIANGULAR face (three), a
+//      QUADRILATERAL face (its smallest vertex and the vertex diagonal to it) or the element itself (its centre).  An edge and a face never share a node, so
+//      each family has an open-addressing table of its own, claimed with a 64-bit atomicCAS.  Keys are exact for any 32-bit ids: an edge and a quadrilateral
+//      are two ids in one word; a triangle is (slot of the edge of its two smallest vertices in the edge table, third vertex) -- the edge is looked up by
+//      inserting it, which returns the one slot the key ever gets whoever claims it.  first[node] = min occ by atomicMin.
+//   3. flag[occ] = (first[node] == occ); an exclusive scan of the flags is the numbering.  The widths of the classes differ per element in a mixed mesh: the
+//      offset of (class, element) comes from exclusive scans of the per-element class widths over the COARSE elements (the children of an element are
+//      consecutive and have its shape).  Coarse nodes no child holds (face nodes and centres of the fathers) are never touched and drop out.
+//   4. every (element, local node) reads its id; the first touch of a node writes its coordinates: a coarse node's are copied, a new node's are the row of
+//      the CREATING child's element prolongator times the father's coordinates, over the father's local nodes k = 0 .. nl - 1 in that order from +0.0, every
+//      product and every sum rounded on its own (mixed_mesh.py: refine; NOT the ascending-node-id order of the hex path).  The first touch is the child the
+//      host's first_touch calls the creator: the smallest fine element that holds the key.
+// Slot numbers depend on the race; ids, flags and coordinates do not.
+#include "fh_internal.h"
+#include "fh_fe.h"
+#include <cmath>
+#include <memory>
+#include <mutex>
+
+namespace {
+constexpr int EM_W = 27, EM_F = 6, EM_G = 6;      // widths of the padded element and face rows; shape codes 0 .. 5 (2 = line: not a mesh shape here)
+constexpr unsigned long long EM_EMPTY = ~0ull;
+constexpr int EM_NONE = 0x7f7f7f7f;
+
+struct EmTab {                    // per shape code; lives in device memory
+  int nv[EM_G], ne[EM_G], nl[EM_G], nf[EM_G], ep[EM_G];     // ends of the vertex / edge-node / all classes, faces, first double of the shape's prolongator
+  signed char f2c[EM_G][8][8];            // [child][child vertex] -> father's local node
+  signed char edge_v[EM_G][12][2];        // the two vertices of edge node nv + m
+  signed char face_of[EM_G][EM_W];        // local node -> the face it is the last node of (-1: none)
+  signed char nvf[EM_G][EM_F];            // vertices per face
+  signed char face_v[EM_G][EM_F][4];
+  signed char face_diag[EM_G][EM_F][4];   // quadrilateral faces: position of the vertex diagonal to vertex k
+  signed char cff[EM_G][8][EM_F];         // [child][child face] -> father's face whose flag it inherits (-1: none)
+};
+struct EmTables {
+  EmTab h;
+  std::vector<double> EP;         // every shape's [nch][nl][nl], one after the other
+  bool ok = false;
+  std::string why;
+};
+struct EmDevTables {
+  EmTab* d_tab = nullptr;
+  double* d_EP = nullptr;
+  ~EmDevTables() {
+    if (d_tab) hipFree(d_tab);
+    if (d_EP) hipFree(d_EP);
+  }
+};
+
+bool em_shape(int g) { return g == fhfe::GEOM_HEX || g == fhfe::GEOM_QUAD || g == fhfe::GEOM_TRI || g == fhfe::GEOM_TET || g == fhfe::GEOM_WEDGE; }
+
+// the tables of mixed_mesh.py: tables, from the same sources
+void em_build_tables(EmTables& T) {
+  using namespace fhfe;
+  memset(&T.h, 0, sizeof(T.h));
+  memset(T.h.face_of, -1, sizeof(T.h.face_of));
+  memset(T.h.cff, -1, sizeof(T.h.cff));
+  auto fail = [&](const char* what, int g) { T.why = std::string(what) + " (shape " + std::to_string(g) + ")"; };
+  for (int g = 0; g < EM_G; g++) {
+    if (!em_shape(g)) continue;
+    const int dim = dim_of(g), nv = nvert_of(g), ne = nedge_end_of(g), nl = nloc_of(g), nf = nfaces_of(g), nch = dim == 3 ? 8 : 4;
+    T.h.nv[g] = nv; T.h.ne[g] = ne; T.h.nl[g] = nl; T.h.nf[g] = nf; T.h.ep[g] = (int)T.EP.size();
+    std::vector<double> P;
+    elem_prolongator(g, FE_BIQUADRATIC, P);
+    if (P.size() != (size_t)nch * nl * nl || nv > 8 || ne - nv > 12 || nl > EM_W || nf > EM_F) return fail("unexpected sizes", g);
+    T.EP.insert(T.EP.end(), P.begin(), P.end());
+    for (int j = 0; j < nch; j++)
+      for (int v = 0; v < nv; v++) {               // the argmax of the prolongator row of the child's vertex (the first of equal maxima)
+        const double* row = &P[((size_t)j * nl + v) * nl];
+        int best = 0;
+        for (int k = 1; k < nl; k++)
+          if (row[k] > row[best]) best = k;
+        T.h.f2c[g][j][v] = (signed char)best;
+      }
+    double x[EM_W][3] = {};
+    for (int n = 0; n < nl; n++) node_ref(g, n, x[n]);
+    auto close = [&](const double* m, const double* ref) {
+      for (int d = 0; d < dim; d++)
+        if (std::fabs(m[d] - ref[d]) > 1e-8 + 1e-5 * std::fabs(ref[d])) return false;
+      return true;
+    };
+    for (int m = nv; m < ne; m++) {                // an edge node's two vertices: the first pair whose middle it is
+      bool found = false;
+      for (int a = 0; a < nv && !found; a++)
+        for (int b = a + 1; b < nv && !found; b++) {
+          double mid[3];
+          for (int d = 0; d < dim; d++) mid[d] = 0.5 * (x[a][d] + x[b][d]);
+          if (close(mid, x[m])) {
+            T.h.edge_v[g][m - nv][0] = (signed char)a;
+            T.h.edge_v[g][m - nv][1] = (signed char)b;
+            found = true;
+          }
+        }
+      if (!found) return fail("an edge node between no two vertices", g);
+    }
+    int fn[EM_F][9], fnn[EM_F];
+    for (int f = 0; f < nf; f++) {
+      fnn[f] = face_nodes(g, FE_BIQUADRATIC, f, fn[f]);
+      const int nvf = fnn[f] == 9 ? 4 : fnn[f] == 7 ? 3 : fnn[f] == 3 ? 2 : 0;
+      if (!nvf) return fail("a face of an unknown kind", g);
+      T.h.nvf[g][f] = (signed char)nvf;
+      for (int k = 0; k < std::min(nvf, 4); k++) T.h.face_v[g][f][k] = (signed char)fn[f][k];
+      const int last = fn[f][fnn[f] - 1];
+      if (dim == 3) {
+        if (last < ne || last >= nl - 1 || T.h.face_of[g][last] >= 0) return fail("the last node of a face is not a face node of its own", g);
+        T.h.face_of[g][last] = (signed char)f;
+      }
+      if (nvf == 4)
+        for (int k = 0; k < 4; k++) {
+          int diag = -1;
+          for (int k2 = 0; k2 < 4; k2++) {
+            double mid[3];
+            for (int d = 0; d < dim; d++) mid[d] = 0.5 * (x[fn[f][k]][d] + x[fn[f][k2]][d]);
+            if (k2 != k && close(mid, x[last])) diag = k2;
+          }
+          if (diag < 0) return fail("a quadrilateral face without a diagonal", g);
+          T.h.face_diag[g][f][k] = (signed char)diag;
+        }
+    }
+    if (dim == 3)
+      for (int i = ne; i < nl - 1; i++)
+        if (T.h.face_of[g][i] < 0) return fail("a face node of no face", g);
+    // child face lf inherits father face f: the same number of vertices and every vertex of lf, through f2c, a node of f (mid-nodes included); the last f wins
+    for (int j = 0; j < nch; j++)
+      for (int lf = 0; lf < nf; lf++)
+        for (int f = 0; f < nf; f++) {
+          if (T.h.nvf[g][lf] != T.h.nvf[g][f]) continue;
+          bool all = true;
+          for (int k = 0; k < T.h.nvf[g][lf] && all; k++) {
+            const int c = T.h.f2c[g][j][fn[lf][k]];
+            bool in = false;
+            for (int q = 0; q < fnn[f]; q++) in = in || fn[f][q] == c;
+            all = in;
+          }
+          if (all) T.h.cff[g][j][lf] = (signed char)f;
+        }
+  }
+  T.ok = true;
+}
+
+const EmTables& em_tables() {
+  static EmTables T;
+  static std::once_flag once;
+  std::call_once(once, [] { em_build_tables(T); });
+  return T;
+}
+
+struct Scratch {
+  std::vector<void*> p;
+  ~Scratch() {
+    for (void* q : p)
+      if (q) hipFree(q);
+  }
+  template <class T>
+  int get(T** out, size_t n) {
+    void* q = nullptr;
+    if (hipMalloc(&q, std::max<size_t>(n, 2) * sizeof(T)) != hipSuccess) {
+      fh_set_error("fh_elem_mesh_refine: out of device memory");
+      return 2;
+    }
+    p.push_back(q);
+    *out = (T*)q;
+    return 0;
+  }
+};
+}   // namespace
+
+struct fh_elem_mesh_s {
+  fh_ctx_t ctx = nullptr;
+  int dim = 0, nel = 0, nnode = 0, own[3] = {0, 0, 0}, level = 0;
+  int64_t count[EM_G] = {0, 0, 0, 0, 0, 0};      // elements per shape: sizes every allocation of a refinement without asking the device
+  int* d_geom = nullptr;          // [nel]
+  int* d_ed = nullptr;            // [nel * 27], -1 beyond the shape's width
+  double* d_x = nullptr;          // [nnode * dim]
+  int* d_ff = nullptr;            // [nel * 6], -1 beyond the shape's faces
+  std::shared_ptr<EmDevTables> tab;               // shared along a chain of refinements
+  ~fh_elem_mesh_s() {
+    for (void* q : {(void*)d_geom, (void*)d_ed, (void*)d_x, (void*)d_ff})
+      if (q) hipFree(q);
+  }
+};
+
+// ---- kernels: one thread per (fine element, column of the padded row) ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_em_widths(const EmTab* __restrict__ T, int nel, const int* __restrict__ geom, int* __restrict__ w0, int* __restrict__ w1,
+                                                   int* __restrict__ w2) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= nel) return;
+  const int g = geom[e];
+  w0[e] = T->nv[g];
+  w1[e] = T->ne[g] - T->nv[g];
+  w2[e] = T->nl[g] - T->ne[g];
+}
+
+__global__ __launch_bounds__(256) void k_em_children(const EmTab* __restrict__ T, int nel_f, int nch, const int* __restrict__ geom_c, const int* __restrict__ ed_c,
+                                                     const int* __restrict__ ff_c, int* __restrict__ geom_f, int* __restrict__ ed_f, int* __restrict__ ff_f) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)nel_f * EM_W) return;
+  const int jel = (int)(t / EM_W), i = (int)(t % EM_W), e = jel / nch, j = jel % nch;
+  const int g = geom_c[e];
+  if (i == 0) geom_f[jel] = g;
+  ed_f[t] = i < T->nv[g] ? ed_c[(size_t)e * EM_W + T->f2c[g][j][i]] : -1;
+  if (i < EM_F) {
+    const int f = i < T->nf[g] ? T->cff[g][j][i] : -1;
+    ff_f[(size_t)jel * EM_F + i] = f >= 0 ? ff_c[(size_t)e * EM_F + f] : -1;
+  }
+}
+
+// plain read, then CAS, then the returned value: a stale plain read can only show "empty", and the CAS corrects it (fh_meshdev.hip: rf_insert)
+__device__ __forceinline__ int em_insert(unsigned long long* keys, unsigned mask, int shift, unsigned long long key) {
+  unsigned s = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> shift) & mask;
+  for (;;) {
+    unsigned long long old = keys[s];
+    if (old == key) return (int)s;
+    if (old == EM_EMPTY) {
+      old = atomicCAS(&keys[s], EM_EMPTY, key);
+      if (old == EM_EMPTY || old == key) return (int)s;
+    }
+    s = (s + 1) & mask;
+  }
+}
+__device__ __forceinline__ unsigned long long em_pair(int a, int b) { return ((unsigned long long)(unsigned)a << 32) | (unsigned)b; }
+
+struct EmOcc {                    // the order (class, fine element, local node)
+  const int *o0, *o1, *o2;        // exclusive scans of the class widths over the coarse elements
+  int base1, base2, nch;
+};
+__device__ __forceinline__ int em_occ(const EmTab* T, const EmOcc& O, int g, int e, int j, int i) {
+  const int nv = T->nv[g], ne = T->ne[g];
+  if (i < nv) return O.nch * O.o0[e] + j * nv + i;
+  if (i < ne) return O.base1 + O.nch * O.o1[e] + j * (ne - nv) + (i - nv);
+  return O.base2 + O.nch * O.o2[e] + j * (T->nl[g] - ne) + (i - ne);
+}
+
+struct EmHash {
+  unsigned long long* keys;
+  unsigned mask;
+  int shift, id0;                 // id0: the first provisional id of the family
+};
+
+__global__ __launch_bounds__(256) void k_em_touch(const EmTab* __restrict__ T, EmOcc O, int nel_f, const int* __restrict__ geom_f, const int* __restrict__ ed_f,
+                                                  EmHash E, EmHash TR, EmHash Q, int C0, int* __restrict__ first, int* __restrict__ ident) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)nel_f * EM_W) return;
+  const int jel = (int)(t / EM_W), i = (int)(t % EM_W);
+  const int g = geom_f[jel];
+  const int nv = T->nv[g], ne = T->ne[g], nl = T->nl[g];
+  if (i >= nl) return;
+  const int* fd = ed_f + (size_t)jel * EM_W;
+  int id;
+  if (i < nv) {
+    id = fd[i];
+  } else if (i < ne) {
+    int a = fd[T->edge_v[g][i - nv][0]], b = fd[T->edge_v[g][i - nv][1]];
+    if (a > b) { const int c = a; a = b; b = c; }
+    id = E.id0 + em_insert(E.keys, E.mask, E.shift, em_pair(a, b));
+  } else if (i < nl - 1) {
+    const int f = T->face_of[g][i];
+    if (T->nvf[g][f] == 3) {
+      int a = fd[T->face_v[g][f][0]], b = fd[T->face_v[g][f][1]], c = fd[T->face_v[g][f][2]], s;
+      if (a > b) { s = a; a = b; b = s; }
+      if (b > c) { s = b; b = c; c = s; }
+      if (a > b) { s = a; a = b; b = s; }
+      const int slot = em_insert(E.keys, E.mask, E.shift, em_pair(a, b));       // the edge of the two smallest vertices: the slot it has or gets now
+      id = TR.id0 + em_insert(TR.keys, TR.mask, TR.shift, em_pair(slot, c));
+    } else {
+      int v[4], km = 0;
+      for (int k = 0; k < 4; k++) v[k] = fd[T->face_v[g][f][k]];
+      for (int k = 1; k < 4; k++)
+        if (v[k] < v[km]) km = k;
+      id = Q.id0 + em_insert(Q.keys, Q.mask, Q.shift, em_pair(v[km], v[T->face_diag[g][f][km]]));
+    }
+  } else {
+    id = C0 + jel;
+  }
+  const int occ = em_occ(T, O, g, jel / O.nch, jel % O.nch, i);
+  ident[occ] = id;
+  atomicMin(&first[id], occ);
+}
+
+__global__ __launch_bounds__(256) void k_em_flag(int nocc, const int* __restrict__ first, const int* __restrict__ ident, int* __restrict__ flag) {
+  const int occ = blockIdx.x * 256 + threadIdx.x;
+  if (occ < nocc) flag[occ] = first[ident[occ]] == occ;
+}
+
+__global__ __launch_bounds__(256) void k_em_number(const EmTab* __restrict__ T, EmOcc O, int nel_f, int dim, const int* __restrict__ geom_f, const int* __restrict__ first,
+                                                   const int* __restrict__ ident, const int* __restrict__ pos, const int* __restrict__ ed_c,
+                                                   const double* __restrict__ xc, const double* __restrict__ EP, int* __restrict__ ed_f, double* __restrict__ xf) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)nel_f * EM_W) return;
+  const int jel = (int)(t / EM_W), i = (int)(t % EM_W);
+  const int g = geom_f[jel];
+  const int nl = T->nl[g];
+  if (i >= nl) return;
+  const int e = jel / O.nch, j = jel % O.nch;
+  const int occ = em_occ(T, O, g, e, j, i);
+  const int node = ident[occ], fo = first[node];
+  const int id = pos[fo];
+  ed_f[t] = id;
+  if (fo != occ) return;
+  double s[3] = {0.0, 0.0, 0.0};
+  if (i < T->nv[g]) {             // a coarse node keeps its coordinates
+    for (int d = 0; d < dim; d++) s[d] = xc[(size_t)node * dim + d];
+  } else {
+    const double* row = EP + T->ep[g] + ((size_t)j * nl + i) * nl;
+    const int* cd = ed_c + (size_t)e * EM_W;
+    for (int k = 0; k < nl; k++) {
+      const double w = row[k];
+      const double* x = xc + (size_t)cd[k] * dim;
+      for (int d = 0; d < dim; d++) s[d] = __dadd_rn(s[d], __dmul_rn(w, x[d]));
+    }
+  }
+  for (int d = 0; d < dim; d++) xf[(size_t)id * dim + d] = s[d];
+}
+
+// ---- C ABI ---------------------------------------------------------------------------------------------------------------------------------------------------
+static int em_alloc(fh_elem_mesh_s* m, bool coords) {
+  auto get = [&](void** p, size_t bytes) -> int {       // every entry is written before it is read; poisoned, a missed one is a NaN or an id of -1
+    FH_CHECK_HIP(hipMalloc(p, std::max<size_t>(bytes, 8)));
+    if (m->ctx->debug_poison) FH_CHECK_HIP(hipMemsetAsync(*p, 0xFF, std::max<size_t>(bytes, 8), m->ctx->stream));
+    return 0;
+  };
+  FH_TRY(get((void**)&m->d_geom, (size_t)m->nel * sizeof(int)));
+  FH_TRY(get((void**)&m->d_ed, (size_t)m->nel * EM_W * sizeof(int)));
+  FH_TRY(get((void**)&m->d_ff, (size_t)m->nel * EM_F * sizeof(int)));
+  if (coords) FH_TRY(get((void**)&m->d_x, (size_t)m->nnode * m->dim * sizeof(double)));
+  return 0;
+}
+
+extern "C" int fh_elem_mesh_create(fh_ctx_t ctx, int dim, int nel, int nnode, const int* elem_geom, const int* elem_dof, const double* coords, const int* face_flag,
+                                   const int own[3], fh_elem_mesh_t* out) {
+  FH_GUARD_BEGIN
+  FH_REQUIRE(ctx && out && own && nel >= 0 && nnode >= 0, "fh_elem_mesh_create: null or negative argument");
+  FH_REQUIRE(dim == 2 || dim == 3, "fh_elem_mesh_create: dim must be 2 or 3, not %d", dim);
+  FH_REQUIRE((elem_geom && elem_dof && face_flag) || nel == 0, "fh_elem_mesh_create: null element arrays");
+  FH_REQUIRE(coords || nnode == 0, "fh_elem_mesh_create: null coordinates");
+  const EmTables& H = em_tables();
+  FH_REQUIRE(H.ok, "fh_elem_mesh_create: reference-element tables: %s", H.why.c_str());
+  std::unique_ptr<fh_elem_mesh_s> m(new fh_elem_mesh_s());
+  for (int e = 0; e < nel; e++) {
+    const int g = elem_geom[e];
+    FH_REQUIRE(g != fhfe::GEOM_LINE, "fh_elem_mesh_create: element %d is a line (shape code 2): not an element of these meshes", e);
+    FH_REQUIRE(g >= 0 && g < EM_G, "fh_elem_mesh_create: element %d has shape code %d: 0 (hex), 1 (quad), 3 (triangle), 4 (tetrahedron), 5 (prism)", e, g);
+    FH_REQUIRE(fhfe::dim_of(g) == dim, "fh_elem_mesh_create: element %d of shape code %d is %d-dimensional in a %d-dimensional mesh", e, g, fhfe::dim_of(g), dim);
+    const int nl = H.h.nl[g], nf = H.h.nf[g];
+    const int* row = elem_dof + (size_t)e * EM_W;
+    for (int k = 0; k < EM_W; k++) {
+      if (k < nl)
+        FH_REQUIRE(row[k] >= 0 && row[k] < nnode, "fh_elem_mesh_create: element %d, local node %d: id %d outside [0, %d)", e, k, row[k], nnode);
+      else
+        FH_REQUIRE(row[k] == -1, "fh_elem_mesh_create: element %d, entry %d beyond the shape's %d nodes is %d, not -1", e, k, nl, row[k]);
+    }
+    for (int f = nf; f < EM_F; f++)
+      FH_REQUIRE(face_flag[(size_t)e * EM_F + f] == -1, "fh_elem_mesh_create: element %d, face entry %d beyond the shape's %d faces is %d, not -1", e, f, nf,
+                 face_flag[(size_t)e * EM_F + f]);
+    m->count[g]++;
+  }
+  m->ctx = ctx; m->dim = dim; m->nel = nel; m->nnode = nnode; m->level = 0;
+  for (int k = 0; k < 3; k++) m->own[k] = own[k];
+  hipStream_t st = ctx->stream;
+  m->tab = std::make_shared<EmDevTables>();
+  FH_CHECK_HIP(hipMalloc((void**)&m->tab->d_tab, sizeof(EmTab)));
+  FH_CHECK_HIP(hipMalloc((void**)&m->tab->d_EP, H.EP.size() * sizeof(double)));
+  FH_CHECK_HIP(hipMemcpyAsync(m->tab->d_tab, &H.h, sizeof(EmTab), hipMemcpyHostToDevice, st));
+  FH_CHECK_HIP(hipMemcpyAsync(m->tab->d_EP, H.EP.data(), H.EP.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  FH_TRY(em_alloc(m.get(), true));
+  if (nel) {
+    FH_CHECK_HIP(hipMemcpyAsync(m->d_geom, elem_geom, (size_t)nel * sizeof(int), hipMemcpyHostToDevice, st));
+    FH_CHECK_HIP(hipMemcpyAsync(m->d_ed, elem_dof, (size_t)nel * EM_W * sizeof(int), hipMemcpyHostToDevice, st));
+    FH_CHECK_HIP(hipMemcpyAsync(m->d_ff, face_flag, (size_t)nel * EM_F * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  if (nnode) FH_CHECK_HIP(hipMemcpyAsync(m->d_x, coords, (size_t)nnode * dim * sizeof(double), hipMemcpyHostToDevice, st));
+  FH_CHECK_HIP(hipStreamSynchronize(st));       // the caller's arrays are free again
+  *out = m.release();
+  return 0;
+  FH_GUARD_END("fh_elem_mesh_create")
+}
+
+extern "C" int fh_elem_mesh_refine(fh_elem_mesh_t C, fh_elem_mesh_t* out) {
+  FH_GUARD_BEGIN
+  FH_REQUIRE(C && out, "fh_elem_mesh_refine: null argument");
+  const EmTab& H = em_tables().h;
+  fh_ctx_t ctx = C->ctx;
+  hipStream_t st = ctx->stream;
+  const int dim = C->dim, nch = dim == 3 ? 8 : 4, nel_c = C->nel;
+  // every size follows from the number of elements of each shape
+  int64_t W[3] = {0, 0, 0}, nE = 0, nT = 0, nQ = 0;
+  for (int g = 0; g < EM_G; g++) {
+    const int64_t n = C->count[g] * nch;
+    if (!n) continue;
+    W[0] += n * H.nv[g];
+    W[1] += n * (H.ne[g] - H.nv[g]);
+    W[2] += n * (H.nl[g] - H.ne[g]);
+    if (dim == 3)
+      for (int f = 0; f < H.nf[g]; f++) (H.nvf[g][f] == 3 ? nT : nQ) += n;
+  }
+  nE = W[1];
+  const int64_t nel_f64 = (int64_t)nel_c * nch, nocc64 = W[0] + W[1] + W[2];
+  auto log2cap = [](int64_t nkeys) {            // every key fits with load <= 1/2 even if no edge or face were shared
+    int l = 6;
+    while (((int64_t)1 << l) < 2 * nkeys) l++;
+    return l;
+  };
+  const int lE = log2cap(nE), lT = log2cap(nT), lQ = log2cap(nQ);
+  const int64_t nident64 = (int64_t)C->nnode + ((int64_t)1 << lE) + ((int64_t)1 << lT) + ((int64_t)1 << lQ) + nel_f64;
+  FH_REQUIRE(nocc64 < (int64_t)EM_NONE && nel_f64 * EM_W < ((int64_t)1 << 31),
+             "fh_elem_mesh_refine: the %lld fine elements' first-touch order does not fit 32-bit integers", (long long)nel_f64);
+  FH_REQUIRE(nident64 < (int64_t)EM_NONE, "fh_elem_mesh_refine: the node table of %lld fine elements does not fit 32-bit ids", (long long)nel_f64);
+  const int nel_f = (int)nel_f64, nocc = (int)nocc64;
+  const size_t capE = (size_t)1 << lE, capT = (size_t)1 << lT, capQ = (size_t)1 << lQ, nident = (size_t)nident64, nthr = (size_t)nel_f * EM_W;
+
+  std::unique_ptr<fh_elem_mesh_s> F(new fh_elem_mesh_s());
+  F->ctx = ctx; F->dim = dim; F->nel = nel_f; F->level = C->level + 1; F->tab = C->tab;
+  for (int g = 0; g < EM_G; g++) F->count[g] = C->count[g] * nch;
+  FH_TRY(em_alloc(F.get(), false));
+
+  Scratch B;
+  int *d_w, *d_off, *d_bsum, *d_first, *d_ident, *d_flag;
+  unsigned long long *d_kE, *d_kT, *d_kQ;
+  const size_t nw = (size_t)nel_c + 1;
+  if (B.get(&d_w, 3 * nw) || B.get(&d_off, 3 * nw) || B.get(&d_bsum, (size_t)std::max(nocc, nel_c) / FH_SCAN_BLOCK + 2) || B.get(&d_first, nident) ||
+      B.get(&d_ident, (size_t)nocc) || B.get(&d_flag, (size_t)nocc + 1) || B.get(&d_kE, capE) || B.get(&d_kT, capT) || B.get(&d_kQ, capQ))
+    return 2;
+  if (ctx->debug_poison) {
+    FH_CHECK_HIP(hipMemsetAsync(d_ident, 0xFF, std::max<size_t>(nocc, 2) * sizeof(int), st));
+    FH_CHECK_HIP(hipMemsetAsync(d_flag, 0xFF, ((size_t)nocc + 1) * sizeof(int), st));
+    FH_CHECK_HIP(hipMemsetAsync(d_off, 0xFF, 3 * nw * sizeof(int), st));
+  }
+  FH_CHECK_HIP(hipMemsetAsync(d_kE, 0xFF, capE * sizeof(unsigned long long), st));
+  FH_CHECK_HIP(hipMemsetAsync(d_kT, 0xFF, capT * sizeof(unsigned long long), st));
+  FH_CHECK_HIP(hipMemsetAsync(d_kQ, 0xFF, capQ * sizeof(unsigned long long), st));
+  FH_CHECK_HIP(hipMemsetAsync(d_first, 0x7f, nident * sizeof(int), st));
+  const EmTab* dT = C->tab->d_tab;
+  if (nel_c) hipLaunchKernelGGL(k_em_widths, dim3(fh_div_up(nel_c, 256)), dim3(256), 0, st, dT, nel_c, C->d_geom, d_w, d_w + nw, d_w + 2 * nw);
+  for (int c = 0; c < 3; c++) FH_TRY(fh_device_exclusive_scan(st, d_w + c * nw, d_off + c * nw, nel_c, d_bsum));
+  EmOcc O{d_off, d_off + nw, d_off + 2 * nw, (int)W[0], (int)(W[0] + W[1]), nch};
+  const int E0 = C->nnode, T0 = E0 + (int)capE, Q0 = T0 + (int)capT, C0 = Q0 + (int)capQ;
+  EmHash hE{d_kE, (unsigned)(capE - 1), 64 - lE, E0}, hT{d_kT, (unsigned)(capT - 1), 64 - lT, T0}, hQ{d_kQ, (unsigned)(capQ - 1), 64 - lQ, Q0};
+  const unsigned gb = (unsigned)((nthr + 255) / 256);
+  if (nel_f) {
+    hipLaunchKernelGGL(k_em_children, dim3(gb), dim3(256), 0, st, dT, nel_f, nch, C->d_geom, C->d_ed, C->d_ff, F->d_geom, F->d_ed, F->d_ff);
+    hipLaunchKernelGGL(k_em_touch, dim3(gb), dim3(256), 0, st, dT, O, nel_f, F->d_geom, F->d_ed, hE, hT, hQ, C0, d_first, d_ident);
+    hipLaunchKernelGGL(k_em_flag, dim3(fh_div_up(nocc, 256)), dim3(256), 0, st, nocc, d_first, d_ident, d_flag);
+  }
+  FH_CHECK_HIP(hipGetLastError());
+  FH_TRY(fh_device_exclusive_scan(st, d_flag, d_flag, nocc, d_bsum));
+  // the only numbers that come back: the ends of the three classes (the last one sizes the coordinates)
+  int own[3] = {0, 0, 0};
+  FH_CHECK_HIP(hipMemcpyAsync(&own[0], d_flag + O.base1, sizeof(int), hipMemcpyDeviceToHost, st));
+  FH_CHECK_HIP(hipMemcpyAsync(&own[1], d_flag + O.base2, sizeof(int), hipMemcpyDeviceToHost, st));
+  FH_CHECK_HIP(hipMemcpyAsync(&own[2], d_flag + nocc, sizeof(int), hipMemcpyDeviceToHost, st));
+  FH_CHECK_HIP(hipStreamSynchronize(st));
+  for (int k = 0; k < 3; k++) F->own[k] = own[k];
+  F->nnode = own[2];
+  FH_CHECK_HIP(hipMalloc((void**)&F->d_x, std::max<size_t>((size_t)F->nnode * dim, 1) * sizeof(double)));
+  if (ctx->debug_poison) FH_CHECK_HIP(hipMemsetAsync(F->d_x, 0xFF, std::max<size_t>((size_t)F->nnode * dim, 1) * sizeof(double), st));
+  if (nel_f)
+    hipLaunchKernelGGL(k_em_number, dim3(gb), dim3(256), 0, st, dT, O, nel_f, dim, F->d_geom, d_first, d_ident, d_flag, C->d_ed, C->d_x, C->tab->d_EP, F->d_ed,
+                       F->d_x);
+  FH_CHECK_HIP(hipGetLastError());
+  FH_CHECK_HIP(hipStreamSynchronize(st));       // the scratch is freed on return
+  *out = F.release();
+  return 0;
+  FH_GUARD_END("fh_elem_mesh_refine")
+}
+
+extern "C" int fh_elem_mesh_info(fh_elem_mesh_t m, int* dim, int* nel, int* nnode, int own[3], int* level) {
+  FH_REQUIRE(m, "fh_elem_mesh_info: null mesh");
+  if (dim) *dim = m->dim;
+  if (nel) *nel = m->nel;
+  if (nnode) *nnode = m->nnode;
+  if (own)
+    for (int k = 0; k < 3; k++) own[k] = m->own[k];
+  if (level) *level = m->level;
+  return 0;
+}
+
+extern "C" int fh_elem_mesh_get(fh_elem_mesh_t m, int* elem_geom, int* elem_dof, double* coords, int* face_flag) {
+  FH_REQUIRE(m, "fh_elem_mesh_get: null mesh");
+  hipStream_t st = m->ctx->stream;
+  if (elem_geom && m->nel) FH_CHECK_HIP(hipMemcpyAsync(elem_geom, m->d_geom, (size_t)m->nel * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (elem_dof && m->nel) FH_CHECK_HIP(hipMemcpyAsync(elem_dof, m->d_ed, (size_t)m->nel * EM_W * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (coords && m->nnode) FH_CHECK_HIP(hipMemcpyAsync(coords, m->d_x, (size_t)m->nnode * m->dim * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (face_flag && m->nel) FH_CHECK_HIP(hipMemcpyAsync(face_flag, m->d_ff, (size_t)m->nel * EM_F * sizeof(int), hipMemcpyDeviceToHost, st));
+  FH_CHECK_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+extern "C" int fh_elem_mesh_destroy(fh_elem_mesh_t m) {
+  delete m;
+  return 0;
+}

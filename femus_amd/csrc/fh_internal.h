@@ -247,6 +247,9 @@ void fh_meshdev_free(fh_mesh_dev* d);
 int fh_meshdev_upload(fh_ctx_t ctx, int nel, int nnode, int nloc, int dim, int nf, const int* elem_dof, const double* coords, const int* face_flag,
                       const int* elem_level, fh_mesh_dev** out);
 int fh_meshdev_refine(fh_ctx_t ctx, const fh_refine_tables& tables, fh_mesh_dev* coarse, int level_c, const unsigned char* flags, fh_refine_result* out);
+// exclusive scan of n ints on the device (fh_meshdev.hip): out[n] = total, in and out may be the same array; out holds n + 1 ints, d_bsum n / FH_SCAN_BLOCK + 2
+constexpr int FH_SCAN_BLOCK = 2048;
+int fh_device_exclusive_scan(hipStream_t st, const int* d_in, int* d_out, int n, int* d_bsum);
 // the device copy of a mesh on this context (uploaded now if the mesh has none), its host arrays beside it
 int fh_mesh_device(fh_ctx_t ctx, fh_mesh_t m, fh_mesh_dev** dev);
 

@@ -100,8 +100,9 @@ __global__ __launch_bounds__(SC_T) void k_scan_add(int* __restrict__ out, int n,
     if (i < (size_t)n) out[i] += add;
   }
 }
-// out must hold n + 1 ints; d_bsum at least n / SC_B + 1
-static int device_exclusive_scan(hipStream_t st, const int* d_in, int* d_out, int n, int* d_bsum) {
+// out must hold n + 1 ints; d_bsum at least n / SC_B + 1 (declared in fh_internal.h: fh_elemmesh.hip scans with it too)
+static_assert(SC_B == FH_SCAN_BLOCK, "fh_internal.h names the block of the scan");
+int fh_device_exclusive_scan(hipStream_t st, const int* d_in, int* d_out, int n, int* d_bsum) {
   const int nb = std::max(1, (n + SC_B - 1) / SC_B);
   hipLaunchKernelGGL(k_scan_local, dim3(nb), dim3(SC_T), 0, st, d_in, d_out, n, d_bsum);
   hipLaunchKernelGGL(k_scan_bsums, dim3(1), dim3(SC_T), 0, st, d_bsum, nb, d_out + n);
@@ -308,7 +309,7 @@ int fh_meshdev_refine(fh_ctx_t ctx, const fh_refine_tables& H, fh_mesh_dev* C, i
   FH_CHECK_HIP(hipMalloc(&d_child, std::max<size_t>(nslot, 2) * sizeof(int)));
   FH_CHECK_HIP(hipMalloc(&d_refined, std::max<size_t>(nel_c, 8)));
   if (nel_c) hipLaunchKernelGGL(k_rf_mark, dim3(fh_div_up(nel_c, 256)), dim3(256), 0, st, nel_c, level_c, C->d_elem_level, d_flags, d_refined, d_cnt, nch);
-  FH_TRY(device_exclusive_scan(st, d_cnt, d_start, nel_c, d_bsum));
+  FH_TRY(fh_device_exclusive_scan(st, d_cnt, d_start, nel_c, d_bsum));
   int nel_f = 0;
   FH_CHECK_HIP(hipMemcpyAsync(&nel_f, d_start + nel_c, sizeof(int), hipMemcpyDeviceToHost, st));
   FH_CHECK_HIP(hipStreamSynchronize(st));
@@ -345,7 +346,7 @@ int fh_meshdev_refine(fh_ctx_t ctx, const fh_refine_tables& H, fh_mesh_dev* C, i
     hipLaunchKernelGGL(k_rf_touch, dim3(gb), dim3(256), 0, st, T, nel_f, d_parent, F->d_elem_dof, d_keys, (unsigned)(cap - 1), 64 - log2cap, E0, C0, d_first, d_ident);
     hipLaunchKernelGGL(k_rf_flag, dim3(gb), dim3(256), 0, st, T, nel_f, d_first, d_ident, d_flag);
   }
-  FH_TRY(device_exclusive_scan(st, d_flag, d_flag, (int)nocc, d_bsum));
+  FH_TRY(fh_device_exclusive_scan(st, d_flag, d_flag, (int)nocc, d_bsum));
   int own[3] = {0, 0, 0};
   FH_CHECK_HIP(hipMemcpyAsync(&own[0], d_flag + (size_t)nel_f * T.nv, sizeof(int), hipMemcpyDeviceToHost, st));
   FH_CHECK_HIP(hipMemcpyAsync(&own[1], d_flag + (size_t)nel_f * T.ne, sizeof(int), hipMemcpyDeviceToHost, st));

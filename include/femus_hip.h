@@ -260,6 +260,26 @@ int fh_mesh_child_elems(fh_mesh_t coarse, int* child /* [nel*nchild] */);
  * 03_solvers/LinearEquationSolverPetsc.cpp:53-90).  Returns the sorted list; *n in: capacity, out: count */
 int fh_mesh_dirichlet_dofs(fh_mesh_t mesh, int fe, int* n, int* dofs);
 
+/* ---- element meshes of any mix of shapes, resident on the device (fh_elemmesh.hip) ----
+ * The meshes fh_mesh_t does not hold: TRI7, TET15, WEDGE21 and files that mix them with HEX27 / QUAD9, as femus_amd/mixed_mesh.py reads or builds them.
+ *   elem_geom[nel]     shape code of every element: 0 hex, 1 quad, 3 triangle, 4 tetrahedron, 5 prism (2, the line, is refused)
+ *   elem_dof[nel*27]   biquadratic node ids, -1 beyond the shape's 27 / 9 / 7 / 15 / 21
+ *   coords[nnode*dim], face_flag[nel*6] (-1 beyond the shape's faces), own[3]: ends of the vertex, edge-node and remaining classes
+ * create checks its input on the host before anything is launched (dim 2 or 3, every shape of that dimension, ids in [0, nnode) inside the shape's width,
+ * -1 outside) and uploads once.  refine is one uniform refinement on the context's stream (MeshRefinement::RefineMesh for every shape + the first-touch
+ * numbering of Mesh.cpp:517-559): fine element nch * e + j is child j of e (nch = 8 / 4) and has its shape; the fine mesh is made resident, only the three
+ * class ends come back; the coarse mesh is unchanged.  Integers and coordinate bits are those of mixed_mesh.py: refine.  New nodes are found through three
+ * hash tables (edges: two vertex ids; quadrilateral faces: the smallest vertex id and the one diagonal to it; triangular faces: the slot of the edge of the
+ * two smallest vertices and the third vertex), exact for any 32-bit ids; a refinement whose first-touch order (27 entries per fine element at most) or
+ * node table does not fit 32-bit integers is refused.  get downloads what is asked for (any pointer may be NULL). */
+typedef struct fh_elem_mesh_s* fh_elem_mesh_t;
+int fh_elem_mesh_create(fh_ctx_t ctx, int dim, int nel, int nnode, const int* elem_geom, const int* elem_dof, const double* coords, const int* face_flag,
+                        const int own[3], fh_elem_mesh_t* mesh);
+int fh_elem_mesh_refine(fh_elem_mesh_t coarse, fh_elem_mesh_t* fine);
+int fh_elem_mesh_info(fh_elem_mesh_t mesh, int* dim, int* nel, int* nnode, int own[3], int* level);
+int fh_elem_mesh_get(fh_elem_mesh_t mesh, int* elem_geom /* [nel] */, int* elem_dof /* [nel*27] */, double* coords /* [nnode*dim] */, int* face_flag /* [nel*6] */);
+int fh_elem_mesh_destroy(fh_elem_mesh_t mesh);
+
 /* ---- sparsity (a11): LinearEquation::GetSparsityPatternSize (03_solvers/LinearEquation.cpp:407-548) ----
  * CSR pattern of the element-connectivity graph: two-call protocol (rowptr first, then col). */
 int fh_pattern_from_elements(int nel, int nloc, const int* elem_dof, int ndof, int* rowptr /* [ndof+1] */, int* col /* NULL on first call */);
