@@ -1,4 +1,5 @@
-// Batched Poisson assembly on gfx950 (K1-K4 of SURVEY 2.1; a4, a7, a12 of SURVEY 8).
+// Batched Poisson assembly on gfx950 (K1-K4 of SURVEY 2.1; a4, a7, a12 of SURVEY 8): fh_assembler_* and nothing else.  The public elem_type::Jacobian and the
+// face integrals are in fh_faces.hip, the one-dimensional callback in fh_line.hip, the generic (dim, nc, ng) path of simplex / prism / mixed meshes in fh_generic.hip.
 // Restates, as ONE device pass per element colour, the per-element callback of
 //   src/08_equations/assemble/00_poisson_eqn_with_all_dirichlet_bc_AD_or_nonAD_separate.hpp:106-228
 // with elem_type::Jacobian from src/02_reference_geom_elements/03_fe_evaluations_at_quadrature/ElemType.hpp:1183-1248
@@ -3515,24 +3516,15 @@ extern "C" int fh_assemble_poisson(fh_assembler_t as, fh_vec_t sol, int source_k
   return assemble_poisson_core(as, sol, source_kind, params, A, res);
 }
 
-int fh_expr_program(fh_expr_t e, int* ncode, int* nconst, int* code, double* consts);
-
 // source term from a run-time expression: f = scale * expr(x, y, z, t) evaluated at every Gauss point on the device
 // (001_Poisson/main.cpp:472 calls the ParsedFunction on the host once per Gauss point and test function)
 extern "C" int fh_assemble_poisson_expr(fh_assembler_t as, fh_vec_t sol, fh_expr_t source, double scale, fh_mat_t A, fh_vec_t res) {
   FH_REQUIRE(as && source, "fh_assemble_poisson_expr: null argument");
-  {
-    // the kernels hand the program a 4-entry point (x, y, z, t): a program compiled over more variables would read past it
-    int nv = 0;
-    FH_TRY(fh_expr_nvars(source, &nv));
-    FH_REQUIRE(nv <= 4, "fh_assemble_poisson_expr: the source expression has %d variables, at most 4 (x, y, z, t) are served", nv);
-  }
-  int nc = 0, nk = 0;
-  FH_TRY(fh_expr_program(source, &nc, &nk, nullptr, nullptr));
-  std::vector<int> code(nc);
-  std::vector<double> consts(std::max(nk, 1));
-  FH_TRY(fh_expr_program(source, &nc, &nk, code.data(), consts.data()));
-  consts.resize(nk);
+  // the kernels hand the program a 4-entry point (x, y, z, t): a program compiled over more variables would read past it
+  std::vector<int> code;
+  std::vector<double> consts;
+  FH_TRY(fh_expr_fetch(source, "fh_assemble_poisson_expr: the source expression", 4, code, consts));
+  const int nc = (int)code.size();
   if (code != as->h_prog || consts != as->h_prog_consts || !as->d_prog) {
     FH_CHECK_HIP(hipStreamSynchronize(as->ctx->stream));
     if (as->d_prog) hipFree(as->d_prog);
@@ -4383,917 +4375,4 @@ extern "C" int fh_assembler_galerkin(fh_assembler_t fas, fh_assembler_t cas, con
   fh_mat_values_written(Ac);
   return 0;
   FH_GUARD_END("fh_assembler_galerkin")
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// a4 in full: elem_type::Jacobian (ElemType.hpp:1183-1248 2-D, :1438-1537 3-D) for every (element, Gauss point) of a mesh, with the optional
-// Hessians `nablaphi` (:1509-1534, :1232-1244): one thread per (element, Gauss point), the reference's accumulation order and bracketing.
-// The Hessian formula is the reference's: JacI^T (reference Hessian) JacI, i.e. without the second derivatives of the map (exact on affine elements).
-// ------------------------------------------------------------------------------------------------------------------
-template <int DIM>
-__global__ __launch_bounds__(128) void k_fe_jacobian(int nel, int ng, int nc, int nloc, const int* __restrict__ ed, const double* __restrict__ coords,
-                                                     const double* __restrict__ w, const double* __restrict__ dphi, const double* __restrict__ d2phi,
-                                                     double* __restrict__ weight, double* __restrict__ gradphi, double* __restrict__ nablaphi) {
-  constexpr int NH = DIM == 2 ? 3 : 6;
-  const size_t t = (size_t)blockIdx.x * 128 + threadIdx.x;
-  if (t >= (size_t)nel * ng) return;
-  const int e = (int)(t / ng), g = (int)(t % ng);
-  const int* en = ed + (size_t)e * nloc;
-  const double* dp = dphi + (size_t)g * nc * DIM;
-  double J[DIM][DIM], I[DIM][DIM];
-  for (int a = 0; a < DIM; a++)
-    for (int b = 0; b < DIM; b++) J[a][b] = 0.0;
-  for (int n = 0; n < nc; n++) {
-    const double* x = coords + (size_t)en[n] * DIM;
-    for (int a = 0; a < DIM; a++)
-      for (int b = 0; b < DIM; b++) J[a][b] += dp[n * DIM + a] * x[b];
-  }
-  double det;
-  if (DIM == 2) {
-    det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-    I[0][0] = J[1][1] / det;
-    I[0][1] = -J[0][1] / det;
-    I[1][0] = -J[1][0] / det;
-    I[1][1] = J[0][0] / det;
-  } else {
-    det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) + J[0][1] * (J[1][2] * J[2][0] - J[1][0] * J[2][2]) + J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-    I[0][0] = (-J[1][2] * J[2][1] + J[1][1] * J[2][2]) / det;
-    I[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
-    I[0][2] = (-J[0][2] * J[1][1] + J[0][1] * J[1][2]) / det;
-    I[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) / det;
-    I[1][1] = (-J[0][2] * J[2][0] + J[0][0] * J[2][2]) / det;
-    I[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
-    I[2][0] = (-J[1][1] * J[2][0] + J[1][0] * J[2][1]) / det;
-    I[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
-    I[2][2] = (-J[0][1] * J[1][0] + J[0][0] * J[1][1]) / det;
-  }
-  if (weight) weight[t] = det * w[g];
-  for (int n = 0; n < nc; n++) {
-    if (gradphi)
-      for (int a = 0; a < DIM; a++) {
-        double sum = dp[n * DIM + 0] * I[a][0];
-        for (int b = 1; b < DIM; b++) sum += dp[n * DIM + b] * I[a][b];
-        gradphi[(t * nc + n) * DIM + a] = sum;
-      }
-    if (nablaphi) {
-      const double* h = d2phi + ((size_t)g * nc + n) * NH;
-      double H[DIM][DIM];      // reference Hessian, symmetric
-      if (DIM == 2) {
-        H[0][0] = h[0]; H[1][1] = h[1]; H[0][1] = H[1][0] = h[2];
-      } else {
-        H[0][0] = h[0]; H[1][1] = h[1]; H[2][2] = h[2];
-        H[0][1] = H[1][0] = h[3]; H[1][2] = H[2][1] = h[4]; H[0][2] = H[2][0] = h[5];
-      }
-      auto entry = [&](int a, int b) {
-        double out = 0.0;
-        for (int r = 0; r < DIM; r++) {
-          double row = H[r][0] * I[a][0];
-          for (int c2 = 1; c2 < DIM; c2++) row += H[r][c2] * I[a][c2];
-          out += row * I[b][r];
-        }
-        return out;
-      };
-      double* o = nablaphi + (t * nc + n) * NH;
-      if (DIM == 2) {
-        o[0] = entry(0, 0); o[1] = entry(1, 1); o[2] = entry(0, 1);
-      } else {
-        o[0] = entry(0, 0); o[1] = entry(1, 1); o[2] = entry(2, 2);
-        o[3] = entry(0, 1); o[4] = entry(1, 2); o[5] = entry(2, 0);
-      }
-    }
-  }
-}
-
-extern "C" int fh_fe_tables_d2(int geom, int fe, int order, double* d2phi);
-
-extern "C" int fh_fe_jacobian(fh_ctx_t ctx, int geom, int fe, int order, int nel, int nloc, const int* elem_dof, int nnode, const double* coords,
-                              double* weight, double* gradphi, double* nablaphi) {
-  FH_GUARD_BEGIN
-  FH_REQUIRE(ctx && (nel == 0 || (elem_dof && coords)), "fh_fe_jacobian: null argument");
-  FH_REQUIRE(geom == 0 || geom == 1, "fh_fe_jacobian: geom must be 0 (hex) or 1 (quad)");
-  FH_REQUIRE(fe == 0 || fe == 1 || fe == 2, "fh_fe_jacobian: fe must be 0 (linear), 1 (serendipity) or 2 (biquadratic)");
-  FH_REQUIRE(nloc == fhfe::nloc_of(geom), "fh_fe_jacobian: nloc %d does not match the geometry (%d)", nloc, fhfe::nloc_of(geom));
-  if (nel == 0) return 0;
-  const int dim = fhfe::dim_of(geom), nc = fhfe::ndofs_of(geom, fe), nh = dim == 2 ? 3 : 6;
-  std::vector<double> w, phi, dphi;
-  FH_REQUIRE(fhfe::shape_tables(geom, fe, order, w, phi, dphi) == 0, "fh_fe_jacobian: unsupported Gauss rule %d", order);
-  const int ng = (int)w.size();
-  for (size_t k = 0; k < (size_t)nel * nloc; k++) FH_REQUIRE(elem_dof[k] >= 0 && elem_dof[k] < nnode, "fh_fe_jacobian: node id %d out of range", elem_dof[k]);
-  std::vector<double> d2((size_t)ng * nc * nh, 0.0);
-  if (nablaphi) {
-    std::vector<double> tab((size_t)nh * ng * nc);
-    FH_TRY(fh_fe_tables_d2(geom, fe, order, tab.data()));
-    for (int k = 0; k < nh; k++)
-      for (int g = 0; g < ng; g++)
-        for (int n = 0; n < nc; n++) d2[((size_t)g * nc + n) * nh + k] = tab[((size_t)k * ng + g) * nc + n];
-  }
-  struct Bufs {
-    std::vector<void*> p;
-    ~Bufs() { for (void* q : p) if (q) hipFree(q); }
-  } B;
-  auto dev = [&](void** d, const void* h, size_t bytes) -> int {
-    FH_CHECK_HIP(hipMalloc(d, bytes ? bytes : 8));
-    B.p.push_back(*d);
-    if (h && bytes) FH_CHECK_HIP(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return 0;
-  };
-  const size_t npt = (size_t)nel * ng;
-  int* d_ed;
-  double *d_xy, *d_w, *d_dphi, *d_d2, *d_wt = nullptr, *d_g = nullptr, *d_n = nullptr;
-  FH_TRY(dev((void**)&d_ed, elem_dof, (size_t)nel * nloc * sizeof(int)));
-  FH_TRY(dev((void**)&d_xy, coords, (size_t)nnode * dim * sizeof(double)));
-  FH_TRY(dev((void**)&d_w, w.data(), w.size() * sizeof(double)));
-  FH_TRY(dev((void**)&d_dphi, dphi.data(), dphi.size() * sizeof(double)));
-  FH_TRY(dev((void**)&d_d2, d2.data(), d2.size() * sizeof(double)));
-  if (weight) FH_TRY(dev((void**)&d_wt, nullptr, npt * sizeof(double)));
-  if (gradphi) FH_TRY(dev((void**)&d_g, nullptr, npt * nc * dim * sizeof(double)));
-  if (nablaphi) FH_TRY(dev((void**)&d_n, nullptr, npt * nc * nh * sizeof(double)));
-  const dim3 grid((unsigned)((npt + 127) / 128)), block(128);
-  if (dim == 3) hipLaunchKernelGGL(k_fe_jacobian<3>, grid, block, 0, ctx->stream, nel, ng, nc, nloc, d_ed, d_xy, d_w, d_dphi, d_d2, d_wt, d_g, d_n);
-  else hipLaunchKernelGGL(k_fe_jacobian<2>, grid, block, 0, ctx->stream, nel, ng, nc, nloc, d_ed, d_xy, d_w, d_dphi, d_d2, d_wt, d_g, d_n);
-  FH_CHECK_HIP(hipGetLastError());
-  if (weight) FH_CHECK_HIP(hipMemcpyAsync(weight, d_wt, npt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (gradphi) FH_CHECK_HIP(hipMemcpyAsync(gradphi, d_g, npt * nc * dim * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (nablaphi) FH_CHECK_HIP(hipMemcpyAsync(nablaphi, d_n, npt * nc * nh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  FH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  return 0;
-  FH_GUARD_END("fh_fe_jacobian")
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Neumann boundary faces (a5: elem_type::JacobianSur).  One thread per boundary node: it owns the node's (face, local i)
-// pairs (ascending face order) and integrates phi_i * tau over each face with the face element's quadrature.
-// ------------------------------------------------------------------------------------------------------------------
-// NORMAL: the vector form  res[off[k] + node] += scale * int_face phi_i tau n_k ds  for the DIM components (open-boundary pressure term of the
-// Navier-Stokes residual, 03_navier_stokes.hpp:185-290, normal = the one JacobianSur returns at each face Gauss point)
-template <int DIM, bool NORMAL>
-__global__ __launch_bounds__(128) void k_neumann(const int* __restrict__ node_ptr, const int* __restrict__ node_id, const int* __restrict__ pairs,
-                                                 int nbn, const int* __restrict__ face_nodes, int nfn, const double* __restrict__ tau,
-                                                 const double* __restrict__ coords, const double* __restrict__ w, const double* __restrict__ phi,
-                                                 const double* __restrict__ dphi, int ng, double* __restrict__ res,
-                                                 const int* __restrict__ face_expr, const int* __restrict__ prog, const int* __restrict__ prog_ptr,
-                                                 const double* __restrict__ pconst, const int* __restrict__ const_ptr, int off0, int off1, int off2, double scale) {
-  const int t = blockIdx.x * 128 + threadIdx.x;
-  if (t >= nbn) return;
-  double total = 0.0, totn[3] = {0.0, 0.0, 0.0};
-  for (int p = node_ptr[t]; p < node_ptr[t + 1]; p++) {
-    const int f = pairs[p] >> 4, i = pairs[p] & 15;
-    const int* fn = face_nodes + (size_t)f * nfn;
-    double acc = 0.0, accn[3] = {0.0, 0.0, 0.0};
-    for (int g = 0; g < ng; g++) {
-      double weight, nrm[3] = {0.0, 0.0, 0.0};
-      if (DIM == 3) {   // quad face in 3-D: tangents, normal = t1 x t2, det = |normal|  (ElemType.hpp:1330-1380)
-        double J[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-        for (int n = 0; n < nfn; n++) {
-          const double dx = dphi[((size_t)g * nfn + n) * 2 + 0], dy = dphi[((size_t)g * nfn + n) * 2 + 1];
-          const double* x = coords + (size_t)fn[n] * 3;
-          for (int d = 0; d < 3; d++) {
-            J[d][0] += dx * x[d];
-            J[d][1] += dy * x[d];
-          }
-        }
-        const double nx = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-        const double ny = J[0][1] * J[2][0] - J[2][1] * J[0][0];
-        const double nz = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-        const double inv = 1.0 / sqrt(nx * nx + ny * ny + nz * nz);
-        const double n0 = nx * inv, n1 = ny * inv, n2 = nz * inv;
-        const double det = J[0][0] * (J[1][1] * n2 - n1 * J[2][1]) + J[0][1] * (n1 * J[2][0] - J[1][0] * n2) + n0 * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-        weight = det * w[g];
-        nrm[0] = n0; nrm[1] = n1; nrm[2] = n2;
-      } else {          // edge in 2-D (ElemType.hpp:1089-1138)
-        double j0 = 0.0, j1 = 0.0;
-        for (int n = 0; n < nfn; n++) {
-          const double dx = dphi[(size_t)g * nfn + n];
-          const double* x = coords + (size_t)fn[n] * 2;
-          j0 += dx * x[0];
-          j1 += dx * x[1];
-        }
-        const double modn = sqrt(j0 * j0 + j1 * j1);
-        const double n0 = j1 / modn, n1 = -j0 / modn;
-        const double det = j0 * (-n1) - (-n0) * j1;
-        weight = det * w[g];
-        nrm[0] = n0; nrm[1] = n1;
-      }
-      double tv;
-      if (face_expr) {       // the flux is a parsed function of the Gauss point: (*bdcfunc)(&xyzt[0]), 001_Poisson/main.cpp:524-534
-        double xg[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int n = 0; n < nfn; n++) {
-          const double ph = phi[(size_t)g * nfn + n];
-          const double* x = coords + (size_t)fn[n] * DIM;
-          for (int d = 0; d < DIM; d++) xg[d] += x[d] * ph;
-        }
-        const int ex = face_expr[f];
-        tv = fh_expr_device_eval(prog + prog_ptr[ex], prog_ptr[ex + 1] - prog_ptr[ex], pconst + const_ptr[ex], xg);
-      } else {
-        tv = tau[f];
-      }
-      if (NORMAL) {
-#pragma unroll
-        for (int k = 0; k < DIM; k++) accn[k] += phi[(size_t)g * nfn + i] * tv * nrm[k] * weight;
-      } else {
-        acc += phi[(size_t)g * nfn + i] * tv * weight;
-      }
-    }
-    total += acc;
-#pragma unroll
-    for (int k = 0; k < DIM; k++) totn[k] += accn[k];
-  }
-  if (NORMAL) {
-    const int off[3] = {off0, off1, off2};
-#pragma unroll
-    for (int k = 0; k < DIM; k++) res[off[k] + node_id[t]] += scale * totn[k];
-  } else {
-    res[node_id[t]] += total;
-  }
-}
-
-// tables of the face element of `geom` (quad: the 2-D tables; line: 1-D Lagrange at the 1-D Gauss points): weights, phi[g][n], dphi[g][n][dim-1]
-static int face_element_tables(int geom, int fe, int order, int* nfn_out, std::vector<double>& w, std::vector<double>& phi, std::vector<double>& dphi) {
-  // geom >= 100: the FACE element itself is named (100 + its geometry: 101 quadrilateral, 103 triangle, 102 line) -- prisms have faces of two kinds
-  const int fgeom = geom >= 100 ? geom - 100 : (geom == fhfe::GEOM_HEX) ? fhfe::GEOM_QUAD : (geom == fhfe::GEOM_TET) ? fhfe::GEOM_TRI : fhfe::GEOM_LINE;
-  int tmp[9];
-  const int nfn = geom >= 100 ? fhfe::ndofs_of(fgeom, fe) : fhfe::face_nodes(geom, fe, 0, tmp);
-  *nfn_out = nfn;
-  if (fgeom == fhfe::GEOM_TRI) {        // the faces of a tetrahedron: TRI3 / TRI6 with the triangle's rule of the same order
-    FH_REQUIRE(fhfe::shape_tables(fhfe::GEOM_TRI, fe, order, w, phi, dphi) == 0, "fh_assemble_neumann_faces: unsupported Gauss rule");
-  } else if (fgeom == fhfe::GEOM_QUAD) {
-    FH_REQUIRE(fhfe::shape_tables(fhfe::GEOM_QUAD, fe, order, w, phi, dphi) == 0, "fh_assemble_neumann_faces: unsupported Gauss rule");
-  } else {
-    const int ng1 = order + 1;
-    w.resize(ng1);
-    std::vector<double> x1(ng1);
-    FH_REQUIRE(fhfe::gauss_table(fhfe::GEOM_LINE, order, w.data(), x1.data()) == 0, "fh_assemble_neumann_faces: unsupported Gauss rule");
-    phi.resize((size_t)ng1 * nfn);
-    dphi.resize((size_t)ng1 * nfn);
-    for (int g = 0; g < ng1; g++) {
-      const double x = x1[g];
-      if (fe == 0) {   // LineLinear: nodes -1, +1 (Edge.hpp:72-78)
-        phi[g * 2 + 0] = 0.5 * (1. - x);  phi[g * 2 + 1] = 0.5 * (1. + x);
-        dphi[g * 2 + 0] = -0.5;           dphi[g * 2 + 1] = 0.5;
-      } else {         // LineBiquadratic: nodes -1, +1, 0 (Edge.hpp:94-100)
-        phi[g * 3 + 0] = 0.5 * x * (x - 1.);  phi[g * 3 + 1] = 0.5 * x * (1. + x);  phi[g * 3 + 2] = (1. - x) * (1. + x);
-        dphi[g * 3 + 0] = x - 0.5;            dphi[g * 3 + 1] = x + 0.5;            dphi[g * 3 + 2] = -2. * x;
-      }
-    }
-  }
-  return 0;
-}
-
-// unit normals of boundary faces at one face Gauss point, as elem_type::JacobianSur returns them (host; the applications read them to decide what a
-// face contributes, e.g. 03_navier_stokes.hpp:264-275 picks the normal velocity component from the normal at Gauss point 0)
-extern "C" int fh_fe_face_normals(int geom, int fe, int order, int gauss_point, int nfaces, const int* face_nodes, int nnode, const double* coords,
-                                  double* normals /* [nfaces*dim] */) {
-  FH_GUARD_BEGIN
-  FH_REQUIRE(geom == 0 || geom == 1, "fh_fe_face_normals: geom must be 0 (hex) or 1 (quad)");
-  FH_REQUIRE(fe == 0 || fe == 1 || fe == 2, "fh_fe_face_normals: fe must be 0, 1 or 2");
-  FH_REQUIRE(nfaces == 0 || (face_nodes && coords && normals), "fh_fe_face_normals: null argument");
-  const int dim = fhfe::dim_of(geom);
-  int nfn = 0;
-  std::vector<double> w, phi, dphi;
-  FH_TRY(face_element_tables(geom, fe, order, &nfn, w, phi, dphi));
-  const int g = gauss_point;
-  FH_REQUIRE(g >= 0 && g < (int)w.size(), "fh_fe_face_normals: Gauss point %d of %d", g, (int)w.size());
-  for (int f = 0; f < nfaces; f++) {
-    const int* fn = face_nodes + (size_t)f * nfn;
-    for (int n = 0; n < nfn; n++) FH_REQUIRE(fn[n] >= 0 && fn[n] < nnode, "fh_fe_face_normals: node id out of range");
-    if (dim == 3) {
-      double J[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-      for (int n = 0; n < nfn; n++) {
-        const double dx = dphi[((size_t)g * nfn + n) * 2 + 0], dy = dphi[((size_t)g * nfn + n) * 2 + 1];
-        const double* x = coords + (size_t)fn[n] * 3;
-        for (int d = 0; d < 3; d++) {
-          J[d][0] += dx * x[d];
-          J[d][1] += dy * x[d];
-        }
-      }
-      const double nx = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-      const double ny = J[0][1] * J[2][0] - J[2][1] * J[0][0];
-      const double nz = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-      const double inv = 1.0 / sqrt(nx * nx + ny * ny + nz * nz);
-      normals[(size_t)f * 3 + 0] = nx * inv;
-      normals[(size_t)f * 3 + 1] = ny * inv;
-      normals[(size_t)f * 3 + 2] = nz * inv;
-    } else {
-      double j0 = 0.0, j1 = 0.0;
-      for (int n = 0; n < nfn; n++) {
-        const double dx = dphi[(size_t)g * nfn + n];
-        const double* x = coords + (size_t)fn[n] * 2;
-        j0 += dx * x[0];
-        j1 += dx * x[1];
-      }
-      const double modn = sqrt(j0 * j0 + j1 * j1);
-      normals[(size_t)f * 2 + 0] = j1 / modn;
-      normals[(size_t)f * 2 + 1] = -j0 / modn;
-    }
-  }
-  return 0;
-  FH_GUARD_END("fh_fe_face_normals")
-}
-
-static int neumann_faces(fh_ctx_t ctx, int geom, int fe, int order, int nfaces, const int* face_nodes, const double* tau, const int* face_expr, int nexpr,
-                         const fh_expr_t* exprs, int nnode, const double* coords, fh_vec_t res, const int* comp_offset = nullptr, double scale = 1.0) {
-  FH_REQUIRE(ctx && res && (nfaces == 0 || (face_nodes && (tau || face_expr) && coords)), "fh_assemble_neumann_faces: null argument");
-  FH_REQUIRE(geom == 0 || geom == 1 || geom == 3 || geom == 4 || geom == 101 || geom == 102 || geom == 103,
-             "fh_assemble_neumann_faces: geom must be 0 (hex), 1 (quad), 3 (triangle), 4 (tetrahedron), or 100 + the face element's own geometry (101 / 102 / 103)");
-  FH_REQUIRE(fe == 0 || fe == 1 || fe == 2, "fh_assemble_neumann_faces: fe must be 0, 1 or 2");
-  if (nfaces == 0) return 0;
-  const int dim = geom >= 100 ? fhfe::dim_of(geom - 100) + 1 : fhfe::dim_of(geom);
-  int nfn = 0;
-  std::vector<double> w, phi, dphi;
-  FH_TRY(face_element_tables(geom, fe, order, &nfn, w, phi, dphi));
-  const int ng = (int)w.size();
-  // node -> (face, i) pairs, ascending face order
-  std::vector<int> cnt(nnode + 1, 0);
-  for (size_t k = 0; k < (size_t)nfaces * nfn; k++) {
-    FH_REQUIRE(face_nodes[k] >= 0 && face_nodes[k] < nnode, "fh_assemble_neumann_faces: node id out of range");
-    cnt[face_nodes[k] + 1]++;
-  }
-  std::vector<int> node_id, node_ptr(1, 0), pairs;
-  for (int n = 0; n < nnode; n++) cnt[n + 1] += cnt[n];
-  std::vector<int> cur(cnt.begin(), cnt.end() - 1), flat(cnt[nnode]);
-  FH_REQUIRE(nfaces < (1 << 27), "fh_assemble_neumann_faces: too many faces");
-  for (int f = 0; f < nfaces; f++)
-    for (int i = 0; i < nfn; i++) flat[cur[face_nodes[(size_t)f * nfn + i]]++] = (f << 4) | i;
-  for (int n = 0; n < nnode; n++)
-    if (cnt[n + 1] > cnt[n]) {
-      node_id.push_back(n);
-      pairs.insert(pairs.end(), flat.begin() + cnt[n], flat.begin() + cnt[n + 1]);
-      node_ptr.push_back((int)pairs.size());
-    }
-  const int nbn = (int)node_id.size();
-  FH_REQUIRE(res->n_local + res->nghost > node_id.back() + (comp_offset ? *std::max_element(comp_offset, comp_offset + dim) : 0),
-             "fh_assemble_neumann_faces: vector too short");
-  // parsed fluxes: the programs of all expressions back to back
-  std::vector<int> h_prog, h_prog_ptr(1, 0), h_const_ptr(1, 0);
-  std::vector<double> h_const;
-  if (face_expr) {
-    FH_REQUIRE(nexpr >= 1 && exprs, "fh_assemble_neumann_faces_expr: no expressions");
-    for (int f = 0; f < nfaces; f++) FH_REQUIRE(face_expr[f] >= 0 && face_expr[f] < nexpr, "fh_assemble_neumann_faces_expr: face %d names expression %d of %d", f, face_expr[f], nexpr);
-    for (int k = 0; k < nexpr; k++) {
-      FH_REQUIRE(exprs[k], "fh_assemble_neumann_faces_expr: null expression");
-      int nv = 0, nc = 0, nk = 0;
-      FH_TRY(fh_expr_nvars(exprs[k], &nv));
-      FH_REQUIRE(nv <= 4, "fh_assemble_neumann_faces_expr: expression %d has %d variables, at most 4 (x, y, z, t) are served", k, nv);
-      FH_TRY(fh_expr_program(exprs[k], &nc, &nk, nullptr, nullptr));
-      std::vector<int> code(nc);
-      std::vector<double> consts(nk);
-      FH_TRY(fh_expr_program(exprs[k], &nc, &nk, code.data(), consts.data()));
-      h_prog.insert(h_prog.end(), code.begin(), code.end());
-      h_const.insert(h_const.end(), consts.begin(), consts.end());
-      h_prog_ptr.push_back((int)h_prog.size());
-      h_const_ptr.push_back((int)h_const.size());
-    }
-  }
-  void* dv[13] = {nullptr};
-  auto up = [&](int slot, const void* h, size_t bytes) -> int {
-    FH_CHECK_HIP(hipMalloc(&dv[slot], bytes ? bytes : 8));
-    FH_CHECK_HIP(hipMemcpyAsync(dv[slot], h, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return 0;
-  };
-  FH_TRY(up(0, node_ptr.data(), node_ptr.size() * sizeof(int)));
-  FH_TRY(up(1, node_id.data(), node_id.size() * sizeof(int)));
-  FH_TRY(up(2, pairs.data(), pairs.size() * sizeof(int)));
-  FH_TRY(up(3, face_nodes, (size_t)nfaces * nfn * sizeof(int)));
-  if (tau) FH_TRY(up(4, tau, (size_t)nfaces * sizeof(double)));
-  if (face_expr) {
-    FH_TRY(up(8, face_expr, (size_t)nfaces * sizeof(int)));
-    FH_TRY(up(9, h_prog.data(), h_prog.size() * sizeof(int)));
-    FH_TRY(up(10, h_prog_ptr.data(), h_prog_ptr.size() * sizeof(int)));
-    FH_TRY(up(11, h_const.data(), h_const.size() * sizeof(double)));
-    FH_TRY(up(12, h_const_ptr.data(), h_const_ptr.size() * sizeof(int)));
-  }
-  FH_TRY(up(5, coords, (size_t)nnode * dim * sizeof(double)));
-  FH_TRY(up(6, w.data(), w.size() * sizeof(double)));
-  std::vector<double> tab(phi);
-  tab.insert(tab.end(), dphi.begin(), dphi.end());
-  FH_TRY(up(7, tab.data(), tab.size() * sizeof(double)));
-  const double* d_phi = (const double*)dv[7];
-  const double* d_dphi = d_phi + phi.size();
-  const dim3 grid(fh_div_up(nbn, 128)), block(128);
-  const int o0 = comp_offset ? comp_offset[0] : 0, o1 = comp_offset ? comp_offset[1] : 0, o2 = (comp_offset && dim == 3) ? comp_offset[2] : 0;
-#define FH_NEUMANN_LAUNCH(D, N)                                                                                                                   \
-  hipLaunchKernelGGL((k_neumann<D, N>), grid, block, 0, ctx->stream, (const int*)dv[0], (const int*)dv[1], (const int*)dv[2], nbn, (const int*)dv[3], \
-                     nfn, (const double*)dv[4], (const double*)dv[5], (const double*)dv[6], d_phi, d_dphi, ng, res->d, (const int*)dv[8],          \
-                     (const int*)dv[9], (const int*)dv[10], (const double*)dv[11], (const int*)dv[12], o0, o1, o2, scale)
-  if (dim == 3 && comp_offset) FH_NEUMANN_LAUNCH(3, true);
-  else if (dim == 3) FH_NEUMANN_LAUNCH(3, false);
-  else if (comp_offset) FH_NEUMANN_LAUNCH(2, true);
-  else FH_NEUMANN_LAUNCH(2, false);
-#undef FH_NEUMANN_LAUNCH
-  FH_CHECK_HIP(hipGetLastError());
-  FH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  for (void* q : dv)
-    if (q) hipFree(q);
-  return 0;
-}
-
-extern "C" int fh_assemble_neumann_faces(fh_ctx_t ctx, int geom, int fe, int order, int nfaces, const int* face_nodes, const double* tau, int nnode,
-                                         const double* coords, fh_vec_t res) {
-  FH_REQUIRE(nfaces == 0 || tau, "fh_assemble_neumann_faces: null argument");
-  return neumann_faces(ctx, geom, fe, order, nfaces, face_nodes, tau, nullptr, 0, nullptr, nnode, coords, res);
-}
-
-// Open-boundary pressure term of the steady Navier-Stokes residual (03_navier_stokes.hpp:185-290): on the listed boundary faces (those whose
-// normal velocity component is not Dirichlet -- the application's bdc callback decides, :236-262) aResV[k][node_i] += phi_i tau n_k weight with the
-// prescribed pressure tau (a number per face, or expression face_expr[f] at the face Gauss point) and the JacobianSur normal; the residual
-// vector takes scale * that (scale = -1: RES = -aRes, :425).  comp_offset[k]: where component k of the velocity starts in res.
-extern "C" int fh_assemble_pressure_faces(fh_ctx_t ctx, int geom, int order, int nfaces, const int* face_nodes, const double* tau, const int* face_expr,
-                                          int nexpr, const fh_expr_t* exprs, int nnode, const double* coords, const int* comp_offset, double scale,
-                                          fh_vec_t res) {
-  FH_REQUIRE(comp_offset, "fh_assemble_pressure_faces: null component offsets");
-  FH_REQUIRE(nfaces == 0 || tau || face_expr, "fh_assemble_pressure_faces: neither a pressure per face nor expressions");
-  return neumann_faces(ctx, geom, 2, order, nfaces, face_nodes, face_expr ? nullptr : tau, face_expr, nexpr, exprs, nnode, coords, res, comp_offset, scale);
-}
-
-// the flux as a parsed function of the Gauss point (x, y, z, t = 0), as the parsed-boundary-condition branch of the 001_Poisson callback
-// evaluates it (`(*bdcfunc)(&xyzt[0])` inside the Gauss loop, applications/001_Poisson/main.cpp:495-553): face_expr[f] names one of `nexpr` expressions
-extern "C" int fh_assemble_neumann_faces_expr(fh_ctx_t ctx, int geom, int fe, int order, int nfaces, const int* face_nodes, const int* face_expr, int nexpr,
-                                              const fh_expr_t* exprs, int nnode, const double* coords, fh_vec_t res) {
-  FH_REQUIRE(nfaces == 0 || face_expr, "fh_assemble_neumann_faces_expr: null argument");
-  return neumann_faces(ctx, geom, fe, order, nfaces, face_nodes, nullptr, face_expr, nexpr, exprs, nnode, coords, res);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// The application's callback on a ONE-DIMENSIONAL mesh (applications/001_Poisson/main.cpp:355-480 with dim == 1; its shipped input/input1D.json, an EDGE3
-// box): there the callback is not a Poisson problem -- main.cpp:392-395 sets V = 1, nu = 0.01 -- but advection-diffusion with the streamline-upwind terms the
-// same loop carries in every dimension (tau = 0 where V = 0, which is why the 2-D / 3-D kernels above never see them):
-//   tau   = barNu / V^2,  barNu = (coth(Pe) - 1 / Pe) V h / 2,  Pe = V h / (2 nu),  h = x[1] - x[0]  (directions_of_reference_element, Elem.hpp:149-167)
-//   F_i  += (f phi_i - nu phi_i' u' - V u' phi_i + (f - (-nu u'' + V u')) s_i) w,   s_i = (V phi_i' + nu phi_i'') tau
-//   B_ij += (nu (phi_i' phi_j' - phi_j'' s_i) + V phi_j' (phi_i + s_i)) w
-// with elem_type_1D::Jacobian (ElemType.hpp:994-1035): Jac = sum dphi_n x_n, w = Jac w_g, phi' = dphi / Jac, phi'' = d2phi / Jac^2.
-// One thread per ROW: it walks the elements of its node in ascending order, forms its row of each element matrix over the Gauss points and adds it -- the
-// grouping of the reference's add_matrix_blocked / add_vector_blocked, no atomics.  The problem sizes of a one-dimensional mesh make everything else moot.
-// ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_line_advdiff(int ndof, int nc, int ng, const int* __restrict__ adj_ptr, const int* __restrict__ adj,
-                                                     const int* __restrict__ elem_dof, const double* __restrict__ coords, const double* __restrict__ sol,
-                                                     const double* __restrict__ w, const double* __restrict__ phi, const double* __restrict__ dphi,
-                                                     const double* __restrict__ d2phi, double nu, double V, const int* __restrict__ prog, int nprog,
-                                                     const double* __restrict__ pconst, const int* __restrict__ rowptr, const int* __restrict__ col,
-                                                     double* __restrict__ val, double* __restrict__ res) {
-  const int r = blockIdx.x * 64 + threadIdx.x;
-  if (r >= ndof) return;
-  const int rs = rowptr[r], re = rowptr[r + 1];
-  for (int k = rs; k < re; k++) val[k] = 0.0;
-  double racc = 0.0;
-  for (int a = adj_ptr[r]; a < adj_ptr[r + 1]; a++) {
-    const int e = adj[a] >> 2, i = adj[a] & 3;
-    double x[3], u[3];
-    int dof[3];
-    for (int n = 0; n < nc; n++) {
-      dof[n] = elem_dof[e * 3 + n];
-      x[n] = coords[dof[n]];
-      u[n] = sol ? sol[dof[n]] : 0.0;
-    }
-    // stabilisation parameter of the element (main.cpp:397-428)
-    const double VxiHxi = (x[1] - x[0]) * V;
-    const double PeXi = VxiHxi / (2. * nu);
-    const double barXi = (fabs(PeXi) < 1.0e-10) ? 0. : 1. / tanh(PeXi) - 1. / PeXi;
-    const double barNu = barXi * VxiHxi / 2.;
-    const double vL2Norm2 = V * V;
-    const double supgTau = (vL2Norm2 > 1.0e-15) ? barNu / vL2Norm2 : 0.;
-    double F = 0.0, B[3] = {0.0, 0.0, 0.0};
-    for (int g = 0; g < ng; g++) {
-      double Jac = 0.0;
-      for (int n = 0; n < nc; n++) Jac += dphi[g * nc + n] * x[n];
-      const double weight = Jac * w[g], JacI = 1 / Jac;
-      double ph[3], gr[3], nb[3], gradSol = 0.0, nablaSol = 0.0, xg[4] = {0.0, 0.0, 0.0, 0.0};
-      for (int n = 0; n < nc; n++) {
-        ph[n] = phi[g * nc + n];
-        gr[n] = dphi[g * nc + n] * JacI;
-        nb[n] = d2phi[g * nc + n] * JacI * JacI;
-        xg[0] += x[n] * ph[n];
-        gradSol += gr[n] * u[n];
-        nablaSol += nb[n] * u[n];
-      }
-      const double lapRhs = nu * gr[i] * gradSol;
-      const double advRhs = V * gradSol * ph[i];
-      const double resRhs = -nu * nablaSol + V * gradSol;
-      const double supgPhi = (V * gr[i] + nu * nb[i]) * supgTau;
-      const double src = prog ? fh_expr_device_eval(prog, nprog, pconst, xg) : 0.0;
-      F += (src * ph[i] - lapRhs - advRhs + (src - resRhs) * supgPhi) * weight;
-      for (int j = 0; j < nc; j++) {
-        const double lap = nu * (gr[i] * gr[j] - nb[j] * supgPhi) * weight;
-        const double adv = V * gr[j] * (ph[i] + supgPhi) * weight;
-        B[j] += lap + adv;
-      }
-    }
-    racc += F;
-    for (int j = 0; j < nc; j++)
-      for (int k = rs; k < re; k++)
-        if (col[k] == dof[j]) {
-          val[k] += B[j];
-          break;
-        }
-  }
-  res[r] = racc;
-}
-
-extern "C" int fh_assemble_advdiff_line(fh_ctx_t ctx, int fe, int order, int nel, const int* elem_dof, int nnode, const double* coords, fh_vec_t sol, double nu,
-                                        double velocity, fh_expr_t source, fh_mat_t KK, fh_vec_t RES) {
-  FH_GUARD_BEGIN
-  FH_REQUIRE(ctx && elem_dof && coords && KK && RES && nel >= 1 && nnode >= 2, "fh_assemble_advdiff_line: null or empty argument");
-  FH_REQUIRE(fe == fhfe::FE_LINEAR || fe == fhfe::FE_SERENDIPITY || fe == fhfe::FE_BIQUADRATIC, "fh_assemble_advdiff_line: fe must be 0, 1 or 2");
-  FH_REQUIRE(nu > 0.0, "fh_assemble_advdiff_line: the diffusivity must be positive");
-  const int nc = fhfe::ndofs_of(fhfe::GEOM_LINE, fe), ndof = KK->m;
-  FH_REQUIRE(KK->n == ndof && RES->n_local >= ndof && (!sol || sol->n_local >= ndof), "fh_assemble_advdiff_line: size mismatch");
-  std::vector<int> cnt(ndof + 1, 0);
-  for (int e = 0; e < nel; e++)
-    for (int n = 0; n < nc; n++) {
-      const int d = elem_dof[e * 3 + n];
-      FH_REQUIRE(d >= 0 && d < ndof && d < nnode, "fh_assemble_advdiff_line: element %d, node %d: dof %d outside the system (the vertices are numbered first)", e, n, d);
-      cnt[d + 1]++;
-    }
-  for (int d = 0; d < ndof; d++) cnt[d + 1] += cnt[d];
-  std::vector<int> adj(cnt[ndof]), fill(cnt.begin(), cnt.end() - 1);
-  for (int e = 0; e < nel; e++)                         // ascending element order per dof
-    for (int n = 0; n < nc; n++) adj[fill[elem_dof[e * 3 + n]]++] = e * 4 + n;
-  std::vector<double> w, phi, dphi;
-  FH_REQUIRE(fhfe::shape_tables(fhfe::GEOM_LINE, fe, order, w, phi, dphi) == 0, "fh_assemble_advdiff_line: unsupported Gauss rule");
-  const int ng = (int)w.size();
-  std::vector<double> d2((size_t)ng * nc), x1(ng), t(nc);
-  fhfe::gauss_table(fhfe::GEOM_LINE, order, nullptr, x1.data());
-  for (int g = 0; g < ng; g++) {
-    const double pt[3] = {x1[g], 0.0, 0.0};
-    fhfe::eval_basis_d2(fhfe::GEOM_LINE, fe, pt, t.data());
-    for (int n = 0; n < nc; n++) d2[(size_t)g * nc + n] = t[n];
-  }
-  std::vector<int> code;
-  std::vector<double> consts;
-  if (source) {
-    int nv = 0, ncode = 0, nk = 0;
-    FH_TRY(fh_expr_nvars(source, &nv));
-    FH_REQUIRE(nv <= 4, "fh_assemble_advdiff_line: the source expression has %d variables, at most 4 (x, y, z, t) are served", nv);
-    FH_TRY(fh_expr_program(source, &ncode, &nk, nullptr, nullptr));
-    code.resize(ncode);
-    consts.resize(std::max(nk, 1));
-    FH_TRY(fh_expr_program(source, &ncode, &nk, code.data(), consts.data()));
-  }
-  hipStream_t st = ctx->stream;
-  std::vector<void*> dv;
-  auto up = [&](const void* h, size_t bytes) -> void* {
-    void* d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
-    dv.push_back(d);
-    if (bytes && h) hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st);
-    return d;
-  };
-  int* d_ptr = (int*)up(cnt.data(), cnt.size() * sizeof(int));
-  int* d_adj = (int*)up(adj.data(), adj.size() * sizeof(int));
-  int* d_ed = (int*)up(elem_dof, (size_t)nel * 3 * sizeof(int));
-  double* d_x = (double*)up(coords, (size_t)nnode * sizeof(double));
-  double* d_w = (double*)up(w.data(), w.size() * sizeof(double));
-  double* d_phi = (double*)up(phi.data(), phi.size() * sizeof(double));
-  double* d_dphi = (double*)up(dphi.data(), dphi.size() * sizeof(double));
-  double* d_d2 = (double*)up(d2.data(), d2.size() * sizeof(double));
-  int* d_code = source ? (int*)up(code.data(), code.size() * sizeof(int)) : nullptr;
-  double* d_k = source ? (double*)up(consts.data(), consts.size() * sizeof(double)) : nullptr;
-  int rc = 0;
-  if (!d_ptr || !d_adj || !d_ed || !d_x || !d_w || !d_phi || !d_dphi || !d_d2 || (source && (!d_code || !d_k))) {
-    fh_set_error("fh_assemble_advdiff_line: out of device memory");
-    rc = 2;
-  } else {
-    hipLaunchKernelGGL(k_line_advdiff, dim3(fh_div_up(ndof, 64)), dim3(64), 0, st, ndof, nc, ng, d_ptr, d_adj, d_ed, d_x, sol ? sol->d : nullptr, d_w, d_phi, d_dphi,
-                       d_d2, nu, velocity, d_code, (int)code.size(), d_k, KK->d_rowptr, KK->d_col, KK->d_val, RES->d);
-    if (hipGetLastError() != hipSuccess) {
-      fh_set_error("fh_assemble_advdiff_line: launch failed");
-      rc = 2;
-    }
-    fh_mat_values_written(KK);
-  }
-  hipStreamSynchronize(st);
-  for (void* q : dv) hipFree(q);
-  return rc;
-  FH_GUARD_END("fh_assemble_advdiff_line")
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// The Poisson callback through a GENERIC (dim, nc, ng) kernel (round 6): any element family fh_fe has tables for -- the triangle (geom 3) first, whose meshes
-// do not go through the tensor-product mesh layer -- with the element table given by the caller (nloc nodes per element in the family's local order; dof id =
-// node id, the classes numbered one after the other as every FEMuS mesh is).  Two passes: one wave per element forms the element
-// matrix over the Gauss points (elem_type::Jacobian: Jac[a][b] = sum_n dphi_n/dxi_a x_n[b], grad phi_n = Jac^-1 dphi_n, w = det w_g) into a buffer, with the place of every entry in the matrix beside it; one thread per
-// ROW then adds the rows of its node's elements in ascending element order (first version: the row thread formed them itself -- 80 ms per call on 54 k TET15 elements, host preparation included):
-//   K_ij += grad phi_i . grad phi_j w,   RES_i += (scale f phi_i - grad phi_i . grad u) w        (main.cpp:430-470 with V = 0)
-// The grouping of the reference's add_matrix_blocked / add_vector_blocked, no atomics.  These one-shot calls prepare everything on every call (adjacency on the
-// host, uploads, allocations, a search per entry): they are the yardstick of the resident object in fh_generic.hip (fh_generic_assembler_*), which keeps the plan
-// on the device and gives the same bits, and which repeated assemblies -- the application's linear iterations -- go through.
-// ------------------------------------------------------------------------------------------------------------------
-constexpr int GEN_NC = 27;
-struct GenTab {              // the tables of one element shape: a mesh of mixed shapes (hexahedra, tetrahedra, prisms; quadrilaterals, triangles) names one per element
-  int nc, ng;
-  const double *w, *phi, *dphi;
-};
-struct GenTabs {
-  GenTab t[3];
-};
-// First pass: one WAVE per element.  The Gauss points are taken GEN_GC at a time through LDS: (A) lane = Gauss point: Jacobian, its inverse, weight, source value;
-// (B) lanes over (Gauss point, node): the node's gradient; (C) lane = Gauss point: grad u; (D) lanes over the pairs i <= j of the element matrix (K_ji = K_ij
-// bit for bit: the products commute) and over the residual entries, Gauss points in ascending order.  Every sum is taken in the order of the one-thread-per-row
-// kernel this replaces (nodes ascending inside a Gauss point, Gauss points ascending); 53 760 TET15 elements: 26 + 8.5 ms (element rows by one thread each +
-// searching row pass) -> 4.7 + 0.8 ms (profiles/r06_shipped_inputs_kernel_summary.md).
-// Row i of the element matrix goes to Kb[(e * ncmax + i) * ncmax + j], its residual entry to Fb[e * ncmax + i].
-constexpr int GEN_GC = 32;
-constexpr int GEN_LDS = GEN_NC * 3 + GEN_NC + GEN_GC * 9 + GEN_GC * 2 + GEN_GC * 3 + GEN_GC * GEN_NC * 3;
-__global__ __launch_bounds__(64) void k_poisson_pairs_generic(int nel, int ncmax, int dim, GenTabs tabs, const unsigned char* __restrict__ etab, int nloc,
-                                                              const int* __restrict__ elem_dof, const double* __restrict__ coords, const double* __restrict__ sol,
-                                                              double scale, const int* __restrict__ prog, int nprog, const double* __restrict__ pconst,
-                                                              const int* __restrict__ rowptr, const int* __restrict__ col, double* __restrict__ Kb,
-                                                              int* __restrict__ Pos, double* __restrict__ Fb) {
-  __shared__ double S[GEN_LDS];
-  __shared__ int DOF[GEN_NC];
-  double* X = S;                          // [nc][3]
-  double* U = X + GEN_NC * 3;             // [nc]
-  double* JI = U + GEN_NC;                // [GC][9]
-  double* WG = JI + GEN_GC * 9;           // [GC] det w
-  double* FS = WG + GEN_GC;               // [GC] scale f(x_g)
-  double* GU = FS + GEN_GC;               // [GC][3]
-  double* G = GU + GEN_GC * 3;            // [GC][nc][3]
-  const int e = blockIdx.x, lane = threadIdx.x;
-  const GenTab& T = tabs.t[etab ? etab[e] : 0];
-  const int nc = T.nc, ng = T.ng;
-  const double *w = T.w, *phi = T.phi, *dphi = T.dphi;
-  if (lane < nc) {
-    const int dof = elem_dof[(size_t)e * nloc + lane];
-    DOF[lane] = dof;
-    for (int d = 0; d < 3; d++) X[lane * 3 + d] = d < dim ? coords[(size_t)dof * dim + d] : 0.0;
-    U[lane] = sol ? sol[dof] : 0.0;
-  }
-  // this lane's pairs (i <= j), GEN_NC (GEN_NC + 1) / 2 = 378 at most: six per lane
-  constexpr int NPL = (GEN_NC * (GEN_NC + 1) / 2 + 63) / 64;
-  const int npair = nc * (nc + 1) / 2;
-  int pi[NPL], pj[NPL];
-  double acc[NPL];
-#pragma unroll
-  for (int k = 0; k < NPL; k++) {
-    int p = lane + 64 * k, i = 0;
-    if (p < npair) {
-      while (p >= nc - i) {
-        p -= nc - i;
-        i++;
-      }
-      pi[k] = i;
-      pj[k] = i + p;
-    } else {
-      pi[k] = pj[k] = -1;
-    }
-    acc[k] = 0.0;
-  }
-  double F = 0.0;
-  __syncthreads();
-  for (int g0 = 0; g0 < ng; g0 += GEN_GC) {
-    const int gc = min(GEN_GC, ng - g0);
-    if (lane < gc) {                      // (A)
-      const int g = g0 + lane;
-      const double* dp = dphi + (size_t)g * nc * dim;
-      double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, Ji[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, det;
-      for (int n = 0; n < nc; n++)
-        for (int p = 0; p < dim; p++)
-          for (int q = 0; q < dim; q++) J[p][q] += dp[n * dim + p] * X[n * 3 + q];
-      if (dim == 1) {
-        det = J[0][0];
-        Ji[0][0] = 1 / det;
-      } else if (dim == 2) {
-        det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-        Ji[0][0] = J[1][1] / det;
-        Ji[0][1] = -J[0][1] / det;
-        Ji[1][0] = -J[1][0] / det;
-        Ji[1][1] = J[0][0] / det;
-      } else {
-        det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) + J[0][1] * (J[1][2] * J[2][0] - J[1][0] * J[2][2]) + J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-        Ji[0][0] = (-J[1][2] * J[2][1] + J[1][1] * J[2][2]) / det;
-        Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
-        Ji[0][2] = (-J[0][2] * J[1][1] + J[0][1] * J[1][2]) / det;
-        Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) / det;
-        Ji[1][1] = (-J[0][2] * J[2][0] + J[0][0] * J[2][2]) / det;
-        Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
-        Ji[2][0] = (-J[1][1] * J[2][0] + J[1][0] * J[2][1]) / det;
-        Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
-        Ji[2][2] = (-J[0][1] * J[1][0] + J[0][0] * J[1][1]) / det;
-      }
-      for (int q = 0; q < 3; q++)
-        for (int p = 0; p < 3; p++) JI[lane * 9 + q * 3 + p] = Ji[q][p];
-      WG[lane] = det * w[g];
-      double xq[4] = {0, 0, 0, 0};
-      for (int n = 0; n < nc; n++) {
-        const double ph = phi[(size_t)g * nc + n];
-        for (int q = 0; q < dim; q++) xq[q] += X[n * 3 + q] * ph;
-      }
-      FS[lane] = prog ? scale * fh_expr_device_eval(prog, nprog, pconst, xq) : 0.0;
-    }
-    __syncthreads();
-    for (int t = lane; t < gc * nc; t += 64) {                      // (B)
-      const int l = t / nc, n = t - l * nc;
-      const double* dp = dphi + ((size_t)(g0 + l) * nc + n) * dim;
-      for (int q = 0; q < dim; q++) {
-        double sacc = 0.0;
-        for (int p = 0; p < dim; p++) sacc += JI[l * 9 + q * 3 + p] * dp[p];
-        G[(l * GEN_NC + n) * 3 + q] = sacc;
-      }
-    }
-    __syncthreads();
-    if (lane < gc) {                      // (C)
-      double gu[3] = {0, 0, 0};
-      for (int n = 0; n < nc; n++)
-        for (int q = 0; q < dim; q++) gu[q] += G[(lane * GEN_NC + n) * 3 + q] * U[n];
-      for (int q = 0; q < 3; q++) GU[lane * 3 + q] = gu[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NPL; k++)         // (D)
-      if (pi[k] >= 0) {
-        double a = acc[k];
-        for (int l = 0; l < gc; l++) {
-          const double *gi = G + (l * GEN_NC + pi[k]) * 3, *gj = G + (l * GEN_NC + pj[k]) * 3;
-          double sacc = 0.0;
-          for (int q = 0; q < dim; q++) sacc += gi[q] * gj[q];
-          a += sacc * WG[l];
-        }
-        acc[k] = a;
-      }
-    if (lane < nc)
-      for (int l = 0; l < gc; l++) {
-        const double* gi = G + (l * GEN_NC + lane) * 3;
-        double lap = 0.0;
-        for (int q = 0; q < dim; q++) lap += gi[q] * GU[l * 3 + q];
-        F += (FS[l] * phi[(size_t)(g0 + l) * nc + lane] - lap) * WG[l];
-      }
-    __syncthreads();
-  }
-  // the entry's place in the matrix beside its value (-1: the pattern does not hold it), so that the row pass adds without searching
-  double* out = Kb + (size_t)e * ncmax * ncmax;
-  int* pos = Pos + (size_t)e * ncmax * ncmax;
-  auto place = [&](int i, int j) {
-    const int r = DOF[i], c = DOF[j];
-    int at = -1;
-    for (int k = rowptr[r], re = rowptr[r + 1]; k < re; k++)
-      if (col[k] == c) {
-        at = k;
-        break;
-      }
-    return at;
-  };
-#pragma unroll
-  for (int k = 0; k < NPL; k++)
-    if (pi[k] >= 0) {
-      out[(size_t)pi[k] * ncmax + pj[k]] = acc[k];
-      pos[(size_t)pi[k] * ncmax + pj[k]] = place(pi[k], pj[k]);
-      if (pi[k] != pj[k]) {
-        out[(size_t)pj[k] * ncmax + pi[k]] = acc[k];
-        pos[(size_t)pj[k] * ncmax + pi[k]] = place(pj[k], pi[k]);
-      }
-    }
-  if (lane < nc) Fb[(size_t)e * ncmax + lane] = F;
-}
-
-// Second pass: one thread per row, its (element, local row) pairs in ascending element order -- the order of the reference's element loop --, every entry added
-// at the place the first pass found for it.
-__global__ __launch_bounds__(64) void k_poisson_rows_generic(int ndof, int ncmax, GenTabs tabs, const unsigned char* __restrict__ etab,
-                                                             const int* __restrict__ adj_ptr, const int* __restrict__ adj, const double* __restrict__ Kb,
-                                                             const int* __restrict__ Pos, const double* __restrict__ Fb, const int* __restrict__ rowptr,
-                                                             double* __restrict__ val, double* __restrict__ res) {
-  const int r = blockIdx.x * 64 + threadIdx.x;
-  if (r >= ndof) return;
-  const int rs = rowptr[r], re = rowptr[r + 1];
-  for (int k = rs; k < re; k++) val[k] = 0.0;
-  double racc = 0.0;
-  for (int a = adj_ptr[r]; a < adj_ptr[r + 1]; a++) {
-    const int e = adj[a] / GEN_NC, i = adj[a] % GEN_NC;
-    const int nc = tabs.t[etab ? etab[e] : 0].nc;
-    const size_t pr = (size_t)e * ncmax + i;
-    racc += Fb[pr];
-    const double* B = Kb + pr * ncmax;
-    const int* at = Pos + pr * ncmax;
-    for (int j = 0; j < nc; j++)
-      if (at[j] >= 0) val[at[j]] += B[j];
-  }
-  res[r] = racc;
-}
-
-// shapes[ns] (ns <= 3, one dimension), elem_shape[nel] = index into shapes per element (nullptr: every element is shapes[0])
-static int poisson_rows_impl(fh_ctx_t ctx, int ns, const int* shapes, const int* elem_shape, int fe, int order, int nel, int nloc, const int* elem_dof, int nnode,
-                             const double* coords, fh_vec_t sol, fh_expr_t source, double scale, fh_mat_t KK, fh_vec_t RES) {
-  const int dim = fhfe::dim_of(shapes[0]), ndof = KK->m;
-  int ncs[3] = {0, 0, 0};
-  for (int k = 0; k < ns; k++) {
-    FH_REQUIRE(shapes[k] >= 0 && shapes[k] <= 5, "fh_assemble_poisson_rows: geom must be 0 (hex), 1 (quad), 2 (line), 3 (triangle), 4 (tetrahedron) or 5 (prism)");
-    FH_REQUIRE(fhfe::dim_of(shapes[k]) == dim, "fh_assemble_poisson_mixed: the shapes of one mesh have one dimension");
-    ncs[k] = fhfe::ndofs_of(shapes[k], fe);
-    FH_REQUIRE(nloc >= ncs[k] && ncs[k] <= GEN_NC, "fh_assemble_poisson_rows: %d nodes per element given, the family has %d", nloc, ncs[k]);
-  }
-  FH_REQUIRE(KK->n == ndof && RES->n_local >= ndof && (!sol || sol->n_local >= ndof), "fh_assemble_poisson_rows: size mismatch");
-  std::vector<unsigned char> etab;
-  if (elem_shape) {
-    etab.resize(nel);
-    for (int e = 0; e < nel; e++) {
-      FH_REQUIRE(elem_shape[e] >= 0 && elem_shape[e] < ns, "fh_assemble_poisson_mixed: element %d names shape %d of %d", e, elem_shape[e], ns);
-      etab[e] = (unsigned char)elem_shape[e];
-    }
-  }
-  auto nc_of = [&](int e) { return ncs[elem_shape ? elem_shape[e] : 0]; };
-  std::vector<int> cnt(ndof + 1, 0);
-  for (int e = 0; e < nel; e++)
-    for (int n = 0; n < nc_of(e); n++) {
-      const int d = elem_dof[(size_t)e * nloc + n];
-      FH_REQUIRE(d >= 0 && d < ndof && d < nnode, "fh_assemble_poisson_rows: element %d, node %d: dof %d outside the system (the classes are numbered one after the other)", e, n, d);
-      cnt[d + 1]++;
-    }
-  for (int d = 0; d < ndof; d++) cnt[d + 1] += cnt[d];
-  std::vector<int> adj(cnt[ndof]), fill(cnt.begin(), cnt.end() - 1);
-  FH_REQUIRE((int64_t)nel * GEN_NC < 2147483647ll, "fh_assemble_poisson_rows: too many elements");
-  for (int e = 0; e < nel; e++)                         // ascending element order per dof
-    for (int n = 0; n < nc_of(e); n++) adj[fill[elem_dof[(size_t)e * nloc + n]]++] = e * GEN_NC + n;
-  std::vector<double> w[3], phi[3], dphi[3];
-  for (int k = 0; k < ns; k++) FH_REQUIRE(fhfe::shape_tables(shapes[k], fe, order, w[k], phi[k], dphi[k]) == 0, "fh_assemble_poisson_rows: unsupported Gauss rule");
-  std::vector<int> code;
-  std::vector<double> consts;
-  if (source) {
-    int nv = 0, ncode = 0, nk = 0;
-    FH_TRY(fh_expr_nvars(source, &nv));
-    FH_REQUIRE(nv <= 4, "fh_assemble_poisson_rows: the source expression has %d variables, at most 4 (x, y, z, t) are served", nv);
-    FH_TRY(fh_expr_program(source, &ncode, &nk, nullptr, nullptr));
-    code.resize(ncode);
-    consts.resize(std::max(nk, 1));
-    FH_TRY(fh_expr_program(source, &ncode, &nk, code.data(), consts.data()));
-  }
-  hipStream_t st = ctx->stream;
-  std::vector<void*> dv;
-  bool oom = false;
-  auto up = [&](const void* h, size_t bytes) -> void* {
-    void* d = nullptr;
-    if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) {
-      oom = true;
-      return nullptr;
-    }
-    dv.push_back(d);
-    if (bytes && h) hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st);
-    return d;
-  };
-  int* d_ptr = (int*)up(cnt.data(), cnt.size() * sizeof(int));
-  int* d_adj = (int*)up(adj.data(), adj.size() * sizeof(int));
-  int* d_ed = (int*)up(elem_dof, (size_t)nel * nloc * sizeof(int));
-  double* d_x = (double*)up(coords, (size_t)nnode * dim * sizeof(double));
-  GenTabs tabs;
-  for (int k = 0; k < 3; k++) tabs.t[k] = GenTab{0, 0, nullptr, nullptr, nullptr};
-  for (int k = 0; k < ns; k++)
-    tabs.t[k] = GenTab{ncs[k], (int)w[k].size(), (const double*)up(w[k].data(), w[k].size() * sizeof(double)), (const double*)up(phi[k].data(), phi[k].size() * sizeof(double)),
-                       (const double*)up(dphi[k].data(), dphi[k].size() * sizeof(double))};
-  unsigned char* d_etab = elem_shape ? (unsigned char*)up(etab.data(), etab.size()) : nullptr;
-  int* d_code = source ? (int*)up(code.data(), code.size() * sizeof(int)) : nullptr;
-  double* d_k = source ? (double*)up(consts.data(), consts.size() * sizeof(double)) : nullptr;
-  const int ncmax = std::max(ncs[0], std::max(ncs[1], ncs[2]));
-  FH_REQUIRE((int64_t)nel * ncmax < 2147483647ll, "fh_assemble_poisson_rows: too many elements");
-  double* d_Kb = (double*)up(nullptr, (size_t)nel * ncmax * ncmax * sizeof(double));      // element rows between the two passes
-  double* d_Fb = (double*)up(nullptr, (size_t)nel * ncmax * sizeof(double));
-  int* d_Pos = (int*)up(nullptr, (size_t)nel * ncmax * ncmax * sizeof(int));
-  int rc = 0;
-  if (oom) {
-    fh_set_error("fh_assemble_poisson_rows: out of device memory");
-    rc = 2;
-  } else {
-    hipLaunchKernelGGL(k_poisson_pairs_generic, dim3(nel), dim3(64), 0, st, nel, ncmax, dim, tabs, d_etab, nloc, d_ed, d_x,
-                       sol ? sol->d : nullptr, scale, d_code, (int)code.size(), d_k, KK->d_rowptr, KK->d_col, d_Kb, d_Pos, d_Fb);
-    hipLaunchKernelGGL(k_poisson_rows_generic, dim3(fh_div_up(ndof, 64)), dim3(64), 0, st, ndof, ncmax, tabs, d_etab, d_ptr, d_adj, d_Kb, d_Pos, d_Fb, KK->d_rowptr,
-                       KK->d_val, RES->d);
-    if (hipGetLastError() != hipSuccess) {
-      fh_set_error("fh_assemble_poisson_rows: launch failed");
-      rc = 2;
-    }
-    fh_mat_values_written(KK);
-  }
-  hipStreamSynchronize(st);
-  for (void* q : dv) hipFree(q);
-  return rc;
-}
-
-extern "C" int fh_assemble_poisson_rows(fh_ctx_t ctx, int geom, int fe, int order, int nel, int nloc, const int* elem_dof, int nnode, const double* coords,
-                                        fh_vec_t sol, fh_expr_t source, double scale, fh_mat_t KK, fh_vec_t RES) {
-  FH_GUARD_BEGIN
-  FH_REQUIRE(ctx && elem_dof && coords && KK && RES && nel >= 1 && nnode >= 1, "fh_assemble_poisson_rows: null or empty argument");
-  FH_REQUIRE(geom >= 0 && geom <= 5, "fh_assemble_poisson_rows: geom must be 0 (hex), 1 (quad), 2 (line), 3 (triangle), 4 (tetrahedron) or 5 (prism)");
-  FH_REQUIRE(fe == fhfe::FE_LINEAR || fe == fhfe::FE_SERENDIPITY || fe == fhfe::FE_BIQUADRATIC, "fh_assemble_poisson_rows: fe must be 0, 1 or 2");
-  return poisson_rows_impl(ctx, 1, &geom, nullptr, fe, order, nel, nloc, elem_dof, nnode, coords, sol, source, scale, KK, RES);
-  FH_GUARD_END("fh_assemble_poisson_rows")
-}
-
-// The same on a mesh of MIXED shapes (cube_all_shapes*.neu of applications/001_Poisson: hexahedra, tetrahedra and prisms in one file): elem_geom[nel] names the
-// shape of every element (at most three different ones, of one dimension); rows of elem_dof padded to nloc.  The entries of a row are summed in ascending element
-// order whatever the shapes, as the reference's element loop does.
-extern "C" int fh_assemble_poisson_mixed(fh_ctx_t ctx, int fe, int order, int nel, int nloc, const int* elem_geom, const int* elem_dof, int nnode, const double* coords,
-                                         fh_vec_t sol, fh_expr_t source, double scale, fh_mat_t KK, fh_vec_t RES) {
-  FH_GUARD_BEGIN
-  FH_REQUIRE(ctx && elem_geom && elem_dof && coords && KK && RES && nel >= 1 && nnode >= 1, "fh_assemble_poisson_mixed: null or empty argument");
-  FH_REQUIRE(fe == fhfe::FE_LINEAR || fe == fhfe::FE_SERENDIPITY || fe == fhfe::FE_BIQUADRATIC, "fh_assemble_poisson_mixed: fe must be 0, 1 or 2");
-  int shapes[3], ns = 0;
-  std::vector<int> idx(nel);
-  for (int e = 0; e < nel; e++) {
-    int k = 0;
-    while (k < ns && shapes[k] != elem_geom[e]) k++;
-    if (k == ns) {
-      FH_REQUIRE(ns < 3, "fh_assemble_poisson_mixed: more than three shapes in one mesh");
-      FH_REQUIRE(elem_geom[e] >= 0 && elem_geom[e] <= 5, "fh_assemble_poisson_mixed: element %d: shape %d", e, elem_geom[e]);
-      shapes[ns++] = elem_geom[e];
-    }
-    idx[e] = k;
-  }
-  return poisson_rows_impl(ctx, ns, shapes, idx.data(), fe, order, nel, nloc, elem_dof, nnode, coords, sol, source, scale, KK, RES);
-  FH_GUARD_END("fh_assemble_poisson_mixed")
 }

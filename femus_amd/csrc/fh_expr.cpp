@@ -324,6 +324,18 @@ extern "C" int fh_expr_nvars(fh_expr_t e, int* nvars) {
   return 0;
 }
 
+// the program of `e` for an upload: code and consts resized to its lengths (consts may come back empty; a caller that uploads it pads it itself).
+// `who` is the subject of the refusal of a program over more than max_vars variables, e.g. "fh_assemble_poisson_rows: the source expression".
+int fh_expr_fetch(fh_expr_t e, const char* who, int max_vars, std::vector<int>& code, std::vector<double>& consts) {
+  int nv = 0, nc = 0, nk = 0;
+  FH_TRY(fh_expr_nvars(e, &nv));
+  FH_REQUIRE(nv <= max_vars, "%s has %d variables, at most %d (x, y, z, t) are served", who, nv, max_vars);
+  FH_TRY(fh_expr_program(e, &nc, &nk, nullptr, nullptr));
+  code.resize(nc);
+  consts.resize(nk);
+  return fh_expr_program(e, &nc, &nk, code.data(), consts.data());
+}
+
 extern "C" int fh_expr_destroy(fh_expr_t e) {
   delete e;
   return 0;

@@ -3,6 +3,7 @@
 // checks what the device math library makes of every operator and function of the grammar, non-finite values included.
 #include "fh_internal.h"
 #include "fh_expr_device.h"
+#include <climits>
 
 // one thread per point; x[npts * nvars] row by row
 __global__ void k_expr_eval_points(const int* __restrict__ code, int ncode, const double* __restrict__ consts, const double* __restrict__ x, int nvars,
@@ -15,15 +16,16 @@ __global__ void k_expr_eval_points(const int* __restrict__ code, int ncode, cons
 extern "C" int fh_expr_eval_device(fh_ctx_t ctx, fh_expr_t e, int npts, const double* x, double* values) {
   FH_REQUIRE(ctx && e && npts >= 0, "fh_expr_eval_device: null argument");
   if (npts == 0) return 0;
-  int nv = 0, nc = 0, nk = 0;
+  int nv = 0;
   FH_TRY(fh_expr_nvars(e, &nv));
   FH_REQUIRE(values && (x || nv == 0), "fh_expr_eval_device: null argument");
   FH_REQUIRE((int64_t)npts * std::max(nv, 1) < ((int64_t)1 << 31), "fh_expr_eval_device: %d points of %d variables: more than 2^31 numbers", npts, nv);
   FH_GUARD_BEGIN
-  FH_TRY(fh_expr_program(e, &nc, &nk, nullptr, nullptr));
-  std::vector<int> code(nc);
-  std::vector<double> consts(std::max(nk, 1), 0.0);
-  FH_TRY(fh_expr_program(e, &nc, &nk, code.data(), consts.data()));
+  std::vector<int> code;
+  std::vector<double> consts;
+  FH_TRY(fh_expr_fetch(e, "fh_expr_eval_device: the expression", INT_MAX, code, consts));     // a point has as many entries as the expression has variables
+  if (consts.empty()) consts.resize(1, 0.0);
+  const int nc = (int)code.size();
   const size_t bx = (size_t)npts * nv * sizeof(double), bv = (size_t)npts * sizeof(double);
   void* dv[4] = {nullptr, nullptr, nullptr, nullptr};
   auto run = [&]() -> int {

@@ -1,22 +1,29 @@
-// Resident plan for the generic (dim, nc, ng) Poisson assembly (fh_generic_assembler_*): what fh_assemble_poisson_rows / fh_assemble_poisson_mixed
-// (fh_assemble.hip: poisson_rows_impl) rebuild on every call -- the dof -> element adjacency, the uploaded element table, coordinates and FE tables, a dozen
-// allocations, a linear search of every (i, j) in its CSR row -- is made ONCE here and kept on the device; an assembly then only enqueues kernels.
+// The generic (dim, nc, ng) Poisson assembly: every element family fh_fe has tables for, on any mesh whose element table the caller gives (nloc nodes per element
+// in the family's local order; dof id = node id, the classes numbered one after the other as every FEMuS mesh is) -- triangles, tetrahedra, prisms, mixed shapes:
+//   K_ij += grad phi_i . grad phi_j w,   RES_i += (scale f phi_i - grad phi_i . grad u) w        (applications/001_Poisson/main.cpp:430-470 with V = 0)
+// with elem_type::Jacobian (Jac[a][b] = sum_n dphi_n/dxi_a x_n[b], grad phi_n = Jac^-1 dphi_n, w = det w_g), the rows summed in ascending element order: the
+// grouping of the reference's add_matrix_blocked / add_vector_blocked, no atomics.  Two drivers share ONE element body, gen_element_pass:
 //
-// Plan, per shape k of the mesh (at most three of one dimension, in the order of their first element):
+// One-shot calls (fh_assemble_poisson_rows / fh_assemble_poisson_mixed, at the end of this file) prepare everything on every call -- the dof -> element adjacency
+// on the host, uploads, a dozen allocations, a linear search of every (i, j) in its CSR row -- and run one wave per element (k_poisson_pairs_generic) and one
+// thread per row (k_poisson_rows_generic).  They are the independent yardstick of the resident object: their own launch geometry, search and row pass.
+//
+// Resident plan (fh_generic_assembler_*): all of that is made ONCE and kept on the device; an assembly then only enqueues kernels.  Per shape k of the mesh (at
+// most three of one dimension, in the order of their first element):
 //   d_ed[k]     [nslot_k][nc_k]  the dofs of the shape's elements, slot = rank of the element among the elements of its shape (ascending element order)
 //   Kb / Pos    element row (slot, i) of shape k starts at kb_base[k] + (slot nc_k + i) nc_k: its nc_k values, and beside them the CSR position of every
 //               one, found at create by a binary search of the (sorted) row on the device; a pair the pattern does not hold fails create
 //   Fb / adj    the element row's residual entry at row_base[k] + slot nc_k + i = the row's id; adj lists the ids of a dof in ascending ELEMENT order
 //
-// Element pass, one launch per shape (uniform waves on mixed meshes): workgroups of 256 threads, L = 64 / 32 / 16 lanes per element (1 / 2 / 4 elements per wave)
-// from the shape's nc (nc + 1) / 2 pairs; dynamic LDS sized by the shape's nc and Gauss chunk, w / phi / dphi staged once per workgroup where they fit.
-// Every value is formed by the expressions of k_poisson_pairs_generic in their order (Gauss points ascending, nodes ascending inside a point, K_ji the bits of
-// K_ij); the library is built with -ffp-contract=on, so the same source expression contracts the same way, and the results are bitwise the one-shot call's.
-// The length of the Gauss chunk only moves barriers, not one operation: the accumulators run through all points in ascending order whatever it is.
+// Element pass of the plan, one launch per shape (uniform waves on mixed meshes): workgroups of 256 threads, L = 64 / 32 / 16 lanes per element (1 / 2 / 4
+// elements per wave) from the shape's nc (nc + 1) / 2 pairs; dynamic LDS sized by the shape's nc and Gauss chunk, w / phi / dphi staged once per workgroup where
+// they fit.  Its values are bitwise the one-shot call's because both kernels inline the same body: Gauss points ascending, nodes ascending inside a point, K_ji
+// the bits of K_ij.  What the two pass differently -- lanes per element, the node stride of the LDS arrays, the length of the Gauss chunk -- moves addresses and
+// barriers, not one operation: the accumulators run through all points in ascending order whatever the chunk is.
 //
-// Row pass: lpr lanes per row (a group never leaves its wave), the row's sums in LDS: element rows in ascending element order, the lanes of the group split one
-// element row's entries (distinct positions), LDS operations of one wave complete in order -- so every entry sees its additions in ascending element order,
-// starting from 0.0 as the one-shot row thread does.  No search, no atomics, no read-modify-write of global memory.
+// Row pass of the plan: lpr lanes per row (a group never leaves its wave), the row's sums in LDS: element rows in ascending element order, the lanes of the group
+// split one element row's entries (distinct positions), LDS operations of one wave complete in order -- so every entry sees its additions in ascending element
+// order, starting from 0.0 as the one-shot row thread does.  No search, no atomics, no read-modify-write of global memory.
 #include "fh_internal.h"
 #include "fh_fe.h"
 #include "fh_expr_device.h"
@@ -27,9 +34,12 @@ namespace {
 constexpr int GP_THREADS = 256;
 constexpr size_t GP_LDS_BUDGET = 64 * 1024;   // per workgroup: two workgroups and more per CU (160 KB of LDS), and no opt-in to large dynamic LDS needed
 constexpr size_t GP_PROG_BYTES = 4096;        // first size of the source program's buffer
+constexpr int GEN_NC = 27;                    // most nodes of an element (HEX27); the node stride of the one-shot kernel
+constexpr int GEN_GC = 32;                    // Gauss points per chunk of the one-shot kernel
 
-// doubles of LDS one element needs: X[nc][3], U[nc], JI[gc][9], WG[gc], FS[gc], GU[gc][3], G[gc][nc][3]
-inline size_t gp_elem_doubles(int nc, int gc) { return (size_t)nc * 4 + (size_t)gc * 14 + (size_t)gc * nc * 3; }
+// doubles of LDS one element needs at node stride ns and chunk gc: X[ns][3], U[ns], JI[gc][9], WG[gc], FS[gc], GU[gc][3], G[gc][ns][3]
+constexpr size_t gp_elem_doubles(int ns, int gc) { return (size_t)ns * 4 + (size_t)gc * 14 + (size_t)gc * ns * 3; }
+constexpr int gp_pairs_per_lane(int L) { return L == 64 ? (GEN_NC * (GEN_NC + 1) / 2 + 63) / 64 : 2; }     // 378 pairs on 64 lanes: six; at most 2 L pairs where L < 64
 inline int gp_lanes_per_element(int nc, int pack) {
   const int npair = nc * (nc + 1) / 2;
   if (!pack) return 64;
@@ -37,46 +47,31 @@ inline int gp_lanes_per_element(int nc, int pack) {
 }
 }  // namespace
 
-// Element pass.  L lanes per element, 256 / L elements per workgroup; TL: the shape's tables in LDS.  Phases (A)-(D) of k_poisson_pairs_generic, lane loops
-// strided by L where the one-shot kernel has `lane < gc` of 64.
-template <int L, bool TL>
-__global__ __launch_bounds__(GP_THREADS) void k_gen_pairs(int nslot, int nc, int ng, int gcm, int dim, const double* __restrict__ gw, const double* __restrict__ gphi,
-                                                          const double* __restrict__ gdphi, const int* __restrict__ ed, const double* __restrict__ coords,
-                                                          const double* __restrict__ sol, double scale, const int* __restrict__ prog, int nprog,
-                                                          const double* __restrict__ pconst, double* __restrict__ Kb, double* __restrict__ Fb) {
-  extern __shared__ __attribute__((aligned(16))) double gen_smem[];
-  constexpr int EPG = GP_THREADS / L;
-  constexpr int NPL = L == 64 ? 6 : 2;           // 27 * 28 / 2 = 378 pairs on 64 lanes; at most 2 L pairs where L < 64
-  const int ntab = TL ? ng + ng * nc + ng * nc * dim : 0;
-  const int per = nc * 4 + gcm * 14 + gcm * nc * 3;
-  const int sub = threadIdx.x / L, lane = threadIdx.x % L;
-  const int slot = blockIdx.x * EPG + sub;
-  const bool active = slot < nslot;              // tail sub-groups keep the barriers and touch nothing
-  const double *w, *phi, *dphi;
-  if (TL) {
-    double* tw = gen_smem;
-    double* tphi = tw + ng;
-    double* tdphi = tphi + ng * nc;
-    for (int t = threadIdx.x; t < ng; t += GP_THREADS) tw[t] = gw[t];
-    for (int t = threadIdx.x; t < ng * nc; t += GP_THREADS) tphi[t] = gphi[t];
-    for (int t = threadIdx.x; t < ng * nc * dim; t += GP_THREADS) tdphi[t] = gdphi[t];
-    w = tw, phi = tphi, dphi = tdphi;
-  } else {
-    w = gw, phi = gphi, dphi = gdphi;
-  }
-  double* X = gen_smem + ntab + (size_t)sub * per;   // [nc][3]
-  double* U = X + nc * 3;                            // [nc]
-  double* JI = U + nc;                               // [gcm][9]
+// THE element body: L lanes form the matrix and the residual entries of one element whose dofs are dof_row[0 .. nc), in `lds` (gp_elem_doubles(ns, gcm) doubles).
+// The Gauss points are taken gcm at a time through LDS: (A) lane = Gauss point: Jacobian, its inverse, weight, source value; (B) lanes over (Gauss point, node):
+// the node's gradient; (C) lane = Gauss point: grad u; (D) lanes over the pairs i <= j of the element matrix (K_ji = K_ij bit for bit: the products commute) and
+// over the residual entries.  Every sum is taken nodes ascending inside a Gauss point, Gauss points ascending.  On return pair k of this lane is (pi[k], pj[k])
+// (-1: none) with the sum acc[k], and F is residual entry `lane` (lane < nc).  Every thread of the workgroup calls this, with the same ng and gcm: the barriers
+// are workgroup barriers; a sub-group without an element passes active = false and touches nothing.
+template <int L, int NPL>
+__device__ __forceinline__ void gen_element_pass(bool active, int lane, int nc, int ng, int gcm, int ns, int dim, const double* w, const double* phi, const double* dphi,
+                                                 const int* dof_row, const double* coords, const double* sol, double scale, const int* prog, int nprog,
+                                                 const double* pconst, double* lds, int (&pi_out)[NPL], int (&pj_out)[NPL], double (&acc_out)[NPL], double& F_out) {
+  double* X = lds;                                   // [ns][3]
+  double* U = X + ns * 3;                            // [ns]
+  double* JI = U + ns;                               // [gcm][9]
   double* WG = JI + gcm * 9;                         // [gcm] det w
   double* FS = WG + gcm;                             // [gcm] scale f(x_g)
   double* GU = FS + gcm;                             // [gcm][3]
-  double* G = GU + gcm * 3;                          // [gcm][nc][3]
+  double* G = GU + gcm * 3;                          // [gcm][ns][3]
   if (active && lane < nc) {
-    const int dof = ed[(size_t)slot * nc + lane];
+    const int dof = dof_row[lane];
     for (int d = 0; d < 3; d++) X[lane * 3 + d] = d < dim ? coords[(size_t)dof * dim + d] : 0.0;
     U[lane] = sol ? sol[dof] : 0.0;
   }
   const int npair = nc * (nc + 1) / 2;
+  // the lane's pairs and sums live in arrays of this function and are handed out at the end: written through the caller's references the pair arrays
+  // end up in scratch memory (this body is optimised before it is inlined, and its two-way store to pi / pj cannot be split into registers afterwards)
   int pi[NPL], pj[NPL];
   double acc[NPL];
 #pragma unroll
@@ -145,7 +140,7 @@ __global__ __launch_bounds__(GP_THREADS) void k_gen_pairs(int nslot, int nc, int
         for (int q = 0; q < dim; q++) {
           double sacc = 0.0;
           for (int p = 0; p < dim; p++) sacc += JI[l * 9 + q * 3 + p] * dp[p];
-          G[(l * nc + n) * 3 + q] = sacc;
+          G[(l * ns + n) * 3 + q] = sacc;
         }
       }
     __syncthreads();
@@ -153,7 +148,7 @@ __global__ __launch_bounds__(GP_THREADS) void k_gen_pairs(int nslot, int nc, int
       for (int l = lane; l < gc; l += L) {             // (C)
         double gu[3] = {0, 0, 0};
         for (int n = 0; n < nc; n++)
-          for (int q = 0; q < dim; q++) gu[q] += G[(l * nc + n) * 3 + q] * U[n];
+          for (int q = 0; q < dim; q++) gu[q] += G[(l * ns + n) * 3 + q] * U[n];
         for (int q = 0; q < 3; q++) GU[l * 3 + q] = gu[q];
       }
     __syncthreads();
@@ -162,7 +157,7 @@ __global__ __launch_bounds__(GP_THREADS) void k_gen_pairs(int nslot, int nc, int
       if (pi[k] >= 0) {
         double a = acc[k];
         for (int l = 0; l < gc; l++) {
-          const double *gi = G + (l * nc + pi[k]) * 3, *gj = G + (l * nc + pj[k]) * 3;
+          const double *gi = G + (l * ns + pi[k]) * 3, *gj = G + (l * ns + pj[k]) * 3;
           double sacc = 0.0;
           for (int q = 0; q < dim; q++) sacc += gi[q] * gj[q];
           a += sacc * WG[l];
@@ -171,13 +166,49 @@ __global__ __launch_bounds__(GP_THREADS) void k_gen_pairs(int nslot, int nc, int
       }
     if (active && lane < nc)
       for (int l = 0; l < gc; l++) {
-        const double* gi = G + (l * nc + lane) * 3;
+        const double* gi = G + (l * ns + lane) * 3;
         double lap = 0.0;
         for (int q = 0; q < dim; q++) lap += gi[q] * GU[l * 3 + q];
         F += (FS[l] * phi[(size_t)(g0 + l) * nc + lane] - lap) * WG[l];
       }
     __syncthreads();
   }
+#pragma unroll
+  for (int k = 0; k < NPL; k++) pi_out[k] = pi[k], pj_out[k] = pj[k], acc_out[k] = acc[k];
+  F_out = F;
+}
+
+// Element pass of the plan.  L lanes per element, 256 / L elements per workgroup; TL: the shape's tables in LDS.  Element rows compact: row i of slot s at
+// Kb[(s nc + i) nc], its residual entry at Fb[s nc + i].
+template <int L, bool TL>
+__global__ __launch_bounds__(GP_THREADS) void k_gen_pairs(int nslot, int nc, int ng, int gcm, int dim, const double* __restrict__ gw, const double* __restrict__ gphi,
+                                                          const double* __restrict__ gdphi, const int* __restrict__ ed, const double* __restrict__ coords,
+                                                          const double* __restrict__ sol, double scale, const int* __restrict__ prog, int nprog,
+                                                          const double* __restrict__ pconst, double* __restrict__ Kb, double* __restrict__ Fb) {
+  extern __shared__ __attribute__((aligned(16))) double gen_smem[];
+  constexpr int EPG = GP_THREADS / L;
+  constexpr int NPL = gp_pairs_per_lane(L);
+  const int ntab = TL ? ng + ng * nc + ng * nc * dim : 0;
+  const int per = nc * 4 + gcm * 14 + gcm * nc * 3;
+  const int sub = threadIdx.x / L, lane = threadIdx.x % L;
+  const int slot = blockIdx.x * EPG + sub;
+  const bool active = slot < nslot;              // tail sub-groups keep the barriers and touch nothing
+  const double *w, *phi, *dphi;
+  if (TL) {
+    double* tw = gen_smem;
+    double* tphi = tw + ng;
+    double* tdphi = tphi + ng * nc;
+    for (int t = threadIdx.x; t < ng; t += GP_THREADS) tw[t] = gw[t];
+    for (int t = threadIdx.x; t < ng * nc; t += GP_THREADS) tphi[t] = gphi[t];
+    for (int t = threadIdx.x; t < ng * nc * dim; t += GP_THREADS) tdphi[t] = gdphi[t];
+    w = tw, phi = tphi, dphi = tdphi;
+  } else {
+    w = gw, phi = gphi, dphi = gdphi;
+  }
+  int pi[NPL], pj[NPL];
+  double acc[NPL], F;
+  gen_element_pass<L, NPL>(active, lane, nc, ng, gcm, nc, dim, w, phi, dphi, ed + (size_t)slot * nc, coords, sol, scale, prog, nprog, pconst,
+                           gen_smem + ntab + (size_t)sub * per, pi, pj, acc, F);
   if (!active) return;
   double* out = Kb + (size_t)slot * nc * nc;
 #pragma unroll
@@ -244,6 +275,56 @@ __global__ __launch_bounds__(GP_THREADS) void k_gen_rows(int ndof, int lpr, int 
   }
   for (int k = t; k < n; k += lpr) val[rs + k] = acc[k];
   if (t == 0) res[r] = racc;
+}
+
+// What both drivers make of a mesh before anything touches the device: the shapes in the order of their first element, the tables and checks of each, and how
+// many element rows every dof has.  Filled by gen_mesh, whose refusals begin with the entry point that was called (`who`).
+struct GenMesh {
+  int ns = 0, dim = 0, ncmax = 0;
+  int shapes[3] = {0, 0, 0}, nc[3] = {0, 0, 0}, nslot[3] = {0, 0, 0};     // nslot: elements of the shape
+  std::vector<unsigned char> eshape;                                      // [nel] the element's index into shapes
+  std::vector<double> w[3], phi[3], dphi[3];
+  std::vector<int> adj_ptr;                                               // [ndof + 1] the element rows of dof d are adj_ptr[d] .. adj_ptr[d + 1]
+};
+
+// elem_geom[nel] names the shape of every element (nullptr: every element is `geom`); the dofs of an element are the first nc of its nloc
+static int gen_mesh(const char* who, int fe, int order, int nel, int nloc, const int* elem_geom, int geom, const int* elem_dof, int nnode, int ndof, GenMesh& m) {
+  m.eshape.assign(nel, 0);
+  if (elem_geom) {
+    for (int e = 0; e < nel; e++) {
+      int k = 0;
+      while (k < m.ns && m.shapes[k] != elem_geom[e]) k++;
+      if (k == m.ns) {
+        FH_REQUIRE(m.ns < 3, "%s: more than three shapes in one mesh (element %d)", who, e);
+        FH_REQUIRE(elem_geom[e] >= 0 && elem_geom[e] <= 5, "%s: element %d: shape %d", who, e, elem_geom[e]);
+        m.shapes[m.ns++] = elem_geom[e];
+      }
+      m.eshape[e] = (unsigned char)k;
+    }
+  } else {
+    FH_REQUIRE(geom >= 0 && geom <= 5, "%s: geom must be 0 (hex), 1 (quad), 2 (line), 3 (triangle), 4 (tetrahedron) or 5 (prism)", who);
+    m.shapes[m.ns++] = geom;
+  }
+  m.dim = fhfe::dim_of(m.shapes[0]);
+  for (int k = 0; k < m.ns; k++) {
+    FH_REQUIRE(fhfe::dim_of(m.shapes[k]) == m.dim, "%s: the shapes of one mesh have one dimension (shapes %d and %d)", who, m.shapes[0], m.shapes[k]);
+    m.nc[k] = fhfe::ndofs_of(m.shapes[k], fe);
+    FH_REQUIRE(m.nc[k] >= 1 && m.nc[k] <= GEN_NC && nloc >= m.nc[k], "%s: %d nodes per element given, the family has %d", who, nloc, m.nc[k]);
+    FH_REQUIRE(fhfe::shape_tables(m.shapes[k], fe, order, m.w[k], m.phi[k], m.dphi[k]) == 0, "%s: unsupported Gauss rule", who);
+    m.ncmax = std::max(m.ncmax, m.nc[k]);
+  }
+  m.adj_ptr.assign((size_t)ndof + 1, 0);
+  for (int e = 0; e < nel; e++) {
+    const int k = m.eshape[e];
+    m.nslot[k]++;
+    for (int n = 0; n < m.nc[k]; n++) {
+      const int d = elem_dof[(size_t)e * nloc + n];
+      FH_REQUIRE(d >= 0 && d < ndof && d < nnode, "%s: element %d, node %d: dof %d outside the system (the classes are numbered one after the other)", who, e, n, d);
+      m.adj_ptr[d + 1]++;
+    }
+  }
+  for (int d = 0; d < ndof; d++) m.adj_ptr[d + 1] += m.adj_ptr[d];
+  return 0;
 }
 
 struct fh_generic_assembler_s {
@@ -318,50 +399,20 @@ extern "C" int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int order, int 
   FH_REQUIRE(fe == fhfe::FE_LINEAR || fe == fhfe::FE_SERENDIPITY || fe == fhfe::FE_BIQUADRATIC, "fh_generic_assembler_create: fe must be 0, 1 or 2");
   *out = nullptr;
   // ---- every check first: nothing is allocated on the device before the last of them ----
-  int shapes[3] = {0, 0, 0}, ns = 0;
-  std::vector<unsigned char> eshape(nel, 0);
-  if (elem_geom) {
-    for (int e = 0; e < nel; e++) {
-      int k = 0;
-      while (k < ns && shapes[k] != elem_geom[e]) k++;
-      if (k == ns) {
-        FH_REQUIRE(ns < 3, "fh_generic_assembler_create: more than three shapes in one mesh (element %d)", e);
-        FH_REQUIRE(elem_geom[e] >= 0 && elem_geom[e] <= 5, "fh_generic_assembler_create: element %d: shape %d", e, elem_geom[e]);
-        shapes[ns++] = elem_geom[e];
-      }
-      eshape[e] = (unsigned char)k;
-    }
-  } else {
-    FH_REQUIRE(geom >= 0 && geom <= 5, "fh_generic_assembler_create: geom must be 0 (hex), 1 (quad), 2 (line), 3 (triangle), 4 (tetrahedron) or 5 (prism)");
-    shapes[ns++] = geom;
-  }
-  const int dim = fhfe::dim_of(shapes[0]), ndof = KK->m;
-  int ncs[3] = {0, 0, 0}, nslot[3] = {0, 0, 0};
-  std::vector<double> w[3], phi[3], dphi[3];
-  for (int k = 0; k < ns; k++) {
-    FH_REQUIRE(fhfe::dim_of(shapes[k]) == dim, "fh_generic_assembler_create: the shapes of one mesh have one dimension (shapes %d and %d)", shapes[0], shapes[k]);
-    ncs[k] = fhfe::ndofs_of(shapes[k], fe);
-    FH_REQUIRE(ncs[k] >= 1 && ncs[k] <= 27 && nloc >= ncs[k], "fh_generic_assembler_create: %d nodes per element given, the family has %d", nloc, ncs[k]);
-    FH_REQUIRE(fhfe::shape_tables(shapes[k], fe, order, w[k], phi[k], dphi[k]) == 0, "fh_generic_assembler_create: unsupported Gauss rule");
-  }
+  const int ndof = KK->m;
   FH_REQUIRE(KK->n == ndof && (int)KK->h_rowptr.size() == ndof + 1, "fh_generic_assembler_create: the matrix is not square with a host row table");
-  for (int e = 0; e < nel; e++) nslot[eshape[e]]++;
+  GenMesh m;
+  FH_TRY(gen_mesh("fh_generic_assembler_create", fe, order, nel, nloc, elem_geom, geom, elem_dof, nnode, ndof, m));
+  const int ns = m.ns, dim = m.dim, ncmax = m.ncmax;
+  const int *ncs = m.nc, *nslot = m.nslot;
   int64_t nrows = 0, nent = 0;
   for (int k = 0; k < ns; k++) {
     nrows += (int64_t)nslot[k] * ncs[k];
     nent += (int64_t)nslot[k] * ncs[k] * ncs[k];
   }
   FH_REQUIRE(nrows < 2147483647ll && nent < (1ll << 40), "fh_generic_assembler_create: too many elements");
-  std::vector<int> cnt(ndof + 1, 0);
-  for (int e = 0; e < nel; e++)
-    for (int n = 0; n < ncs[eshape[e]]; n++) {
-      const int d = elem_dof[(size_t)e * nloc + n];
-      FH_REQUIRE(d >= 0 && d < ndof && d < nnode, "fh_generic_assembler_create: element %d, node %d: dof %d outside the system (the classes are numbered one after the other)", e, n, d);
-      cnt[d + 1]++;
-    }
   int maxrow = 1;
   for (int r = 0; r < ndof; r++) maxrow = std::max(maxrow, KK->h_rowptr[r + 1] - KK->h_rowptr[r]);
-  const int ncmax = std::max(ncs[0], std::max(ncs[1], ncs[2]));
   int lpr = ncmax <= 6 ? 4 : ncmax <= 10 ? 8 : 16;
   while (lpr < 64 && (size_t)(GP_THREADS / lpr) * maxrow * sizeof(double) > GP_LDS_BUDGET) lpr *= 2;
   FH_REQUIRE((size_t)(GP_THREADS / lpr) * maxrow * sizeof(double) <= GP_LDS_BUDGET, "fh_generic_assembler_create: a row of %d entries is longer than the row pass holds (%d)",
@@ -384,7 +435,7 @@ extern "C" int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int order, int 
     int rb = 0;
     long long kb = 0;
     for (int k = 0; k < ns; k++) {
-      as->nc[k] = ncs[k], as->ng[k] = (int)w[k].size(), as->nslot[k] = nslot[k];
+      as->nc[k] = ncs[k], as->ng[k] = (int)m.w[k].size(), as->nslot[k] = nslot[k];
       as->rows.row_base[k] = rb, as->rows.nc[k] = ncs[k], as->rows.kb_base[k] = kb;
       rb += nslot[k] * ncs[k];
       kb += (long long)nslot[k] * ncs[k] * ncs[k];
@@ -399,21 +450,20 @@ extern "C" int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int order, int 
       as->lds[k] = base + (as->tl[k] ? tab : 0);
       if (as->lds[k] > GP_LDS_BUDGET) {
         delete as;
-        fh_set_error("fh_generic_assembler_create: shape %d does not fit the LDS of a workgroup", shapes[k]);
+        fh_set_error("fh_generic_assembler_create: shape %d does not fit the LDS of a workgroup", m.shapes[k]);
         return 2;
       }
     }
   }
-  for (int d = 0; d < ndof; d++) cnt[d + 1] += cnt[d];
   // slot of every element inside its shape, the compact dof tables, the adjacency (ids of element rows, ascending element order per dof)
   std::vector<int> ed[3], slot_elem[3];
   for (int k = 0; k < ns; k++) {
     ed[k].reserve((size_t)nslot[k] * ncs[k]);
     slot_elem[k].reserve(nslot[k]);
   }
-  std::vector<int> adj(cnt[ndof]), fill(cnt.begin(), cnt.end() - 1);
+  std::vector<int> adj(m.adj_ptr[ndof]), fill(m.adj_ptr.begin(), m.adj_ptr.end() - 1);
   for (int e = 0; e < nel; e++) {
-    const int k = eshape[e], s = (int)slot_elem[k].size();
+    const int k = m.eshape[e], s = (int)slot_elem[k].size();
     slot_elem[k].push_back(e);
     for (int n = 0; n < ncs[k]; n++) {
       const int d = elem_dof[(size_t)e * nloc + n];
@@ -434,14 +484,14 @@ extern "C" int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int order, int 
     if (h && bytes && hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st) != hipSuccess) bad = true;
     return d;
   };
-  as->d_adj_ptr = (int*)up(cnt.data(), cnt.size() * sizeof(int));
+  as->d_adj_ptr = (int*)up(m.adj_ptr.data(), m.adj_ptr.size() * sizeof(int));
   as->d_adj = (int*)up(adj.data(), adj.size() * sizeof(int));
   as->d_coords = (double*)up(coords, (size_t)nnode * dim * sizeof(double));
   for (int k = 0; k < ns; k++) {
     as->d_ed[k] = (int*)up(ed[k].data(), ed[k].size() * sizeof(int));
-    as->d_w[k] = (double*)up(w[k].data(), w[k].size() * sizeof(double));
-    as->d_phi[k] = (double*)up(phi[k].data(), phi[k].size() * sizeof(double));
-    as->d_dphi[k] = (double*)up(dphi[k].data(), dphi[k].size() * sizeof(double));
+    as->d_w[k] = (double*)up(m.w[k].data(), m.w[k].size() * sizeof(double));
+    as->d_phi[k] = (double*)up(m.phi[k].data(), m.phi[k].size() * sizeof(double));
+    as->d_dphi[k] = (double*)up(m.dphi[k].data(), m.dphi[k].size() * sizeof(double));
   }
   as->d_Kb = (double*)up(nullptr, (size_t)nent * sizeof(double));
   as->d_Fb = (double*)up(nullptr, (size_t)nrows * sizeof(double));
@@ -506,13 +556,10 @@ extern "C" int fh_generic_assembler_set_coords(fh_generic_assembler_t as, int nn
 
 // the source program into the object's buffer, when it is not the one already there
 static int gp_stage_program(fh_generic_assembler_t as, fh_expr_t source) {
-  int nv = 0, ncode = 0, nk = 0;
-  FH_TRY(fh_expr_nvars(source, &nv));
-  FH_REQUIRE(nv <= 4, "fh_generic_assembler_assemble: the source expression has %d variables, at most 4 (x, y, z, t) are served", nv);
-  FH_TRY(fh_expr_program(source, &ncode, &nk, nullptr, nullptr));
-  std::vector<int> code(ncode);
-  std::vector<double> consts(std::max(nk, 1), 0.0);
-  FH_TRY(fh_expr_program(source, &ncode, &nk, code.data(), consts.data()));
+  std::vector<int> code;
+  std::vector<double> consts;
+  FH_TRY(fh_expr_fetch(source, "fh_generic_assembler_assemble: the source expression", 4, code, consts));
+  if (consts.empty()) consts.resize(1, 0.0);
   if (as->have_prog && code == as->code && consts == as->consts) return 0;
   const size_t bytes = consts.size() * sizeof(double) + code.size() * sizeof(int);
   hipStream_t st = as->ctx->stream;
@@ -588,4 +635,172 @@ extern "C" int fh_generic_assembler_info(fh_generic_assembler_t as, int elems_pe
 extern "C" int fh_generic_assembler_destroy(fh_generic_assembler_t as) {
   gp_free(as);
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The one-shot calls.  Two passes: one WAVE per element forms the element matrix with gen_element_pass (node stride GEN_NC, Gauss chunk GEN_GC, static LDS)
+// into a buffer, with the place of every entry in the matrix beside it; one thread per ROW then adds the rows of its node's elements in ascending element order
+// (first version: the row thread formed them itself -- 80 ms per call on 54 k TET15 elements, host preparation included; 53 760 TET15 elements: 26 + 8.5 ms ->
+// 4.7 + 0.8 ms, profiles/r06_shipped_inputs_kernel_summary.md).  Repeated assemblies -- the application's linear iterations -- go through the resident object.
+// ------------------------------------------------------------------------------------------------------------------
+struct GenTab {              // the tables of one element shape: a mesh of mixed shapes (hexahedra, tetrahedra, prisms; quadrilaterals, triangles) names one per element
+  int nc, ng;
+  const double *w, *phi, *dphi;
+};
+struct GenTabs {
+  GenTab t[3];
+};
+// Row i of the element matrix goes to Kb[(e * ncmax + i) * ncmax + j], its residual entry to Fb[e * ncmax + i].
+__global__ __launch_bounds__(64) void k_poisson_pairs_generic(int nel, int ncmax, int dim, GenTabs tabs, const unsigned char* __restrict__ etab, int nloc,
+                                                              const int* __restrict__ elem_dof, const double* __restrict__ coords, const double* __restrict__ sol,
+                                                              double scale, const int* __restrict__ prog, int nprog, const double* __restrict__ pconst,
+                                                              const int* __restrict__ rowptr, const int* __restrict__ col, double* __restrict__ Kb,
+                                                              int* __restrict__ Pos, double* __restrict__ Fb) {
+  __shared__ double S[gp_elem_doubles(GEN_NC, GEN_GC)];
+  __shared__ int DOF[GEN_NC];
+  const int e = blockIdx.x, lane = threadIdx.x;
+  const GenTab& T = tabs.t[etab ? etab[e] : 0];
+  const int nc = T.nc;
+  const int* dof_row = elem_dof + (size_t)e * nloc;
+  if (lane < nc) DOF[lane] = dof_row[lane];
+  constexpr int NPL = gp_pairs_per_lane(64);
+  int pi[NPL], pj[NPL];
+  double acc[NPL], F;
+  gen_element_pass<64, NPL>(true, lane, nc, T.ng, GEN_GC, GEN_NC, dim, T.w, T.phi, T.dphi, dof_row, coords, sol, scale, prog, nprog, pconst, S, pi, pj, acc, F);
+  // the entry's place in the matrix beside its value (-1: the pattern does not hold it), so that the row pass adds without searching
+  double* out = Kb + (size_t)e * ncmax * ncmax;
+  int* pos = Pos + (size_t)e * ncmax * ncmax;
+  auto place = [&](int i, int j) {
+    const int r = DOF[i], c = DOF[j];
+    int at = -1;
+    for (int k = rowptr[r], re = rowptr[r + 1]; k < re; k++)
+      if (col[k] == c) {
+        at = k;
+        break;
+      }
+    return at;
+  };
+#pragma unroll
+  for (int k = 0; k < NPL; k++)
+    if (pi[k] >= 0) {
+      out[(size_t)pi[k] * ncmax + pj[k]] = acc[k];
+      pos[(size_t)pi[k] * ncmax + pj[k]] = place(pi[k], pj[k]);
+      if (pi[k] != pj[k]) {
+        out[(size_t)pj[k] * ncmax + pi[k]] = acc[k];
+        pos[(size_t)pj[k] * ncmax + pi[k]] = place(pj[k], pi[k]);
+      }
+    }
+  if (lane < nc) Fb[(size_t)e * ncmax + lane] = F;
+}
+
+// Second pass: one thread per row, its (element, local row) pairs in ascending element order -- the order of the reference's element loop --, every entry added
+// at the place the first pass found for it.
+__global__ __launch_bounds__(64) void k_poisson_rows_generic(int ndof, int ncmax, GenTabs tabs, const unsigned char* __restrict__ etab,
+                                                             const int* __restrict__ adj_ptr, const int* __restrict__ adj, const double* __restrict__ Kb,
+                                                             const int* __restrict__ Pos, const double* __restrict__ Fb, const int* __restrict__ rowptr,
+                                                             double* __restrict__ val, double* __restrict__ res) {
+  const int r = blockIdx.x * 64 + threadIdx.x;
+  if (r >= ndof) return;
+  const int rs = rowptr[r], re = rowptr[r + 1];
+  for (int k = rs; k < re; k++) val[k] = 0.0;
+  double racc = 0.0;
+  for (int a = adj_ptr[r]; a < adj_ptr[r + 1]; a++) {
+    const int e = adj[a] / GEN_NC, i = adj[a] % GEN_NC;
+    const int nc = tabs.t[etab ? etab[e] : 0].nc;
+    const size_t pr = (size_t)e * ncmax + i;
+    racc += Fb[pr];
+    const double* B = Kb + pr * ncmax;
+    const int* at = Pos + pr * ncmax;
+    for (int j = 0; j < nc; j++)
+      if (at[j] >= 0) val[at[j]] += B[j];
+  }
+  res[r] = racc;
+}
+
+// elem_geom as gen_mesh takes it.  Every check comes before the first allocation on the device.
+static int poisson_rows_impl(const char* who, fh_ctx_t ctx, const int* elem_geom, int geom, int fe, int order, int nel, int nloc, const int* elem_dof, int nnode,
+                             const double* coords, fh_vec_t sol, fh_expr_t source, double scale, fh_mat_t KK, fh_vec_t RES) {
+  FH_REQUIRE(ctx && elem_dof && coords && KK && RES && nel >= 1 && nnode >= 1, "%s: null or empty argument", who);
+  FH_REQUIRE(fe == fhfe::FE_LINEAR || fe == fhfe::FE_SERENDIPITY || fe == fhfe::FE_BIQUADRATIC, "%s: fe must be 0, 1 or 2", who);
+  const int ndof = KK->m;
+  FH_REQUIRE(KK->n == ndof && RES->n_local >= ndof && (!sol || sol->n_local >= ndof), "%s: size mismatch", who);
+  FH_REQUIRE((int64_t)nel * GEN_NC < 2147483647ll, "%s: too many elements", who);
+  GenMesh m;
+  FH_TRY(gen_mesh(who, fe, order, nel, nloc, elem_geom, geom, elem_dof, nnode, ndof, m));
+  const int ncmax = m.ncmax;
+  std::vector<int> adj(m.adj_ptr[ndof]), fill(m.adj_ptr.begin(), m.adj_ptr.end() - 1);
+  for (int e = 0; e < nel; e++)                         // ascending element order per dof; rows padded to GEN_NC
+    for (int n = 0; n < m.nc[m.eshape[e]]; n++) adj[fill[elem_dof[(size_t)e * nloc + n]]++] = e * GEN_NC + n;
+  std::vector<int> code;
+  std::vector<double> consts;
+  if (source) {
+    char subject[96];
+    snprintf(subject, sizeof subject, "%s: the source expression", who);
+    FH_TRY(fh_expr_fetch(source, subject, 4, code, consts));
+    if (consts.empty()) consts.resize(1);
+  }
+  hipStream_t st = ctx->stream;
+  std::vector<void*> dv;
+  bool oom = false;
+  auto up = [&](const void* h, size_t bytes) -> void* {
+    void* d = nullptr;
+    if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) {
+      oom = true;
+      return nullptr;
+    }
+    dv.push_back(d);
+    if (bytes && h) hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st);
+    return d;
+  };
+  int* d_ptr = (int*)up(m.adj_ptr.data(), m.adj_ptr.size() * sizeof(int));
+  int* d_adj = (int*)up(adj.data(), adj.size() * sizeof(int));
+  int* d_ed = (int*)up(elem_dof, (size_t)nel * nloc * sizeof(int));
+  double* d_x = (double*)up(coords, (size_t)nnode * m.dim * sizeof(double));
+  GenTabs tabs;
+  for (int k = 0; k < 3; k++) tabs.t[k] = GenTab{0, 0, nullptr, nullptr, nullptr};
+  for (int k = 0; k < m.ns; k++)
+    tabs.t[k] = GenTab{m.nc[k], (int)m.w[k].size(), (const double*)up(m.w[k].data(), m.w[k].size() * sizeof(double)),
+                       (const double*)up(m.phi[k].data(), m.phi[k].size() * sizeof(double)), (const double*)up(m.dphi[k].data(), m.dphi[k].size() * sizeof(double))};
+  unsigned char* d_etab = elem_geom ? (unsigned char*)up(m.eshape.data(), m.eshape.size()) : nullptr;
+  int* d_code = source ? (int*)up(code.data(), code.size() * sizeof(int)) : nullptr;
+  double* d_k = source ? (double*)up(consts.data(), consts.size() * sizeof(double)) : nullptr;
+  double* d_Kb = (double*)up(nullptr, (size_t)nel * ncmax * ncmax * sizeof(double));      // element rows between the two passes
+  double* d_Fb = (double*)up(nullptr, (size_t)nel * ncmax * sizeof(double));
+  int* d_Pos = (int*)up(nullptr, (size_t)nel * ncmax * ncmax * sizeof(int));
+  int rc = 0;
+  if (oom) {
+    fh_set_error("%s: out of device memory", who);
+    rc = 2;
+  } else {
+    hipLaunchKernelGGL(k_poisson_pairs_generic, dim3(nel), dim3(64), 0, st, nel, ncmax, m.dim, tabs, d_etab, nloc, d_ed, d_x,
+                       sol ? sol->d : nullptr, scale, d_code, (int)code.size(), d_k, KK->d_rowptr, KK->d_col, d_Kb, d_Pos, d_Fb);
+    hipLaunchKernelGGL(k_poisson_rows_generic, dim3(fh_div_up(ndof, 64)), dim3(64), 0, st, ndof, ncmax, tabs, d_etab, d_ptr, d_adj, d_Kb, d_Pos, d_Fb, KK->d_rowptr,
+                       KK->d_val, RES->d);
+    if (hipGetLastError() != hipSuccess) {
+      fh_set_error("%s: launch failed", who);
+      rc = 2;
+    }
+    fh_mat_values_written(KK);
+  }
+  hipStreamSynchronize(st);
+  for (void* q : dv) hipFree(q);
+  return rc;
+}
+
+extern "C" int fh_assemble_poisson_rows(fh_ctx_t ctx, int geom, int fe, int order, int nel, int nloc, const int* elem_dof, int nnode, const double* coords,
+                                        fh_vec_t sol, fh_expr_t source, double scale, fh_mat_t KK, fh_vec_t RES) {
+  FH_GUARD_BEGIN
+  return poisson_rows_impl("fh_assemble_poisson_rows", ctx, nullptr, geom, fe, order, nel, nloc, elem_dof, nnode, coords, sol, source, scale, KK, RES);
+  FH_GUARD_END("fh_assemble_poisson_rows")
+}
+
+// The same on a mesh of MIXED shapes (cube_all_shapes*.neu of applications/001_Poisson: hexahedra, tetrahedra and prisms in one file): elem_geom[nel] names the
+// shape of every element (at most three different ones, of one dimension); rows of elem_dof padded to nloc.  The entries of a row are summed in ascending element
+// order whatever the shapes, as the reference's element loop does.
+extern "C" int fh_assemble_poisson_mixed(fh_ctx_t ctx, int fe, int order, int nel, int nloc, const int* elem_geom, const int* elem_dof, int nnode, const double* coords,
+                                         fh_vec_t sol, fh_expr_t source, double scale, fh_mat_t KK, fh_vec_t RES) {
+  FH_GUARD_BEGIN
+  FH_REQUIRE(elem_geom, "fh_assemble_poisson_mixed: null or empty argument");
+  return poisson_rows_impl("fh_assemble_poisson_mixed", ctx, elem_geom, 0, fe, order, nel, nloc, elem_dof, nnode, coords, sol, source, scale, KK, RES);
+  FH_GUARD_END("fh_assemble_poisson_mixed")
 }

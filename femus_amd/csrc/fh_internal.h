@@ -65,6 +65,10 @@ static inline void fh_copy_out(T* dst, const std::vector<T>& v) {
   if (!v.empty()) std::copy(v.begin(), v.end(), dst);
 }
 
+// the device program of an expression into two host vectors, after refusing one over more than max_vars variables in the words
+// "<who> has %d variables, at most %d (x, y, z, t) are served" (fh_expr.cpp); consts is NOT padded: an upload of it wants at least one entry
+int fh_expr_fetch(fh_expr_t e, const char* who, int max_vars, std::vector<int>& code, std::vector<double>& consts);
+
 struct fh_ctx_s {
   int device = 0;
   hipStream_t stream = nullptr;       // compute stream

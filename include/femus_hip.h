@@ -416,7 +416,8 @@ int fh_assemble_advdiff_line(fh_ctx_t ctx, int fe, int gauss_order, int nel, con
  * (geom 3: TRI7 node order of 2d/Triangle.cpp: vertices, edge middles, centre) first: elem_dof[nel*nloc] in the family's local order with the node classes
  * numbered one after the other (a node id is its dof id), coords[nnode*dim].  KK and RES are OVERWRITTEN: KK_ij = sum grad phi_i . grad phi_j w,
  * RES_i = sum (scale f phi_i - grad phi_i . grad Sol) w.  Element matrices first (one wave per element, the entries' places in KK beside them), then one thread per row adding them in
- * ascending element order; geom 0 .. 2 are served too (a cross-check of the
+ * ascending element order (fh_generic.hip, where the kernels share their element body with the resident object below); every check runs before the first
+ * allocation on the device; geom 0 .. 2 are served too (a cross-check of the
  * tensor-product assemblers on small meshes). */
 int fh_assemble_poisson_rows(fh_ctx_t ctx, int geom, int fe, int gauss_order, int nel, int nloc, const int* elem_dof, int nnode, const double* coords, fh_vec_t sol,
                              fh_expr_t source, double scale, fh_mat_t KK, fh_vec_t RES);
