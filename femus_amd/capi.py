@@ -1379,6 +1379,17 @@ class Multigrid:
             self.h = None
 
 
+def coarse_dissection(rowptr, col, coords, coarse_nd):
+    """(order, offsets) of the nested dissection the exact coarse solve makes of a CSR pattern with coordinates (host only, fh_coarse_dissection):
+    order = [block 0 | ... | block k-1 | separator], offsets[i] = start of block i, offsets[k] = start of the separator, offsets[k + 1] = n"""
+    L = load_library()
+    rowptr, col, xy = _i32(rowptr), _i32(col), _f64(coords)
+    n, dim = rowptr.size - 1, xy.shape[1] if xy.ndim == 2 else 1
+    order, off, noff = np.empty(n, np.int32), np.empty(min(max(int(coarse_nd), 1), max(n, 1)) + 2, np.int32), ctypes.c_int()
+    _chk(L.fh_coarse_dissection(n, _p(rowptr), _p(col), dim, _p(xy), int(coarse_nd), _p(order), _p(off), ctypes.byref(noff)))
+    return order, off[:noff.value].copy()
+
+
 def version():
     return load_library().fh_version().decode()
 

@@ -13,7 +13,7 @@
 //     struct(t) = (adj(S_t) u struct(children)) \ subtree(t).
 //   numeric (device, every factorisation; nodes of equal height in the tree batched into the same launches)
 //     D_t = A[S,S] + children's updates, E_t = A[S,B] + ..., U_t = children's updates on [B,B]      (assembly by index maps, extend-add)
-//     D_t <- D_t^-1 (the batched symmetric 128-block inverse of fh_mg.hip), W_t = D_t^-1 E_t, U_t <- U_t - E_t^T W_t   (FP64 matrix cores)
+//     D_t <- D_t^-1 (the batched symmetric 128-block inverse of fh_coarse.hip), W_t = D_t^-1 E_t, U_t <- U_t - E_t^T W_t   (FP64 matrix cores)
 //   solve (device, graph-capturable: fixed launch sequence and buffers), front vectors y_t = [r_t ; u_t] flow up the tree as the matrices did
 //     up:    y_t = [b[S_t] ; 0] + children's u (gather, fixed order: deterministic) ; z_t = D_t^-1 r_t ; u_t -= W_t^T r_t
 //     down:  x[S_t] = z_t - W_t x[B_t]
@@ -24,7 +24,7 @@
 // Navier-Stokes Jacobian): the same tree on the symmetrised pattern, fronts [D E; F U] with D^-1 by blocked Gauss-Jordan with partial pivoting inside
 // the front and static perturbation of pivots that stay tiny (k_gi_*), W = D^-1 E, V = (F D^-1)^T, U -= F W; up sweep z = D^-1 r, u -= V^T r; steps of
 // iterative refinement behind a perturbed factorisation.  A symmetric operator whose unpivoted fronts break down is factored again on this path.
-#include "fh_internal.h"
+#include "fh_coarse.h"
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(256) void k_dd_extend_add(const EaDesc* __restrict_
 }
 
 // C (M x N, ldc) += alpha P^T Q with P (K x M, ldp), Q (K x N, ldq), all row-major: 64 x 64 tile per workgroup on v_mfma_f64_16x16x4 (operand
-// staging k-major with row stride 80 doubles: conflict-free fragment reads; fragments as in k_gjb_update_mfma of fh_mg.hip)
+// staging k-major with row stride 80 doubles: conflict-free fragment reads; fragments as in k_gjb_update_mfma of fh_coarse.hip)
 struct GemmDesc {
   const double *P, *Q;
   double* C;
@@ -356,7 +356,7 @@ __global__ __launch_bounds__(256) void k_dd_mirror_diag(const GemmDesc* __restri
 // block): threshold pivoting inside the front; a pivot that stays below `tiny` = sqrt(eps) of the front's largest entry is replaced by +-tiny (static
 // perturbation, counted in flag[2]; fh_direct_solve then adds steps of iterative refinement).  Per block step of 32 columns, batched over the fronts of one
 // tree height (blockIdx.z / blockIdx.y = front): (1) LU with partial pivoting of the column panel below the diagonal -> the 32 pivot rows, (2) whole-row
-// interchanges, (3) the block Gauss-Jordan step of fh_mg.hip's general sweep (pivot block inverted in LDS, row panel, rank-32 update on the matrix cores,
+// interchanges, (3) the block Gauss-Jordan step of fh_coarse.hip's general sweep (pivot block inverted in LDS, row panel, rank-32 update on the matrix cores,
 // column panel).  At the end X = (P D)^-1 and D^-1 = X P: the columns of X scattered by the row permutation.
 constexpr int GI_NB = 32;
 constexpr double GI_TINY = 1.5e-8;       // sqrt(machine epsilon): a pivot below GI_TINY x (largest entry of the front) is replaced (MUMPS / SuperLU_DIST static pivoting)

@@ -192,17 +192,6 @@ struct fh_mat_s {
   void (*plan_destroy)(void*) = nullptr;
 };
 
-// descriptor of one dense symmetric matrix of the batched 128-block inverse (fh_mg.hip: k_inv_*_b; fh_inv_sym_batched)
-struct InvDesc {
-  double* D;             // n x n, leading dimension n; replaced by its inverse
-  int n;
-  double *PT, *RT, *Dv0, *Dv1;   // work: panels 2 x (n x 128), pivot-block inverses 2 x 2 x 128 x 128 (fh_inv_work_doubles(n) doubles from PT)
-  int* flg;              // two ints; flg[1] != 0: a pivot block had no usable diagonal pivot
-  int off;               // first unknown of the block in the dissected ordering (k_nd_w)
-};
-size_t fh_inv_work_doubles(int n);
-int fh_inv_sym_batched(fh_ctx_t c, const InvDesc* d_desc, int k, int nmax);
-
 // every writer of a matrix's values ends here (the Dirichlet-row replacement, fh_mat_zero_rows*, calls fh_mat_rows_replaced instead): one place, so that a new
 // writer cannot tell one kind of derived state and forget the other
 static inline void fh_mat_values_written(fh_mat_t A) {

@@ -595,6 +595,11 @@ int fh_mg_set_level_coords(fh_mg_t mg, int level, int dim, int n, const double* 
 /* what the last fh_mg_setup made of the coarsest level: unknowns in the dense problem (the others are solved by their diagonal), interior
  * blocks of the dissection (0 = one dense inverse), separator size, largest block; any pointer may be NULL */
 int fh_mg_coarse_info(fh_mg_t mg, int* n_dense, int* nd_blocks, int* nd_separator, int* nd_largest_block);
+/* diagnostic, host only (no device): the ordering [interior block 0 | ... | interior block k-1 | separator] that the dissection of option "coarse_nd"
+ * gives the n unknowns of a CSR pattern with coordinates coords[n * dim], dim 1..3.  order[n]; offsets[0 .. k + 1] with offsets[k] = first separator
+ * unknown and offsets[k + 1] = n, room for max(coarse_nd, 1) + 2 ints (k does not exceed max(n, 1) either); *n_offsets = k + 2.  Nothing to cut (coarse_nd < 2, fewer than 64 unknowns):
+ * one block, no separator, the identity order */
+int fh_coarse_dissection(int n, const int* rowptr, const int* col, int dim, const double* coords, int coarse_nd, int* order, int* offsets, int* n_offsets);
 int fh_mg_vcycle(fh_mg_t mg, fh_vec_t b, fh_vec_t x);
 int fh_mg_solve(fh_mg_t mg, fh_vec_t b, fh_vec_t x, int outer, double rtol, double atol, double dtol, int maxit, int restart,
                 int* iterations, double* final_residual);

@@ -777,7 +777,8 @@ def test_dissection_cuts_a_q2_block_at_element_planes(ctx):
 
 def test_dissected_coarse_solve_falls_back(ctx):
     """symmetric but indefinite (no usable unpivoted pivot in a block) and unsymmetric operators with coordinates set: the one dense inverse
-    with its pivoted fall-back serves them, the solution is still exact"""
+    with its pivoted fall-back serves them, the solution is still exact -- with the symmetry verdict taken along by the coupling pass
+    (coarse_reduce 1) and by the dense inverse's own test (coarse_reduce 0)"""
     rng = np.random.default_rng(3)
     n = 160
     xy = rng.uniform(0, 1, (n, 3))
@@ -785,17 +786,20 @@ def test_dissected_coarse_solve_falls_back(ctx):
     for k in range(0, n, 2):
         M[k, k + 1] = M[k + 1, k] = 1.0 + 0.1 * rng.uniform()
     C = 0.05 * rng.uniform(-1, 1, (n, n))
-    for name, Mk in (("indefinite", M + C + C.T), ("unsymmetric", M + C + 2.0 * np.eye(n))):
-        ctx.set_option("coarse_nd_min", 16)
-        mg, A = _one_level(ctx, Mk)
-        mg.set_coarse_coords(xy)
-        mg.setup()
-        assert mg.coarse_info()[1] == 0, name
-        rhs = rng.uniform(-1, 1, n)
-        b, x = ctx.vector_from(rhs), ctx.vector(n)
-        mg.vcycle(b, x)
-        assert rel(x.to_numpy(), np.linalg.solve(Mk, rhs)) < 1e-10, name
-        mg.destroy()
+    for reduce in (1, 0):
+        ctx.set_option("coarse_reduce", reduce)
+        for name, Mk in (("indefinite", M + C + C.T), ("unsymmetric", M + C + 2.0 * np.eye(n))):
+            ctx.set_option("coarse_nd_min", 16)
+            mg, A = _one_level(ctx, Mk)
+            mg.set_coarse_coords(xy)
+            mg.setup()
+            assert mg.coarse_info()[1] == 0, (name, reduce)
+            rhs = rng.uniform(-1, 1, n)
+            b, x = ctx.vector_from(rhs), ctx.vector(n)
+            mg.vcycle(b, x)
+            assert rel(x.to_numpy(), np.linalg.solve(Mk, rhs)) < 1e-10, (name, reduce)
+            mg.destroy()
+    ctx.set_option("coarse_reduce", 1)
     ctx.set_option("coarse_nd_min", 1024)
 
 
