@@ -236,25 +236,42 @@ class Poisson001:
             return None
         return seen.pop() if seen in ({"tet"}, {"wedge"}) else "mixed"
 
-    def run_elements(self, log=None, smoother=capi.SMOOTH_GS_COLOR, omega=1.0):
+    def run_elements(self, log=None, smoother=capi.SMOOTH_GS_COLOR, omega=1.0, transfers="device"):
         """LinearImplicitSystem::MGsolve on the meshes femus_amd/mixed_mesh.py builds, in all three Lagrange families: the TRI6 box (TRI7 inside; the box's
         boundary conditions and source), Gambit files of TET10 (input3D_Tet_*.json with input/cube_Tet.neu; TET15 inside), of WEDGE18 (input3D_Wedge_*.json with
         input/cube_Wedge.neu; WEDGE21 inside), of mixed shapes (input3D.json / input3D_All_first.json with input/cube_all_shapes_Six_boundary_groups.neu:
         tetrahedra, prisms and hexahedra) and the two-dimensional files of QUAD9 and / or TRI6 (the boundary conditions of the application's SetBoundaryCondition:
         Dirichlet 0, flux 0.2 on face name 3).  The Poisson callback through the generic kernel on the finest level (fh_assemble_poisson_rows for the box and
         the tetrahedral / prism files, fh_assemble_poisson_mixed on the mixed path, elem_dof rows padded with -1), transfers from the element prolongators,
-        Galerkin operators below.
+        Galerkin operators below.  transfers: "device" builds every level's PP and Dirichlet list from the resident meshes (capi.ElementMesh.prolongator /
+        boundary_dofs), "host" with _prolongator_from_children and the face loop below -- the same bits.
         result["levels"]: (ed, xs, ff) of every level; ed and ff as wide as the shape, or padded to 27 and 6 on the mixed path"""
         from . import mixed_mesh
         ctx = self.ctx
         levels = [mixed_mesh.tri_box(self.box[0], self.box[1], self.lo[:2], self.hi[:2]) if self.box is not None else mixed_mesh.read_gambit(self.mesh_file)]
-        # level 0 goes up once and is refined on the device (capi.ElementMesh: the arrays of mixed_mesh.refine, integer for integer and bit for bit); every
-        # level comes down once for the host-side Dirichlet lists and transfers below
+        if transfers not in ("device", "host"):
+            raise ValueError("transfers must be \"device\" or \"host\", not %r" % (transfers,))
+        fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
+        # level 0 goes up once and is refined on the device (capi.ElementMesh: the arrays of mixed_mesh.refine, integer for integer and bit for bit); the
+        # transfers and the Dirichlet lists are built from the resident meshes; every level comes down once for result["levels"], the flux faces and the top
+        # level's boundary values
         resident = [capi.ElementMesh.from_arrays(ctx, *levels[0])]
+        P_dev, bdc_dev = [None], []
         try:
             for _ in range(1, self.nlevels):
                 resident.append(resident[-1].refine())
                 levels.append(resident[-1].arrays())
+            if transfers == "device":
+                # the flags a mesh carries are those of level 0: a child face inherits its father's
+                dirichlet = sorted({int(f) for f in np.unique(levels[0][3]) if f < -1 and self.face_bc(int(f))[0] == "dirichlet"})
+                for l, m in enumerate(resident):
+                    bdc_dev.append(m.boundary_dofs(fam, dirichlet))
+                    if l:
+                        P_dev.append(resident[l - 1].prolongator(m, fam))
+        except BaseException:
+            for p in P_dev[1:]:
+                p.destroy()
+            raise
         finally:
             for m in resident:
                 m.destroy()
@@ -263,7 +280,6 @@ class Poisson001:
             levels = [(kind, ed[:, :mixed_mesh.NLOC[g]], xs, ff[:, :mixed_mesh.NFACES[g]], own) for kind, ed, xs, ff, own in levels]
         shapes = sorted(set(levels[0][0].tolist()))
         dim = levels[0][2].shape[1]
-        fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
         fn_by = {s: [capi.fe_face_nodes(s, self.fe, f) for f in range(mixed_mesh.NFACES[s])] for s in shapes}
         groups = [[(s, np.nonzero(lv[0] == s)[0], mixed_mesh.CLASSES[s][fam]) for s in shapes] for lv in levels]     # (shape, its elements, dofs per element)
         ndofs = [lv[4][fam] for lv in levels]
@@ -276,6 +292,9 @@ class Poisson001:
         bdc = []
         flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals = [], [], [], [], []
         for l, (kl, edl, xl, ffl, _) in enumerate(levels):
+            if transfers == "device" and l != top:                  # the list is there; values and flux faces belong to the top level alone
+                bdc.append(bdc_dev[l])
+                continue
             val = {}
             for iel, f in zip(*np.nonzero(ffl < -1)):               # elements and faces in order; a later face overwrites an earlier one (GenerateBdc)
                 flag = int(ffl[iel, f])
@@ -296,10 +315,11 @@ class Poisson001:
                         tau_faces.append(nodes)
                         tau_vals.append(self.file_flux[flag])
             idx = np.array(sorted(val), dtype=np.int32)
-            bdc.append(idx)
+            bdc.append(bdc_dev[l] if transfers == "device" else idx)
             if l == top:
                 sol0[idx] = [val[i] for i in idx]
-        P = [None] + [self._prolongator_from_children(groups[l - 1], levels[l - 1][1], levels[l][1], ndofs[l - 1], ndofs[l]) for l in range(1, self.nlevels)]
+        P = P_dev if transfers == "device" else [None] + [self._prolongator_from_children(groups[l - 1], levels[l - 1][1], levels[l][1], ndofs[l - 1], ndofs[l])
+                                                          for l in range(1, self.nlevels)]
         SOL.upload(sol0)
 
         # the plan of the element loop, made once: every linear iteration assembles on the same mesh and pattern

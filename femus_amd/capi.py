@@ -778,6 +778,24 @@ class ElementMesh:
         _chk(self.L.fh_elem_mesh_get(self.h, _p(code), _p(ed), _p(xs), _p(ff)))
         return self._NAMES[code], ed.astype(np.int64), xs, ff.astype(np.int64), list(self.own)
 
+    def prolongator(self, fine, fe):
+        """PP into `fine`, the refinement of this mesh, for a family of FE (fh_elem_mesh_prolongator): a resident Mat of fine.own[fe] rows and own[fe] columns,
+        the bits of app_poisson._prolongator_from_children"""
+        h = ctypes.c_void_p()
+        _chk(self.L.fh_elem_mesh_prolongator(self.h, fine.h, FE[fe] if isinstance(fe, str) else int(fe), ctypes.byref(h)))
+        return Mat(self.ctx, h)
+
+    def boundary_dofs(self, fe, flags):
+        """the ascending dofs of a family that lie on a face whose flag is one of `flags` (fh_elem_mesh_boundary_dofs), int32"""
+        k = FE[fe] if isinstance(fe, str) else int(fe)
+        fl = _i32(np.asarray(list(flags), dtype=np.int64).reshape(-1))
+        n = ctypes.c_int(0)
+        _chk(self.L.fh_elem_mesh_boundary_dofs(self.h, k, int(fl.size), _p(fl) if fl.size else None, ctypes.byref(n), None))
+        out = np.empty(n.value, np.int32)
+        if n.value:
+            _chk(self.L.fh_elem_mesh_boundary_dofs(self.h, k, int(fl.size), _p(fl), ctypes.byref(n), _p(out)))
+        return out
+
     def destroy(self):
         if self.h:
             _chk(self.L.fh_elem_mesh_destroy(self.h))

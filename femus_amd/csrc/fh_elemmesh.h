@@ -1,0 +1,40 @@
+// The device-resident element mesh (fh_elemmesh.hip): what the builders of its transfers and boundary lists (fh_elemtransfer.hip) see of it.
+#pragma once
+#include "fh_internal.h"
+#include <memory>
+
+constexpr int EM_W = 27, EM_F = 6, EM_G = 6;      // widths of the padded element and face rows; shape codes 0 .. 5 (2 = line: not a mesh shape here)
+
+struct EmTab {                    // per shape code; lives in device memory
+  int nv[EM_G], ne[EM_G], nl[EM_G], nf[EM_G], ep[EM_G];     // ends of the vertex / edge-node / all classes, faces, first double of the shape's prolongator
+  signed char f2c[EM_G][8][8];            // [child][child vertex] -> father's local node
+  signed char edge_v[EM_G][12][2];        // the two vertices of edge node nv + m
+  signed char face_of[EM_G][EM_W];        // local node -> the face it is the last node of (-1: none)
+  signed char nvf[EM_G][EM_F];            // vertices per face
+  signed char face_v[EM_G][EM_F][4];
+  signed char face_diag[EM_G][EM_F][4];   // quadrilateral faces: position of the vertex diagonal to vertex k
+  signed char cff[EM_G][8][EM_F];         // [child][child face] -> father's face whose flag it inherits (-1: none)
+};
+struct EmDevTables {
+  EmTab* d_tab = nullptr;
+  double* d_EP = nullptr;
+  ~EmDevTables() {
+    if (d_tab) hipFree(d_tab);
+    if (d_EP) hipFree(d_EP);
+  }
+};
+
+struct fh_elem_mesh_s {
+  fh_ctx_t ctx = nullptr;
+  int dim = 0, nel = 0, nnode = 0, own[3] = {0, 0, 0}, level = 0;
+  int64_t count[EM_G] = {0, 0, 0, 0, 0, 0};      // elements per shape: sizes every allocation of a refinement without asking the device
+  int* d_geom = nullptr;          // [nel]
+  int* d_ed = nullptr;            // [nel * 27], -1 beyond the shape's width
+  double* d_x = nullptr;          // [nnode * dim]
+  int* d_ff = nullptr;            // [nel * 6], -1 beyond the shape's faces
+  std::shared_ptr<EmDevTables> tab;               // shared along a chain of refinements
+  ~fh_elem_mesh_s() {
+    for (void* q : {(void*)d_geom, (void*)d_ed, (void*)d_x, (void*)d_ff})
+      if (q) hipFree(q);
+  }
+};

@@ -18,42 +18,21 @@
 //      product and every sum rounded on its own (mixed_mesh.py: refine; NOT the ascending-node-id order of the hex path).  The first touch is the child the
 //      host's first_touch calls the creator: the smallest fine element that holds the key.
 // Slot numbers depend on the race; ids, flags and coordinates do not.
-#include "fh_internal.h"
+#include "fh_elemmesh.h"
 #include "fh_fe.h"
 #include <cmath>
-#include <memory>
 #include <mutex>
 
 namespace {
-constexpr int EM_W = 27, EM_F = 6, EM_G = 6;      // widths of the padded element and face rows; shape codes 0 .. 5 (2 = line: not a mesh shape here)
 constexpr unsigned long long EM_EMPTY = ~0ull;
 constexpr int EM_NONE = 0x7f7f7f7f;
 
-struct EmTab {                    // per shape code; lives in device memory
-  int nv[EM_G], ne[EM_G], nl[EM_G], nf[EM_G], ep[EM_G];     // ends of the vertex / edge-node / all classes, faces, first double of the shape's prolongator
-  signed char f2c[EM_G][8][8];            // [child][child vertex] -> father's local node
-  signed char edge_v[EM_G][12][2];        // the two vertices of edge node nv + m
-  signed char face_of[EM_G][EM_W];        // local node -> the face it is the last node of (-1: none)
-  signed char nvf[EM_G][EM_F];            // vertices per face
-  signed char face_v[EM_G][EM_F][4];
-  signed char face_diag[EM_G][EM_F][4];   // quadrilateral faces: position of the vertex diagonal to vertex k
-  signed char cff[EM_G][8][EM_F];         // [child][child face] -> father's face whose flag it inherits (-1: none)
-};
 struct EmTables {
   EmTab h;
   std::vector<double> EP;         // every shape's [nch][nl][nl], one after the other
   bool ok = false;
   std::string why;
 };
-struct EmDevTables {
-  EmTab* d_tab = nullptr;
-  double* d_EP = nullptr;
-  ~EmDevTables() {
-    if (d_tab) hipFree(d_tab);
-    if (d_EP) hipFree(d_EP);
-  }
-};
-
 bool em_shape(int g) { return g == fhfe::GEOM_HEX || g == fhfe::GEOM_QUAD || g == fhfe::GEOM_TRI || g == fhfe::GEOM_TET || g == fhfe::GEOM_WEDGE; }
 
 // the tables of mixed_mesh.py: tables, from the same sources
@@ -171,21 +150,6 @@ struct Scratch {
   }
 };
 }   // namespace
-
-struct fh_elem_mesh_s {
-  fh_ctx_t ctx = nullptr;
-  int dim = 0, nel = 0, nnode = 0, own[3] = {0, 0, 0}, level = 0;
-  int64_t count[EM_G] = {0, 0, 0, 0, 0, 0};      // elements per shape: sizes every allocation of a refinement without asking the device
-  int* d_geom = nullptr;          // [nel]
-  int* d_ed = nullptr;            // [nel * 27], -1 beyond the shape's width
-  double* d_x = nullptr;          // [nnode * dim]
-  int* d_ff = nullptr;            // [nel * 6], -1 beyond the shape's faces
-  std::shared_ptr<EmDevTables> tab;               // shared along a chain of refinements
-  ~fh_elem_mesh_s() {
-    for (void* q : {(void*)d_geom, (void*)d_ed, (void*)d_x, (void*)d_ff})
-      if (q) hipFree(q);
-  }
-};
 
 // ---- kernels: one thread per (fine element, column of the padded row) ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_em_widths(const EmTab* __restrict__ T, int nel, const int* __restrict__ geom, int* __restrict__ w0, int* __restrict__ w1,

@@ -95,6 +95,8 @@ struct fh_ctx_s {
   int assemble_sf = 8;               // HEX27/Q2, 64 Gauss points, tensor-product tables: element matrices by sum factorisation on the vector ALU, value = waves per workgroup (0 = off: matrix-core kernel)
   int assemble_sumfac = 1;           // matrix-core element kernel: map Jacobian by sum factorisation (tensor-product tables)
   int assemble_rows2 = 1;            // row pass: two rows per 32-lane group when no row has more than 128 entries
+  int elem_transfer_lds_rows = 1024;  // transfers of element meshes (fh_elemtransfer.hip): a row whose elements hold at most this many candidate slots (27 per element) is
+                                     // sorted by one wave in LDS, any other by a workgroup in global scratch; same bits (1024 at most; lowered by the A/B of the bitwise test)
   int generic_pack = 1;              // generic assembler object (fh_generic.hip): 2 / 4 elements per wave for the narrow families; 0 = one element per wave for every shape (the A/B of the probe), read at create
   int assemble_kpad = 1;            // HEX27/Q2 two-pass assembly: element rows padded to 32 doubles (whole 64-byte lines per row)
   int assemble_sym = 1;              // symmetric-tile HEX27/Q2 element kernel (2 elements per wave)
@@ -205,6 +207,17 @@ fh_mat_t fh_mat_alive(uint64_t uid);
 // host copy of the column indices: matrices whose pattern was built on the device (fh_mat_create_from_elements) fetch it at the first host use
 int fh_mat_fetch_host_cols(fh_mat_t A);
 int fh_mat_alloc_device_pattern(fh_ctx_t c, int m, int n, std::vector<int>&& rp, fh_mat_t* out);   // columns left to the caller's kernels
+// dof -> the elements that hold it, by a counting pass on the device (fh_mat.hip; the pattern of fh_mat_create_from_elements and the transfers of
+// fh_elemtransfer.hip): d_ed[ne] a table of dofs in device memory, entry k belongs to element k / div (div = 1: the lists name the entries themselves);
+// lists are kept for the dofs < m, an entry outside [0, ncols) is refused in the words "<who>: a dof of an element is out of range" -- except, with
+// padded, the -1 beyond a row's width.  ptr is scanned on the host (d_ptr = its copy); the ORDER inside a list depends on the race between the threads.
+// The fill runs on the context's stream when build returns; the buffers are freed with the object, after the caller has synchronised the stream.
+struct fh_dof_lists {
+  std::vector<int> ptr;           // [m + 1]
+  int *d_ptr = nullptr, *d_adj = nullptr, *d_cur = nullptr, *d_err = nullptr;     // d_err: one int, zero after a good build (free for the caller's kernels)
+  ~fh_dof_lists();
+};
+int fh_dof_lists_build(fh_ctx_t c, const char* who, size_t ne, int div, const int* d_ed, int m, int ncols, bool padded, fh_dof_lists* L);
 static inline const std::vector<int>& fh_hcol(fh_mat_t A) {
   if (A->h_col.size() != (size_t)A->nnz) fh_mat_fetch_host_cols(A);
   return A->h_col;

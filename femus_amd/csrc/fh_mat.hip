@@ -125,18 +125,54 @@ int fh_mat_alloc_device_pattern(fh_ctx_t c, int m, int n, std::vector<int>&& rp,
 // the column array never visits it unless host code asks (fh_hcol).  Same pattern as fh_pattern_from_elements (sorted, unique).
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int PE_CAP = 1024;
-__global__ __launch_bounds__(256) void k_pe_count(size_t n, const int* __restrict__ elem_dof, int m, int ncols, int* __restrict__ cnt, int* __restrict__ err) {
+// pad: an entry of -1 (the padding of a table whose rows have several widths) is skipped, not refused
+__global__ __launch_bounds__(256) void k_pe_count(size_t n, const int* __restrict__ elem_dof, int m, int ncols, int pad, int* __restrict__ cnt, int* __restrict__ err) {
   const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (k >= n) return;
   const int d = elem_dof[k];
+  if (d == -1 && pad) return;
   if (d < 0 || d >= ncols) { atomicExch(err, 1); return; }
   if (d < m) atomicAdd(&cnt[d], 1);
 }
-__global__ __launch_bounds__(256) void k_pe_fill(size_t n, int nloc, const int* __restrict__ elem_dof, int m, int* __restrict__ cur, int* __restrict__ adj) {
+// div = nloc: the list of a dof names the elements that hold it; div = 1: the entries of the table (element * nloc + local node)
+__global__ __launch_bounds__(256) void k_pe_fill(size_t n, int div, const int* __restrict__ elem_dof, int m, int* __restrict__ cur, int* __restrict__ adj) {
   const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (k >= n) return;
   const int d = elem_dof[k];
-  if (d >= 0 && d < m) adj[atomicAdd(&cur[d], 1)] = (int)(k / nloc);
+  if (d >= 0 && d < m) adj[atomicAdd(&cur[d], 1)] = (int)(k / div);
+}
+
+fh_dof_lists::~fh_dof_lists() {
+  for (int* p : {d_ptr, d_adj, d_cur, d_err})
+    if (p) hipFree(p);
+}
+
+// the counting pass: dof -> the elements (or table entries) that hold it, for the dofs < m.  The order inside a list depends on the race between the threads.
+int fh_dof_lists_build(fh_ctx_t c, const char* who, size_t ne, int div, const int* d_ed, int m, int ncols, bool padded, fh_dof_lists* L) {
+  FH_CHECK_HIP(hipMalloc(&L->d_cur, ((size_t)m + 2) * sizeof(int)));
+  FH_CHECK_HIP(hipMalloc(&L->d_err, sizeof(int)));
+  FH_CHECK_HIP(hipMemsetAsync(L->d_cur, 0, ((size_t)m + 2) * sizeof(int), c->stream));
+  FH_CHECK_HIP(hipMemsetAsync(L->d_err, 0, sizeof(int), c->stream));
+  const unsigned gb = (unsigned)((ne + 255) / 256);
+  if (ne) hipLaunchKernelGGL(k_pe_count, dim3(gb), dim3(256), 0, c->stream, ne, d_ed, m, ncols, padded ? 1 : 0, L->d_cur, L->d_err);
+  L->ptr.assign((size_t)m + 1, 0);
+  if (m) FH_CHECK_HIP(hipMemcpyAsync(L->ptr.data() + 1, L->d_cur, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  int err = 0;
+  FH_CHECK_HIP(hipMemcpyAsync(&err, L->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  FH_CHECK_HIP(hipStreamSynchronize(c->stream));
+  FH_REQUIRE(!err, "%s: a dof of an element is out of range", who);
+  int64_t tot = 0;
+  for (int r = 0; r < m; r++) {
+    tot += L->ptr[r + 1];
+    L->ptr[r + 1] = (int)tot;
+  }
+  FH_REQUIRE(tot < 2147483647ll, "%s: adjacency overflows int32", who);
+  FH_CHECK_HIP(hipMalloc(&L->d_ptr, ((size_t)m + 1) * sizeof(int)));
+  FH_CHECK_HIP(hipMalloc(&L->d_adj, std::max<size_t>((size_t)tot, 1) * sizeof(int)));
+  FH_CHECK_HIP(hipMemcpyAsync(L->d_ptr, L->ptr.data(), ((size_t)m + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  FH_CHECK_HIP(hipMemcpyAsync(L->d_cur, L->ptr.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));        // cursors
+  if (ne) hipLaunchKernelGGL(k_pe_fill, dim3(gb), dim3(256), 0, c->stream, ne, div, d_ed, m, L->d_cur, L->d_adj);
+  return 0;
 }
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_pe_rows(int m, const int* __restrict__ aptr, const int* __restrict__ adj, const int* __restrict__ elem_dof, int nloc,
@@ -195,9 +231,9 @@ static int mat_create_from_elements_impl(fh_ctx_t c, int nel, int nloc, const in
   FH_GUARD_BEGIN
   FH_REQUIRE(c && out && nel >= 0 && nloc > 0 && m >= 0 && n >= m && (elem_dof || dev_elem_dof || nel == 0), "fh_mat_create_from_elements: bad arguments");
   const size_t ne = (size_t)nel * nloc;
-  int *d_ed = nullptr, *d_ed_own = nullptr, *d_cnt = nullptr, *d_adj = nullptr, *d_err = nullptr, *d_len = nullptr;
+  int *d_ed = nullptr, *d_ed_own = nullptr, *d_len = nullptr;
   auto cleanup = [&]() {
-    for (int* p : {d_ed_own, d_cnt, d_adj, d_err, d_len})
+    for (int* p : {d_ed_own, d_len})
       if (p) hipFree(p);
   };
   std::vector<int> fetched;        // host copy of a device-only table, made only if the host builder has to serve a row
@@ -207,36 +243,18 @@ static int mat_create_from_elements_impl(fh_ctx_t c, int nel, int nloc, const in
     FH_CHECK_HIP(hipMalloc(&d_ed_own, std::max<size_t>(ne, 1) * sizeof(int)));
     d_ed = d_ed_own;
   }
-  FH_CHECK_HIP(hipMalloc(&d_cnt, ((size_t)m + 2) * sizeof(int)));
-  FH_CHECK_HIP(hipMalloc(&d_err, sizeof(int)));
   FH_CHECK_HIP(hipMalloc(&d_len, ((size_t)m + 1) * sizeof(int)));
   if (ne && !dev_elem_dof) FH_CHECK_HIP(hipMemcpyAsync(d_ed, elem_dof, ne * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  FH_CHECK_HIP(hipMemsetAsync(d_cnt, 0, ((size_t)m + 2) * sizeof(int), c->stream));
-  FH_CHECK_HIP(hipMemsetAsync(d_err, 0, sizeof(int), c->stream));
-  const unsigned gb = (unsigned)((ne + 255) / 256);
-  if (ne) hipLaunchKernelGGL(k_pe_count, dim3(gb), dim3(256), 0, c->stream, ne, d_ed, m, n, d_cnt, d_err);
-  std::vector<int> aptr((size_t)m + 1, 0);
-  if (m) FH_CHECK_HIP(hipMemcpyAsync(aptr.data() + 1, d_cnt, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  int err = 0;
-  FH_CHECK_HIP(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  FH_CHECK_HIP(hipStreamSynchronize(c->stream));
-  if (err) {
+  fh_dof_lists L;                  // freed on return; every path below synchronises the stream first
+  if (int rc = fh_dof_lists_build(c, "fh_mat_create_from_elements", ne, nloc, d_ed, m, n, false, &L)) {
+    hipStreamSynchronize(c->stream);
     cleanup();
-    fh_set_error("fh_mat_create_from_elements: a dof of an element is out of range");
-    return 2;
+    return rc;
   }
-  int64_t tot = 0;
-  for (int r = 0; r < m; r++) {
-    tot += aptr[r + 1];
-    aptr[r + 1] = (int)tot;
-  }
-  FH_REQUIRE(tot < 2147483647ll, "fh_mat_create_from_elements: adjacency overflows int32");
-  int* d_aptr = nullptr;
-  FH_CHECK_HIP(hipMalloc(&d_aptr, ((size_t)m + 1) * sizeof(int)));
-  FH_CHECK_HIP(hipMalloc(&d_adj, std::max<size_t>((size_t)tot, 1) * sizeof(int)));
-  FH_CHECK_HIP(hipMemcpyAsync(d_aptr, aptr.data(), ((size_t)m + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  FH_CHECK_HIP(hipMemcpyAsync(d_cnt, aptr.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));        // cursors
-  if (ne) hipLaunchKernelGGL(k_pe_fill, dim3(gb), dim3(256), 0, c->stream, ne, nloc, d_ed, m, d_cnt, d_adj);
+  int* const d_aptr = L.d_ptr;
+  int* const d_adj = L.d_adj;
+  int* const d_err = L.d_err;
+  int err = 0;
   if (m) hipLaunchKernelGGL(k_pe_rows<false>, dim3(fh_div_up(m, 4)), dim3(256), 0, c->stream, m, d_aptr, d_adj, d_ed, nloc, (const int*)nullptr, d_len, (int*)nullptr, d_err);
   std::vector<int> rp((size_t)m + 1, 0);
   if (m) FH_CHECK_HIP(hipMemcpyAsync(rp.data() + 1, d_len, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -248,7 +266,6 @@ static int mat_create_from_elements_impl(fh_ctx_t c, int nel, int nloc, const in
       FH_CHECK_HIP(hipMemcpy(fetched.data(), d_ed, ne * sizeof(int), hipMemcpyDeviceToHost));
       elem_dof = fetched.data();
     }
-    hipFree(d_aptr);
     cleanup();
     std::vector<int> hrp((size_t)n + 1), hcol;
     FH_TRY(fh_pattern_from_elements(nel, nloc, elem_dof, n, hrp.data(), nullptr));
@@ -256,20 +273,18 @@ static int mat_create_from_elements_impl(fh_ctx_t c, int nel, int nloc, const in
     FH_TRY(fh_pattern_from_elements(nel, nloc, elem_dof, n, hrp.data(), hcol.data()));
     return fh_mat_create_csr(c, m, n, hrp.data(), hcol.data(), nullptr, out);
   }
-  tot = 0;
+  int64_t tot = 0;
   for (int r = 0; r < m; r++) {
     tot += rp[r + 1];
     rp[r + 1] = (int)tot;
   }
   if (tot >= 2147483647ll) {
-    hipFree(d_aptr);
     cleanup();
     fh_set_error("fh_mat_create_from_elements: nnz overflows int32");
     return 2;
   }
   fh_mat_t A = nullptr;
   if (fh_mat_alloc_device_pattern(c, m, n, std::move(rp), &A)) {
-    hipFree(d_aptr);
     cleanup();
     fh_mat_destroy(A);
     return 2;
@@ -277,7 +292,6 @@ static int mat_create_from_elements_impl(fh_ctx_t c, int nel, int nloc, const in
   if (m) hipLaunchKernelGGL(k_pe_rows<true>, dim3(fh_div_up(m, 4)), dim3(256), 0, c->stream, m, d_aptr, d_adj, d_ed, nloc, A->d_rowptr, (int*)nullptr, A->d_col, d_err);
   FH_CHECK_HIP(hipGetLastError());
   FH_CHECK_HIP(hipStreamSynchronize(c->stream));
-  hipFree(d_aptr);
   cleanup();
   FH_TRY(fh_mat_build_rowblocks(A, c->spmv_tile));
   *out = A;

@@ -280,6 +280,21 @@ int fh_elem_mesh_info(fh_elem_mesh_t mesh, int* dim, int* nel, int* nnode, int o
 int fh_elem_mesh_get(fh_elem_mesh_t mesh, int* elem_geom /* [nel] */, int* elem_dof /* [nel*27] */, double* coords /* [nnode*dim] */, int* face_flag /* [nel*6] */);
 int fh_elem_mesh_destroy(fh_elem_mesh_t mesh);
 
+/* ---- transfers and boundary lists of resident element meshes (fh_elemtransfer.hip) ----
+ * prolongator: PP of the level `fine` from the element prolongators (ElemType.cpp:439-532), an ordinary fh_mat_t of fine.own[fe] rows and coarse.own[fe]
+ * columns, resident and never on the host.  fe: 0 linear, 1 serendipity, 2 biquadratic.  fine must be the refinement of coarse: the same context and
+ * dimension, level + 1, nch times the elements (8 / 4) and fine element nch * e + j of the shape of e; anything else is refused before a kernel is launched.
+ * For every shape s, child j, fine local node n and coarse local function k < nc(s, fe) with EP_s[j][n][k] != 0 (fh_fe_elem_prolongator(s, fe): |.| < 1e-14
+ * is zero and adds no entry) and every coarse element e of shape s, EP_s[j][n][k] is inserted at (ed_f[nch e + j][n], ed_c[e][k]).  Insertions are ordered
+ * by (shape, j, n, k, e) and the last one of an entry stays (INSERT_VALUES); shapes in the order of their names sorted as strings, hex < quad < tet < tri <
+ * wedge: the shape codes 0, 1, 4, 3, 5.  The columns of a row ascend.  The result does not depend on the order the threads run in.
+ * fh_set_option(ctx, "elem_transfer_lds_rows", v): rows whose elements hold more than v candidate slots (27 per element; 1024, the default, at most) are
+ * built by a workgroup in global scratch, not by a wave in LDS -- the same bits (lowered by the A/B of the bitwise test).
+ * boundary_dofs: the ascending, duplicate-free list of the dofs < own[fe] on a face whose flag is one of flags[nflags]: ed[iel][fh_fe_face_nodes(shape, fe,
+ * face)].  Two-call protocol: with dofs = NULL the number comes back in *ndofs; the second call takes it there and fills dofs[*ndofs]. */
+int fh_elem_mesh_prolongator(fh_elem_mesh_t coarse, fh_elem_mesh_t fine, int fe, fh_mat_t* P);
+int fh_elem_mesh_boundary_dofs(fh_elem_mesh_t mesh, int fe, int nflags, const int* flags, int* ndofs, int* dofs /* NULL on the first call */);
+
 /* ---- sparsity (a11): LinearEquation::GetSparsityPatternSize (03_solvers/LinearEquation.cpp:407-548) ----
  * CSR pattern of the element-connectivity graph: two-call protocol (rowptr first, then col). */
 int fh_pattern_from_elements(int nel, int nloc, const int* elem_dof, int ndof, int* rowptr /* [ndof+1] */, int* col /* NULL on first call */);
