@@ -274,3 +274,5 @@ int fh_dev_halo_spmv(fh_halo_t h, fh_mat_t A, double* x, int n_own, double* y, i
 void fh_halo_send_plan(fh_halo_t h, const int** send_idx, double** sendbuf, int* nsend);
 
 static inline int fh_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// workgroups of a grid-stride launch of 256 threads over n entries: eight per compute unit at the most
+static inline int sgrid(fh_ctx_t c, int n) { return std::max(1, std::min(fh_div_up(n, 256), c->num_cu * 8)); }

@@ -13,6 +13,7 @@
 // fh_coarse.hip's (a dense GEMV with the inverse factored once per assembly, or its block / sparse forms); the whole cycle (~25 short launches, launch-bound on the coarse
 // levels) is captured in a hipGraph and replayed.
 #include "fh_coarse.h"
+#include "fh_krylov.h"
 #include "fh_trisolve.h"
 #include <algorithm>
 #include <memory>
@@ -67,11 +68,8 @@ struct MgLevel {
   std::vector<double> xyz;
   int xyz_dim = 0;
   // level solver: 0 = Richardson(omega) around the sweep preconditioner, 1 = GMRES (fixed iteration count, left-preconditioned)
-  int solver = 0, gm_restart = 30, gm_m = 0;
-  double* gm_buf = nullptr;  // (gm_m + 1) basis vectors of ncols + 2 entries
-  double** gm_dV = nullptr;  // their device pointer table
-  double* gm_small = nullptr;   // partial sums, Hessenberg matrix, reduced right-hand side, solution of the least-squares problem
-  int gm_nb = 0;             // workgroups of the dot-product launches
+  int solver = 0, gm_restart = 30;
+  LevelGmres gm;             // workspace of the GMRES level solver (fh_krylov.hip)
 };
 
 struct fh_mg_s {
@@ -85,14 +83,7 @@ struct fh_mg_s {
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
   uint64_t graph_sig = 0;     // what the captured cycle was recorded for (every pointer, size and option a launch of the cycle carries)
-  // Krylov workspace
-  std::vector<double*> kv;
-  int kv_n = 0;
-  double** d_V = nullptr;     // device copy of the basis pointers (GMRES), kept with kv
-  int d_V_n = 0;
-  double* d_gm = nullptr;     // state block of the device-resident GMRES (gm_state_doubles(restart)); h_gm = pinned mirror of its header
-  double* h_gm = nullptr;
-  size_t gm_cap = 0;
+  KrylovWork krylov;          // workspace of the outer solvers (fh_krylov.hip)
   int64_t cycle_bytes = 0;
 };
 
@@ -530,165 +521,6 @@ __global__ __launch_bounds__(256) void k_vanka_persistent(const int* __restrict_
   }
 }
 
-// V^T w for nvec basis vectors (GMRES classical Gram-Schmidt): partials[j*nb + block]
-__global__ __launch_bounds__(256) void k_multidot(const double* const* __restrict__ V, const double* __restrict__ w, int nvec, int n,
-                                                  double* __restrict__ part) {
-  __shared__ double sm[4];
-  for (int j = 0; j < nvec; j++) {
-    const double* v = V[j];
-    double acc = 0.0;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) acc += v[i] * w[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[(size_t)j * gridDim.x + blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
-    __syncthreads();
-  }
-}
-
-__global__ __launch_bounds__(256) void k_multidot_final(double* __restrict__ part, int nvec, int nb) {
-  __shared__ double sm[4];
-  const int j = blockIdx.x;
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 256) acc += part[(size_t)j * nb + i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[(size_t)nvec * nb + j] = sm[0] + sm[1] + sm[2] + sm[3];
-}
-
-// w -= sum_j h[j] V_j   (h on the device, right behind the partials)
-__global__ __launch_bounds__(256) void k_multiaxpy(double* __restrict__ w, const double* const* __restrict__ V, const double* __restrict__ h,
-                                                   double sign, int nvec, int n) {
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    double acc = w[i];
-    for (int j = 0; j < nvec; j++) acc += sign * h[j] * V[j][i];
-    w[i] = acc;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_axpby2(double* y, const double* x, double a, double b, int n) {   // x may alias y
-  // BLAS semantics: with b == 0 the old y is NOT referenced (it may be uninitialised memory: 0 * NaN = NaN)
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) y[i] = (b == 0.0) ? a * x[i] : a * x[i] + b * y[i];
-}
-
-// ---- device-resident GMRES (the default outer solver): the Hessenberg column, the Givens rotations, the residual estimate and the convergence test live in
-// a small state block on the device; the host reads {done, rn} back ONCE per iteration (one synchronisation instead of two, no arithmetic on the host) ----
-// state layout (doubles): [0] reference norm beta0  [1] rtol  [2] atol  [3] dtol  [4] rn  [5] scale of the next basis vector (1 / h_{k+1,k}, or 1 / beta)
-//                         [6] iterations done  [7] done flag  [8] maxit  [9] kused  [10] last norm  [11] restart   [16 ..] g, cs, sn, y, H (row-major, restart columns)
-constexpr int GM_HDR = 16;
-__device__ __forceinline__ double* gm_g(double* S) { return S + GM_HDR; }
-__device__ __forceinline__ double* gm_cs(double* S, int m) { return S + GM_HDR + (m + 1); }
-__device__ __forceinline__ double* gm_sn(double* S, int m) { return S + GM_HDR + (m + 1) + m; }
-__device__ __forceinline__ double* gm_y(double* S, int m) { return S + GM_HDR + (m + 1) + 2 * m; }
-__device__ __forceinline__ double* gm_H(double* S, int m) { return S + GM_HDR + (m + 1) + 3 * m; }
-static size_t gm_state_doubles(int m) { return (size_t)GM_HDR + (m + 1) + 3 * (size_t)m + (size_t)(m + 1) * m; }
-
-// squared norm, partial sums per block
-__global__ __launch_bounds__(256) void k_sqnorm_part(const double* __restrict__ w, int n, double* __restrict__ part) {
-  __shared__ double sm[4];
-  double acc = 0.0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) acc += w[i] * w[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
-}
-__global__ __launch_bounds__(256) void k_sum_part(const double* __restrict__ part, int nb, double* __restrict__ out) {
-  __shared__ double sm[4];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 256) acc += part[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = sm[0] + sm[1] + sm[2] + sm[3];
-}
-// y = s[0] * x (s on the device)
-__global__ __launch_bounds__(256) void k_scale_dev(double* __restrict__ y, const double* __restrict__ x, const double* __restrict__ s, int n) {
-  const double a = s[0];
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) y[i] = a * x[i];
-}
-// Knoll guess done: beta0 = ||M^-1 b|| (sq = its square, summed over the ranks)
-__global__ void k_gm_begin(double* __restrict__ S, const double* __restrict__ sq, double rtol, double atol, double dtol, int maxit, int restart) {
-  S[0] = sqrt(sq[0]);
-  S[1] = rtol; S[2] = atol; S[3] = dtol;
-  S[4] = 0.0; S[5] = 0.0; S[6] = 0.0; S[7] = 0.0;
-  S[8] = (double)maxit; S[9] = 0.0; S[10] = 0.0; S[11] = (double)restart;
-}
-// start of a restart cycle: beta = ||v0|| (sq = its square); converged / diverged / out of iterations -> done, otherwise g = beta e_0 and the scale 1 / beta
-__global__ void k_gm_restart(double* __restrict__ S, const double* __restrict__ sq) {
-  const int m = (int)S[11];
-  const double beta = sqrt(sq[0]);
-  S[4] = beta;
-  S[10] = beta;
-  S[9] = 0.0;
-  double* g = gm_g(S);
-  for (int i = 0; i <= m; i++) g[i] = 0.0;
-  g[0] = beta;
-  const bool stop = beta <= fmax(S[1] * S[0], S[2]) || S[6] >= S[8] || beta > S[3] * S[0];
-  S[7] = stop ? 1.0 : 0.0;
-  S[5] = (stop || beta == 0.0) ? 0.0 : 1.0 / beta;
-}
-// iteration k: h[0..k] = V^T w (before the orthogonalisation), wsq = ||w||^2 after it -> column k of the Hessenberg matrix, rotations, residual estimate,
-// convergence test; at the end of a restart cycle (converged or k == restart - 1) the back substitution y = H^-1 g as well.  The statements follow the
-// host loop of the flexible variant below one for one (same operations in the same order).
-__global__ void k_gm_step(double* __restrict__ S, const double* __restrict__ h, const double* __restrict__ wsq, int k) {
-  const int m = (int)S[11];
-  double* g = gm_g(S);
-  double* cs = gm_cs(S, m);
-  double* sn = gm_sn(S, m);
-  double* y = gm_y(S, m);
-  double* H = gm_H(S, m);
-  const double wn = sqrt(wsq[0]);
-  for (int j = 0; j <= k; j++) H[(size_t)j * m + k] = h[j];
-  H[(size_t)(k + 1) * m + k] = wn;
-  S[10] = wn;
-  S[5] = wn != 0.0 ? 1.0 / wn : 0.0;
-  for (int j = 0; j < k; j++) {
-    const double a = H[(size_t)j * m + k], bb = H[(size_t)(j + 1) * m + k];
-    H[(size_t)j * m + k] = cs[j] * a + sn[j] * bb;
-    H[(size_t)(j + 1) * m + k] = -sn[j] * a + cs[j] * bb;
-  }
-  const double a = H[(size_t)k * m + k], bb = H[(size_t)(k + 1) * m + k];
-  const double d = hypot(a, bb);
-  bool done = false;
-  if (d == 0.0) {          // column k of the Hessenberg matrix vanished entirely: nothing to rotate, nothing more to gain
-    cs[k] = 1.0;
-    sn[k] = 0.0;
-    H[(size_t)k * m + k] = 1.0;
-    g[k + 1] = 0.0;
-    S[6] += 1.0;
-    S[4] = 0.0;
-    done = true;
-  } else {
-    cs[k] = a / d;
-    sn[k] = bb / d;
-    H[(size_t)k * m + k] = d;
-    H[(size_t)(k + 1) * m + k] = 0.0;
-    g[k + 1] = -sn[k] * g[k];
-    g[k] = cs[k] * g[k];
-    S[6] += 1.0;
-    const double rn = fabs(g[k + 1]);
-    S[4] = rn;
-    done = rn <= fmax(S[1] * S[0], S[2]) || S[6] >= S[8] || wn == 0.0 || rn > S[3] * S[0];
-  }
-  const int kused = k + 1;
-  S[9] = (double)kused;
-  S[7] = done ? 1.0 : 0.0;
-  if (done || k == m - 1) {
-    for (int i = kused - 1; i >= 0; i--) {
-      double s2 = g[i];
-      for (int j = i + 1; j < kused; j++) s2 -= H[(size_t)i * m + j] * y[j];
-      y[i] = s2 / H[(size_t)i * m + i];
-    }
-  }
-}
-
-static inline int sgrid(fh_ctx_t c, int n) { return std::max(1, std::min(fh_div_up(n, 256), c->num_cu * 8)); }
 
 static inline int halo_spmv(fh_halo_t h, fh_mat_t A, double* x, int n_own, double* y, int mode, const double* b, const double* dinv, double omega,
                             bool prepacked = false) {
@@ -771,21 +603,11 @@ extern "C" int fh_mg_set_level_distributed(fh_mg_t mg, int level, fh_halo_t halo
   return 0;
 }
 
-static void free_level_gmres(MgLevel& L) {
-  if (L.gm_buf) hipFree(L.gm_buf);
-  if (L.gm_dV) hipFree(L.gm_dV);
-  if (L.gm_small) hipFree(L.gm_small);
-  L.gm_buf = nullptr;
-  L.gm_dV = nullptr;
-  L.gm_small = nullptr;
-  L.gm_m = 0;
-}
-
 static void free_level_buffers(MgLevel& L) {
   if (L.buf_base) hipFree(L.buf_base);         // the five work vectors of the level are one allocation (one fill per preparation)
   L.buf_base = nullptr;
   for (double** p : {&L.dinv, &L.x, &L.x2, &L.b, &L.r}) *p = nullptr;
-  free_level_gmres(L);
+  L.gm.release();
   L.buf_n = -1;
 }
 
@@ -844,7 +666,7 @@ static uint64_t cycle_signature(fh_mg_t mg) {
     mixp(L.halo);
     mix((uint64_t)L.solver);
     mix((uint64_t)L.gm_restart);
-    mixp(L.gm_buf);
+    mixp(L.gm.basis);
   }
   return h ? h : 1;
 }
@@ -1257,24 +1079,8 @@ extern "C" int fh_mg_setup(fh_mg_t mg) {
     FH_TRY(fh_dev_get_diag(L.A, L.dinv, 1));
     if (l > 0 && L.smoother == FH_SMOOTH_IDENTITY)      // PCNONE: B = I, the Jacobi kernels with a unit "inverse diagonal"
       hipLaunchKernelGGL(k_fill_value, dim3(sgrid(c, L.n)), dim3(256), 0, c->stream, L.dinv, 1.0, L.n);
-    if (l > 0 && L.solver == FH_LEVEL_GMRES) {
-      const int m = std::max(1, std::min(std::max(L.npre, L.npost), L.gm_restart));
-      if (L.gm_m != m || !L.gm_buf) {
-        free_level_gmres(L);
-        const size_t vs = (size_t)L.ncols + 2;
-        L.gm_nb = sgrid(c, L.n);
-        FH_CHECK_HIP(hipMalloc(&L.gm_buf, (size_t)(m + 1) * vs * sizeof(double)));
-        FH_CHECK_HIP(hipMalloc(&L.gm_dV, (size_t)(m + 1) * sizeof(double*)));
-        FH_CHECK_HIP(hipMalloc(&L.gm_small, ((size_t)(m + 2) * L.gm_nb + m + 2 + (size_t)m * (m + 1) + (m + 1) + m + 2) * sizeof(double)));
-        std::vector<double*> tab(m + 1);
-        for (int j = 0; j <= m; j++) tab[j] = L.gm_buf + (size_t)j * vs;
-        FH_CHECK_HIP(hipMemcpy(L.gm_dV, tab.data(), tab.size() * sizeof(double*), hipMemcpyHostToDevice));
-        L.gm_m = m;
-      }
-      FH_CHECK_HIP(hipMemsetAsync(L.gm_buf, 0, (size_t)(L.gm_m + 1) * ((size_t)L.ncols + 2) * sizeof(double), c->stream));
-    } else if (L.gm_buf) {
-      free_level_gmres(L);
-    }
+    if (l > 0 && L.solver == FH_LEVEL_GMRES) FH_TRY(L.gm.reserve(std::max(1, std::min(std::max(L.npre, L.npost), L.gm_restart)), L.ncols, L.n, c));
+    else L.gm.release();
     if (L.smoother == FH_SMOOTH_GS_COLOR && l > 0 && L.ncolors == 0) FH_TRY(color_rows(L));
     if ((L.smoother == FH_SMOOTH_SOR || L.smoother == FH_SMOOTH_ILU0) && l > 0) {
       if (!L.tri) FH_TRY(fh_tri_create(L.A, &L.tri));                       // level schedules: once per pattern
@@ -1378,55 +1184,6 @@ static int gs_sweeps(fh_mg_t mg, MgLevel& L, int nsweeps, bool zero_guess) {
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-// GMRES as the level solver (FH_LEVEL_GMRES): what `SetSolverFineGrids(GMRES)` -- the reference's default `_levelSolverType`, and
-// what 003_NavierStokes sets -- makes of a level (LinearEquationSolverPetsc.cpp:238-250, 501-502): exactly npre / npost iterations
-// (PCMG skips the convergence test of its smoothers), left-preconditioned by the level's sweep preconditioner B (Jacobi, SOR,
-// ILU(0), colour sweep, one multiplicative pass over the patches), classical Gram-Schmidt, restart _restart.  Minimises
-// ||B (b - A x)||_2 over x0 + K_m(BA, B r0).  Everything stays on the device and on the stream -- dot products into device
-// scalars, the (m + 1) x m least-squares problem in one single-thread kernel -- so the cycle remains one captured graph.
-// ------------------------------------------------------------------------------------------------
-// v <- v / sqrt(s2[0]), the norm goes to *hout (a zero norm -- lucky breakdown -- gives the zero vector and a zero entry)
-__global__ __launch_bounds__(256) void k_gm_normalize(double* __restrict__ v, const double* __restrict__ s2, double* __restrict__ hout, int n) {
-  const double nrm = sqrt(fmax(s2[0], 0.0));
-  const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *hout = nrm;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) v[i] *= inv;
-}
-__global__ void k_gm_copy(double* __restrict__ dst, const double* __restrict__ src, int k) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < k) dst[i] = src[i];
-}
-// least-squares solution of min || beta e1 - H y ||, H (m + 1) x m stored by columns of length ld (Givens rotations, one thread)
-__global__ void k_gm_solve(double* __restrict__ H, int ld, int m, const double* __restrict__ beta, double* __restrict__ g, double* __restrict__ y) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  for (int i = 0; i <= m; i++) g[i] = 0.0;
-  g[0] = *beta;
-  for (int k = 0; k < m; k++) {
-    double* hk = H + (size_t)k * ld;
-    // (rotations 0 .. k-1 have been applied to this column as they were formed: see below)
-    const double a = hk[k], b2 = hk[k + 1];
-    const double d = hypot(a, b2);
-    const double cs = d > 0.0 ? a / d : 1.0, sn = d > 0.0 ? b2 / d : 0.0;
-    hk[k] = d;
-    hk[k + 1] = 0.0;
-    const double t = cs * g[k] + sn * g[k + 1];
-    g[k + 1] = -sn * g[k] + cs * g[k + 1];
-    g[k] = t;
-    for (int j = k + 1; j < m; j++) {          // the same rotation on the later columns
-      double* hj = H + (size_t)j * ld;
-      const double u = cs * hj[k] + sn * hj[k + 1];
-      hj[k + 1] = -sn * hj[k] + cs * hj[k + 1];
-      hj[k] = u;
-    }
-  }
-  for (int k = m - 1; k >= 0; k--) {
-    double acc = g[k];
-    for (int j = k + 1; j < m; j++) acc -= H[(size_t)j * ld + k] * y[j];
-    const double d = H[(size_t)k * ld + k];
-    y[k] = d != 0.0 ? acc / d : 0.0;
-  }
-}
 __global__ __launch_bounds__(256) void k_scale_by(double* __restrict__ z, const double* __restrict__ r, const double* __restrict__ dinv, int n) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) z[i] = dinv[i] * r[i];
 }
@@ -1451,55 +1208,18 @@ static int level_precond(fh_mg_t mg, MgLevel& L, const double* r, double* z) {
   }
 }
 
-static int gmres_smooth(fh_mg_t mg, MgLevel& L, int nits, bool zero_guess) {
-  fh_ctx_t c = mg->ctx;
-  const int n = L.n, nb = L.gm_nb, ld = L.gm_m + 1;
-  const size_t vs = (size_t)L.ncols + 2;
-  double* part = L.gm_small;                               // [(gm_m + 2) * nb + gm_m + 2]
-  double* Hm = part + (size_t)(L.gm_m + 2) * nb + L.gm_m + 2;   // gm_m columns of length ld
-  double* g = Hm + (size_t)L.gm_m * ld;
-  double* y = g + ld;
-  double* beta = y + L.gm_m;
-  auto V = [&](int j) { return L.gm_buf + (size_t)j * vs; };
-  auto dots = [&](int nvec, const double* w) -> int {      // V[0..nvec)^T w -> part[nvec * nb ...]; summed over the ranks on a distributed level
-    hipLaunchKernelGGL(k_multidot, dim3(nb), dim3(256), 0, c->stream, (const double* const*)L.gm_dV, w, nvec, n, part);
-    hipLaunchKernelGGL(k_multidot_final, dim3(nvec), dim3(256), 0, c->stream, part, nvec, nb);
-    if (L.halo) FH_TRY(fh_halo_allreduce_ptr(L.halo, part + (size_t)nvec * nb, nvec));
-    return 0;
-  };
-  int done = 0;
-  while (done < nits) {
-    const int m = std::min(L.gm_m, nits - done);
-    const bool zg = zero_guess && done == 0;
-    if (zg) FH_TRY(level_precond(mg, L, L.b, V(0)));
-    else {
-      FH_TRY(halo_spmv(L.halo, L.A, L.x, n, L.r, 2, L.b, nullptr, 0.0));
-      FH_TRY(level_precond(mg, L, L.r, V(0)));
-    }
-    // beta = ||V0||, V0 <- V0 / beta : the dot kernel takes its vectors from the pointer table, so V0 . V0 = table entry 0 against V0
-    FH_TRY(dots(1, V(0)));
-    hipLaunchKernelGGL(k_gm_normalize, dim3(sgrid(c, n)), dim3(256), 0, c->stream, V(0), part + (size_t)nb, beta, n);
-    FH_CHECK_HIP(hipMemsetAsync(Hm, 0, (size_t)L.gm_m * ld * sizeof(double), c->stream));
-    for (int j = 0; j < m; j++) {
-      FH_TRY(halo_spmv(L.halo, L.A, V(j), n, L.r, 0, nullptr, nullptr, 0.0));
-      FH_TRY(level_precond(mg, L, L.r, V(j + 1)));
-      FH_TRY(dots(j + 1, V(j + 1)));                        // h = V^T w  (classical Gram-Schmidt, no refinement: PETSc's default)
-      hipLaunchKernelGGL(k_gm_copy, dim3(fh_div_up(j + 1, 64)), dim3(64), 0, c->stream, Hm + (size_t)j * ld, part + (size_t)(j + 1) * nb, j + 1);
-      hipLaunchKernelGGL(k_multiaxpy, dim3(nb), dim3(256), 0, c->stream, V(j + 1), (const double* const*)L.gm_dV, Hm + (size_t)j * ld, -1.0, j + 1, n);
-      // ||w||: table entry j + 1 is w itself
-      hipLaunchKernelGGL(k_multidot, dim3(nb), dim3(256), 0, c->stream, (const double* const*)(L.gm_dV + j + 1), V(j + 1), 1, n, part);
-      hipLaunchKernelGGL(k_multidot_final, dim3(1), dim3(256), 0, c->stream, part, 1, nb);
-      if (L.halo) FH_TRY(fh_halo_allreduce_ptr(L.halo, part + (size_t)nb, 1));
-      hipLaunchKernelGGL(k_gm_normalize, dim3(sgrid(c, n)), dim3(256), 0, c->stream, V(j + 1), part + (size_t)nb, Hm + (size_t)j * ld + j + 1, n);
-    }
-    hipLaunchKernelGGL(k_gm_solve, dim3(1), dim3(1), 0, c->stream, Hm, ld, m, beta, g, y);
-    if (zg) FH_CHECK_HIP(hipMemsetAsync(L.x, 0, (size_t)L.ncols * sizeof(double), c->stream));
-    hipLaunchKernelGGL(k_multiaxpy, dim3(nb), dim3(256), 0, c->stream, L.x, (const double* const*)L.gm_dV, y, 1.0, m, n);
-    done += m;
-  }
-  FH_CHECK_HIP(hipGetLastError());
-  return 0;
+// the level as a Krylov solver sees it: operator with ghost refresh, sum over the ranks, sweep preconditioner
+static KrylovOps level_ops(fh_mg_t mg, MgLevel& L) {
+  KrylovOps op;
+  op.ctx = mg->ctx;
+  op.n = L.n;
+  op.ncols = L.ncols;
+  op.spmv = [&L](double* x, double* y, int mode, const double* b) { return halo_spmv(L.halo, L.A, x, L.n, y, mode, b, nullptr, 0.0); };
+  op.allreduce = [&L](double* d, int count) { return L.halo ? fh_halo_allreduce_ptr(L.halo, d, count) : 0; };
+  op.precond = [mg, &L](const double* in, double* out) { return level_precond(mg, L, in, out); };
+  return op;
 }
+
 
 // one multiplicative V-cycle on the internal buffers: input lv[top].b, output lv[top].x
 // distributed levels: ghosts of the operand are refreshed before every operator application (MPIAIJ MatMult semantics)
@@ -1513,7 +1233,7 @@ static int smooth_level(fh_mg_t mg, MgLevel& L, int nits, bool zero_guess, bool*
     if (zero_guess) FH_CHECK_HIP(hipMemsetAsync(L.x, 0, (size_t)L.ncols * sizeof(double), c->stream));
     return 0;
   }
-  if (L.solver == FH_LEVEL_GMRES) return gmres_smooth(mg, L, nits, zero_guess);
+  if (L.solver == FH_LEVEL_GMRES) return fh_gmres_smooth(L.gm, level_ops(mg, L), L.x, L.b, L.r, nits, zero_guess);
   if (L.smoother == FH_SMOOTH_VANKA) {
     if (zero_guess) FH_CHECK_HIP(hipMemsetAsync(L.x, 0, (size_t)L.ncols * sizeof(double), c->stream));
     return vanka_sweeps(mg, L, nits);
@@ -1696,406 +1416,48 @@ extern "C" int fh_mg_destroy(fh_mg_t mg) {
     L.direct = nullptr;
   }
   fh_coarse_destroy(mg->coarse);
-  for (double* p : mg->kv) hipFree(p);
-  if (mg->d_V) hipFree(mg->d_V);
-  if (mg->d_gm) hipFree(mg->d_gm);
-  if (mg->h_gm) hipHostFree(mg->h_gm);
+  mg->krylov.release();
   delete mg;
   return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
-// outer solvers
+// outer solvers (fh_krylov.hip): PREONLY / RICHARDSON(0.99999) / PCG / GMRES(restart) / flexible GMRES(restart) around the cycle
 // ------------------------------------------------------------------------------------------------
-static int krylov_reserve(fh_mg_t mg, int nvec, int n) {
-  if ((int)mg->kv.size() >= nvec && mg->kv_n == n) return 0;
-  for (double* p : mg->kv) hipFree(p);
-  mg->kv.assign(nvec, nullptr);
-  for (int i = 0; i < nvec; i++) {
-    FH_CHECK_HIP(hipMalloc(&mg->kv[i], ((size_t)n + 2) * sizeof(double)));
-    // zero: ghost tails are read by the SpMV before any write.  debug_poison fills with NaN bit patterns instead, so that a test
-    // can show that nothing ELSE of a work vector is read before it is written (tests/test_gpu_multigrid.py)
-    FH_CHECK_HIP(hipMemsetAsync(mg->kv[i], mg->ctx->debug_poison ? 0xFF : 0, ((size_t)n + 2) * sizeof(double), mg->ctx->stream));
-  }
-  mg->kv_n = n;
-  return 0;
-}
-
-static int dev_dot(fh_ctx_t c, const double* x, const double* y, int n, double* out) {
-  fh_vec_s vx, vy;
-  vx.ctx = vy.ctx = c;
-  vx.n_local = vy.n_local = n;
-  vx.d = const_cast<double*>(x);
-  vy.d = const_cast<double*>(y);
-  return fh_vec_dot(&vx, &vy, out);
-}
-
-static int dev_axpby(fh_ctx_t c, double* y, const double* x, double a, double b, int n) {
-  hipLaunchKernelGGL(k_axpby2, dim3(sgrid(c, n)), dim3(256), 0, c->stream, y, x, a, b, n);
-  FH_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
 extern "C" int fh_mg_solve(fh_mg_t mg, fh_vec_t bv, fh_vec_t xv, int outer, double rtol, double atol, double dtol, int maxit, int restart,
                            int* iterations, double* final_residual) {
   FH_REQUIRE(mg && mg->setup_done, "fh_mg_solve: fh_mg_setup has not been called");
   fh_ctx_t c = mg->ctx;
-  const int top = mg->nlevels - 1;
-  fh_mat_t A = mg->lv[top].A;
-  const int n = A->m;                       // owned rows
-  const int ncols = mg->lv[top].ncols;      // owned + ghosts on a distributed level
-  fh_halo_t HL = mg->lv[top].halo;
-  FH_REQUIRE(bv->n_local >= n && xv->n_local + xv->nghost >= ncols, "fh_mg_solve: vectors too short");
-  // distributed forms of the two global operations (MatMult with ghost refresh, VecDot with all-reduce)
-  auto spmv = [&](double* xin, double* yout, int mode, const double* bb) -> int {
-    return halo_spmv(HL, A, xin, n, yout, mode, bb, nullptr, 0.0);
-  };
-  auto dot = [&](const double* u, const double* w2, double* out) -> int {
-    FH_TRY(dev_dot(c, u, w2, n, out));
-    if (HL) FH_TRY(fh_halo_allreduce_sum(HL, out, 1));
-    return 0;
-  };
+  MgLevel& top = mg->lv[mg->nlevels - 1];
+  fh_mat_t A = top.A;
+  fh_halo_t HL = top.halo;
+  // the finest level as the solvers see it: the distributed forms of the global operations (MatMult with ghost refresh, VecDot with all-reduce),
+  // and the cycle as the preconditioner, reading lv[top].b in place and leaving its result in lv[top].x
+  KrylovOps op;
+  op.ctx = c;
+  op.n = A->m;               // owned rows
+  op.ncols = top.ncols;      // owned + ghosts on a distributed level
+  FH_REQUIRE(bv->n_local >= op.n && xv->n_local + xv->nghost >= op.ncols, "fh_mg_solve: vectors too short");
   FH_REQUIRE(outer >= 0 && outer <= 4, "fh_mg_solve: unknown outer solver %d", outer);
-  double* b = bv->d;
-  double* x = xv->d;
-  int its = 0;
+  op.spmv = [=](double* x, double* y, int mode, const double* b) { return halo_spmv(HL, A, x, A->m, y, mode, b, nullptr, 0.0); };
+  op.allreduce = [=](double* d, int count) { return HL ? fh_halo_allreduce_ptr(HL, d, count) : 0; };
+  op.allreduce_host = [=](double* vals, int count) { return HL ? fh_halo_allreduce_sum(HL, vals, count) : 0; };
+  op.precond = [=](const double* in, double* out) { return apply_cycle(mg, in, out); };
+  op.precond_result = [&top]() { return top.x; };
+  op.precond_input = top.b;
+  double *b = bv->d, *x = xv->d;
+  int its = 0, rc = 0;
   double rn = 0.0;
-
-  if (outer == FH_OUTER_PREONLY) {
-    // exactly one cycle per MGSolve (LinearEquationSolverPetsc.cpp:310-313)
-    FH_TRY(apply_cycle(mg, b, x));
-    its = 1;
-  } else if (outer == FH_OUTER_RICHARDSON) {
-    // x <- x + 0.99999 M^-1 (b - A x), x0 = 0.  The scale of the OUTER Richardson is fixed by the reference itself: MGInit sets
-    // _richardsonScaleFactor = .99999 around SetSolver(_ksp) and restores the user's value afterwards (:190-193), so
-    // SetRichardsonScaleFactor only ever reaches the level smoothers (omega of fh_mg_set_level)
-    FH_TRY(krylov_reserve(mg, 2, ncols));
-    double *r = mg->kv[0], *z = mg->kv[1];
-    FH_CHECK_HIP(hipMemsetAsync(x, 0, (size_t)n * sizeof(double), c->stream));
-    double bn;
-    FH_TRY(dot(b, b, &bn));
-    bn = sqrt(bn);
-    for (;;) {
-      FH_TRY(spmv(x, r, 2, b));
-      FH_TRY(dot(r, r, &rn));
-      rn = sqrt(rn);
-      if (rn <= std::max(rtol * bn, atol) || its >= maxit || rn > dtol * bn) break;
-      FH_TRY(apply_cycle(mg, r, z));
-      FH_TRY(dev_axpby(c, x, z, 0.99999, 1.0, n));
-      its++;
-    }
-  } else if (outer == FH_OUTER_CG) {
-    FH_TRY(krylov_reserve(mg, 4, ncols));
-    double *r = mg->kv[0], *z = mg->kv[1], *p = mg->kv[2], *Ap = mg->kv[3];
-    FH_CHECK_HIP(hipMemsetAsync(x, 0, (size_t)n * sizeof(double), c->stream));
-    FH_CHECK_HIP(hipMemcpyAsync(r, b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    double bn, rz, rz_new, pAp;
-    FH_TRY(dot(b, b, &bn));
-    bn = sqrt(bn);
-    rn = bn;
-    FH_TRY(apply_cycle(mg, r, z));
-    FH_CHECK_HIP(hipMemcpyAsync(p, z, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    FH_TRY(dot(r, z, &rz));
-    while (rn > std::max(rtol * bn, atol) && its < maxit && rn <= dtol * bn) {
-      FH_TRY(spmv(p, Ap, 0, nullptr));
-      FH_TRY(dot(p, Ap, &pAp));
-      const double alpha = rz / pAp;
-      FH_TRY(dev_axpby(c, x, p, alpha, 1.0, n));
-      FH_TRY(dev_axpby(c, r, Ap, -alpha, 1.0, n));
-      FH_TRY(dot(r, r, &rn));
-      rn = sqrt(rn);
-      its++;
-      FH_TRY(apply_cycle(mg, r, z));
-      FH_TRY(dot(r, z, &rz_new));
-      FH_TRY(dev_axpby(c, p, z, 1.0, rz_new / rz, n));
-      rz = rz_new;
-    }
-  } else if (outer == FH_OUTER_FGMRES) {
-    // flexible GMRES(restart) (KSPFGMRES, LinearEquationSolverPetsc.cpp:506-507): RIGHT preconditioning with the vectors z_k = M^-1 v_k
-    // kept, so the cycle may be a different operator at every application (GMRES level solvers); classical Gram-Schmidt, Knoll
-    // guess x0 = M^-1 b, convergence on the TRUE residual norm against ||b|| (KSPConvergedDefault with a non-zero guess)
-    FH_REQUIRE(restart >= 1 && restart <= 200, "fh_mg_solve: restart %d out of range", restart);
-    FH_TRY(krylov_reserve(mg, 2 * restart + 2, ncols));
-    double** Vv = mg->kv.data();                       // v_0 .. v_restart
-    double** Zv = mg->kv.data() + restart + 1;         // z_0 .. z_{restart-1}
-    double* w = mg->kv[2 * restart + 1];
-    const int nb = sgrid(c, n);
-    FH_TRY(fh_reserve_reduction(c, (size_t)(restart + 2) * (nb + 1) + 64));
-    if (mg->d_V_n < 2 * restart + 1) {
-      if (mg->d_V) FH_CHECK_HIP(hipFree(mg->d_V));
-      mg->d_V = nullptr;
-      mg->d_V_n = 0;
-      FH_CHECK_HIP(hipMalloc(&mg->d_V, (2 * restart + 1) * sizeof(double*)));
-      mg->d_V_n = 2 * restart + 1;
-    }
-    double** d_V = mg->d_V;
-    double** d_Z = mg->d_V + restart + 1;
-    FH_CHECK_HIP(hipMemcpy(d_V, mg->kv.data(), (2 * restart + 1) * sizeof(double*), hipMemcpyHostToDevice));
-    std::vector<double> H((size_t)(restart + 1) * restart, 0.0), g(restart + 1), cs(restart), sn(restart), y(restart);
-    FH_TRY(apply_cycle(mg, b, x));
-    double bnorm;
-    FH_TRY(dot(b, b, &bnorm));
-    bnorm = sqrt(bnorm);
-    bool done = false;
-    while (!done) {
-      FH_TRY(spmv(x, Vv[0], 2, b));                            // v0 = b - A x
-      double beta;
-      FH_TRY(dot(Vv[0], Vv[0], &beta));
-      beta = sqrt(beta);
-      rn = beta;
-      if (beta <= std::max(rtol * bnorm, atol) || its >= maxit || beta > dtol * bnorm) break;
-      FH_TRY(dev_axpby(c, Vv[0], Vv[0], 0.0, 1.0 / beta, n));
-      std::fill(g.begin(), g.end(), 0.0);
-      g[0] = beta;
-      int kused = 0;
-      for (int k = 0; k < restart; k++) {
-        FH_TRY(apply_cycle(mg, Vv[k], Zv[k]));                 // z_k = M^-1 v_k
-        FH_TRY(spmv(Zv[k], w, 0, nullptr));                    // w = A z_k
-        hipLaunchKernelGGL(k_multidot, dim3(nb), dim3(256), 0, c->stream, (const double* const*)d_V, w, k + 1, n, c->d_red);
-        hipLaunchKernelGGL(k_multidot_final, dim3(k + 1), dim3(256), 0, c->stream, c->d_red, k + 1, nb);
-        if (HL) FH_TRY(fh_halo_allreduce_ptr(HL, c->d_red + (size_t)(k + 1) * nb, k + 1));
-        hipLaunchKernelGGL(k_multiaxpy, dim3(nb), dim3(256), 0, c->stream, w, (const double* const*)d_V, c->d_red + (size_t)(k + 1) * nb, -1.0,
-                           k + 1, n);
-        FH_CHECK_HIP(hipMemcpyAsync(c->h_red, c->d_red + (size_t)(k + 1) * nb, (k + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        FH_CHECK_HIP(hipStreamSynchronize(c->stream));
-        for (int j = 0; j <= k; j++) H[(size_t)j * restart + k] = c->h_red[j];
-        double wn;
-        FH_TRY(dot(w, w, &wn));
-        wn = sqrt(wn);
-        H[(size_t)(k + 1) * restart + k] = wn;
-        if (wn != 0.0) FH_TRY(dev_axpby(c, Vv[k + 1], w, 1.0 / wn, 0.0, n));
-        else FH_CHECK_HIP(hipMemsetAsync(Vv[k + 1], 0, (size_t)n * sizeof(double), c->stream));
-        for (int j = 0; j < k; j++) {
-          const double a = H[(size_t)j * restart + k], bb = H[(size_t)(j + 1) * restart + k];
-          H[(size_t)j * restart + k] = cs[j] * a + sn[j] * bb;
-          H[(size_t)(j + 1) * restart + k] = -sn[j] * a + cs[j] * bb;
-        }
-        const double a = H[(size_t)k * restart + k], bb = H[(size_t)(k + 1) * restart + k];
-        const double d = hypot(a, bb);
-        if (d == 0.0) {
-          cs[k] = 1.0;
-          sn[k] = 0.0;
-          H[(size_t)k * restart + k] = 1.0;
-          g[k + 1] = 0.0;
-          its++;
-          kused = k + 1;
-          rn = 0.0;
-          done = true;
-          break;
-        }
-        cs[k] = a / d;
-        sn[k] = bb / d;
-        H[(size_t)k * restart + k] = d;
-        H[(size_t)(k + 1) * restart + k] = 0.0;
-        g[k + 1] = -sn[k] * g[k];
-        g[k] = cs[k] * g[k];
-        its++;
-        kused = k + 1;
-        rn = fabs(g[k + 1]);
-        if (rn <= std::max(rtol * bnorm, atol) || its >= maxit || wn == 0.0 || rn > dtol * bnorm) {
-          done = true;
-          break;
-        }
-      }
-      for (int i = kused - 1; i >= 0; i--) {
-        double s2 = g[i];
-        for (int j = i + 1; j < kused; j++) s2 -= H[(size_t)i * restart + j] * y[j];
-        y[i] = s2 / H[(size_t)i * restart + i];
-      }
-      // x += Z y
-      FH_CHECK_HIP(hipMemcpyAsync(c->d_red, y.data(), kused * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(k_multiaxpy, dim3(nb), dim3(256), 0, c->stream, x, (const double* const*)d_Z, c->d_red, 1.0, kused, n);
-      FH_CHECK_HIP(hipStreamSynchronize(c->stream));
-    }
-  } else if (c->gmres_device) {
-    // left-preconditioned GMRES(restart), classical Gram-Schmidt, Knoll guess x0 = M^-1 b (LinearEquationSolverPetsc.cpp:294-335), device-resident: the
-    // Hessenberg matrix, the rotations, the residual estimate and the convergence test stay on the device (k_gm_*); per iteration the host enqueues
-    // [A v, cycle, V^T w, w -= V h, ||w||^2, k_gm_step, v_{k+1} = w / h_{k+1,k}] and reads {done, rn, iterations} back once.  Same arithmetic in the same
-    // order as the host-driven form below (option gmres_device 0), which it replaces as the default.
-    FH_REQUIRE(restart >= 1 && restart <= 200, "fh_mg_solve: restart %d out of range", restart);
-    FH_TRY(krylov_reserve(mg, restart + 3, ncols));
-    double* t = mg->lv[mg->nlevels - 1].b;
-    const int nb = sgrid(c, n);
-    FH_TRY(fh_reserve_reduction(c, (size_t)(restart + 2) * (nb + 1) + nb + 64));
-    if (mg->d_V_n < restart + 1) {
-      if (mg->d_V) FH_CHECK_HIP(hipFree(mg->d_V));
-      mg->d_V = nullptr;
-      mg->d_V_n = 0;
-      FH_CHECK_HIP(hipMalloc(&mg->d_V, (restart + 1) * sizeof(double*)));
-      mg->d_V_n = restart + 1;
-    }
-    double** d_V = mg->d_V;
-    FH_CHECK_HIP(hipMemcpyAsync(d_V, mg->kv.data(), (restart + 1) * sizeof(double*), hipMemcpyHostToDevice, c->stream));
-    if (mg->gm_cap < gm_state_doubles(restart)) {
-      if (mg->d_gm) FH_CHECK_HIP(hipFree(mg->d_gm));
-      mg->d_gm = nullptr;
-      mg->gm_cap = 0;
-      FH_CHECK_HIP(hipMalloc(&mg->d_gm, gm_state_doubles(restart) * sizeof(double)));
-      mg->gm_cap = gm_state_doubles(restart);
-    }
-    if (!mg->h_gm) FH_CHECK_HIP(hipHostMalloc(&mg->h_gm, GM_HDR * sizeof(double)));
-    double* S = mg->d_gm;
-    // scratch inside the reduction buffer: partial sums [0, (restart + 1) * nb), the projections h behind them, then the partials of ||w||^2 and its sum
-    double* hcol_of_k = nullptr;
-    double* sqp = c->d_red + (size_t)(restart + 2) * (nb + 1);
-    double* sq1 = sqp + nb;
-    auto sqnorm = [&](const double* v) -> int {          // sq1[0] = ||v||^2 over all ranks
-      hipLaunchKernelGGL(k_sqnorm_part, dim3(nb), dim3(256), 0, c->stream, v, n, sqp);
-      hipLaunchKernelGGL(k_sum_part, dim3(1), dim3(256), 0, c->stream, sqp, nb, sq1);
-      if (HL) FH_TRY(fh_halo_allreduce_ptr(HL, sq1, 1));
-      return 0;
-    };
-    auto readback = [&]() -> int {
-      FH_CHECK_HIP(hipMemcpyAsync(mg->h_gm, S, GM_HDR * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      FH_CHECK_HIP(hipStreamSynchronize(c->stream));
-      return 0;
-    };
-    // Knoll: x0 = M^-1 b ; reference norm = ||M^-1 b||
-    FH_TRY(apply_cycle(mg, b, x));
-    FH_TRY(sqnorm(x));
-    hipLaunchKernelGGL(k_gm_begin, dim3(1), dim3(1), 0, c->stream, S, sq1, rtol, atol, dtol, maxit, restart);
-    bool done = false;
-    while (!done) {
-      FH_TRY(spmv(x, t, 2, b));                                // t = b - A x
-      FH_TRY(apply_cycle(mg, t, mg->kv[0]));                  // v0 = M^-1 t
-      FH_TRY(sqnorm(mg->kv[0]));
-      hipLaunchKernelGGL(k_gm_restart, dim3(1), dim3(1), 0, c->stream, S, sq1);
-      hipLaunchKernelGGL(k_scale_dev, dim3(nb), dim3(256), 0, c->stream, mg->kv[0], mg->kv[0], S + 5, n);
-      FH_CHECK_HIP(hipGetLastError());
-      FH_TRY(readback());
-      rn = mg->h_gm[4];
-      if (mg->h_gm[7] != 0.0) break;
-      int kused = 0;
-      for (int k = 0; k < restart; k++) {
-        FH_TRY(spmv(mg->kv[k], t, 0, nullptr));
-        FH_TRY(apply_cycle(mg, t, nullptr));
-        double* w = mg->lv[mg->nlevels - 1].x;                // (an un-captured cycle alternates between its two buffers)
-        // h = V^T w (one pass), w -= V h, h_{k+1,k} = ||w||
-        hipLaunchKernelGGL(k_multidot, dim3(nb), dim3(256), 0, c->stream, (const double* const*)d_V, w, k + 1, n, c->d_red);
-        hipLaunchKernelGGL(k_multidot_final, dim3(k + 1), dim3(256), 0, c->stream, c->d_red, k + 1, nb);
-        hcol_of_k = c->d_red + (size_t)(k + 1) * nb;
-        if (HL) FH_TRY(fh_halo_allreduce_ptr(HL, hcol_of_k, k + 1));
-        hipLaunchKernelGGL(k_multiaxpy, dim3(nb), dim3(256), 0, c->stream, w, (const double* const*)d_V, hcol_of_k, -1.0, k + 1, n);
-        FH_TRY(sqnorm(w));
-        hipLaunchKernelGGL(k_gm_step, dim3(1), dim3(1), 0, c->stream, S, hcol_of_k, sq1, k);
-        // v_{k+1} = w / h_{k+1,k} (zero on a happy breakdown: the scale is 0 then); never used when the test above said stop
-        hipLaunchKernelGGL(k_scale_dev, dim3(nb), dim3(256), 0, c->stream, mg->kv[k + 1], w, S + 5, n);
-        FH_CHECK_HIP(hipGetLastError());
-        FH_TRY(readback());
-        its = (int)mg->h_gm[6];
-        rn = mg->h_gm[4];
-        kused = k + 1;
-        if (mg->h_gm[7] != 0.0) {
-          done = true;
-          break;
-        }
-      }
-      // x += V y (y from the back substitution inside the last k_gm_step)
-      hipLaunchKernelGGL(k_multiaxpy, dim3(nb), dim3(256), 0, c->stream, x, (const double* const*)d_V, S + GM_HDR + (restart + 1) + 2 * restart, 1.0, kused, n);
-      FH_CHECK_HIP(hipGetLastError());
-    }
-  } else {
-    // the same solver driven from the host (option gmres_device 0): two synchronisations per iteration, the small dense algebra on the host
-    FH_REQUIRE(restart >= 1 && restart <= 200, "fh_mg_solve: restart %d out of range", restart);
-    FH_TRY(krylov_reserve(mg, restart + 3, ncols));
-    // t = the cycle's own right-hand-side buffer (the products A v land where the cycle reads them), w = wherever the cycle leaves its result
-    double* t = mg->lv[mg->nlevels - 1].b;
-    double* w = nullptr;
-    const int nb = sgrid(c, n);
-    FH_TRY(fh_reserve_reduction(c, (size_t)(restart + 2) * (nb + 1) + 64));
-    // basis pointers on the device: owned by the solver object (an early error return must not leak them)
-    if (mg->d_V_n < restart + 1) {
-      if (mg->d_V) FH_CHECK_HIP(hipFree(mg->d_V));
-      mg->d_V = nullptr;
-      mg->d_V_n = 0;
-      FH_CHECK_HIP(hipMalloc(&mg->d_V, (restart + 1) * sizeof(double*)));
-      mg->d_V_n = restart + 1;
-    }
-    double** d_V = mg->d_V;
-    FH_CHECK_HIP(hipMemcpy(d_V, mg->kv.data(), (restart + 1) * sizeof(double*), hipMemcpyHostToDevice));
-    std::vector<double> H((size_t)(restart + 1) * restart, 0.0), g(restart + 1), cs(restart), sn(restart), y(restart);
-    // Knoll: x0 = M^-1 b ; reference norm = ||M^-1 b||
-    FH_TRY(apply_cycle(mg, b, x));
-    double beta0;
-    FH_TRY(dot(x, x, &beta0));
-    beta0 = sqrt(beta0);
-    bool done = false;
-    while (!done) {
-      FH_TRY(spmv(x, t, 2, b));                                // t = b - A x
-      FH_TRY(apply_cycle(mg, t, mg->kv[0]));                  // v0 = M^-1 t
-      double beta;
-      FH_TRY(dot(mg->kv[0], mg->kv[0], &beta));
-      beta = sqrt(beta);
-      rn = beta;
-      if (beta <= std::max(rtol * beta0, atol) || its >= maxit || beta > dtol * beta0) break;
-      FH_TRY(dev_axpby(c, mg->kv[0], mg->kv[0], 0.0, 1.0 / beta, n));
-      std::fill(g.begin(), g.end(), 0.0);
-      g[0] = beta;
-      int kused = 0;
-      for (int k = 0; k < restart; k++) {
-        FH_TRY(spmv(mg->kv[k], t, 0, nullptr));
-        FH_TRY(apply_cycle(mg, t, nullptr));
-        w = mg->lv[mg->nlevels - 1].x;                  // (an un-captured cycle alternates between its two buffers)
-        // h = V^T w (one pass), w -= V h, h_{k+1,k} = ||w||
-        hipLaunchKernelGGL(k_multidot, dim3(nb), dim3(256), 0, c->stream, (const double* const*)d_V, w, k + 1, n, c->d_red);
-        hipLaunchKernelGGL(k_multidot_final, dim3(k + 1), dim3(256), 0, c->stream, c->d_red, k + 1, nb);
-        if (HL) FH_TRY(fh_halo_allreduce_ptr(HL, c->d_red + (size_t)(k + 1) * nb, k + 1));
-        hipLaunchKernelGGL(k_multiaxpy, dim3(nb), dim3(256), 0, c->stream, w, (const double* const*)d_V, c->d_red + (size_t)(k + 1) * nb, -1.0,
-                           k + 1, n);
-        FH_CHECK_HIP(hipMemcpyAsync(c->h_red, c->d_red + (size_t)(k + 1) * nb, (k + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        FH_CHECK_HIP(hipStreamSynchronize(c->stream));
-        for (int j = 0; j <= k; j++) H[(size_t)j * restart + k] = c->h_red[j];
-        double wn;
-        FH_TRY(dot(w, w, &wn));
-        wn = sqrt(wn);
-        H[(size_t)(k + 1) * restart + k] = wn;
-        // happy breakdown (w = 0: the Krylov space is invariant): the next basis vector is never used, but it must not stay
-        // uninitialised / stale either
-        if (wn != 0.0) FH_TRY(dev_axpby(c, mg->kv[k + 1], w, 1.0 / wn, 0.0, n));
-        else FH_CHECK_HIP(hipMemsetAsync(mg->kv[k + 1], 0, (size_t)n * sizeof(double), c->stream));
-        for (int j = 0; j < k; j++) {
-          const double a = H[(size_t)j * restart + k], bb = H[(size_t)(j + 1) * restart + k];
-          H[(size_t)j * restart + k] = cs[j] * a + sn[j] * bb;
-          H[(size_t)(j + 1) * restart + k] = -sn[j] * a + cs[j] * bb;
-        }
-        const double a = H[(size_t)k * restart + k], bb = H[(size_t)(k + 1) * restart + k];
-        const double d = hypot(a, bb);
-        if (d == 0.0) {          // column k of the Hessenberg matrix vanished entirely: nothing to rotate, nothing more to gain
-          cs[k] = 1.0;
-          sn[k] = 0.0;
-          H[(size_t)k * restart + k] = 1.0;      // keeps the back substitution finite; g[k] stays, y[k] = g[k]
-          g[k + 1] = 0.0;
-          its++;
-          kused = k + 1;
-          rn = 0.0;
-          done = true;
-          break;
-        }
-        cs[k] = a / d;
-        sn[k] = bb / d;
-        H[(size_t)k * restart + k] = d;
-        H[(size_t)(k + 1) * restart + k] = 0.0;
-        g[k + 1] = -sn[k] * g[k];
-        g[k] = cs[k] * g[k];
-        its++;
-        kused = k + 1;
-        rn = fabs(g[k + 1]);
-        if (rn <= std::max(rtol * beta0, atol) || its >= maxit || wn == 0.0 || rn > dtol * beta0) {   // dtol: KSP_DIVERGED_DTOL at every iteration
-          done = true;
-          break;
-        }
-      }
-      for (int i = kused - 1; i >= 0; i--) {
-        double s = g[i];
-        for (int j = i + 1; j < kused; j++) s -= H[(size_t)i * restart + j] * y[j];
-        y[i] = s / H[(size_t)i * restart + i];
-      }
-      // x += V y
-      FH_CHECK_HIP(hipMemcpyAsync(c->d_red, y.data(), kused * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(k_multiaxpy, dim3(nb), dim3(256), 0, c->stream, x, (const double* const*)d_V, c->d_red, 1.0, kused, n);
-      FH_CHECK_HIP(hipStreamSynchronize(c->stream));
-    }
+  switch (outer) {
+    case FH_OUTER_PREONLY: rc = fh_krylov_preonly(op, b, x, &its); break;
+    case FH_OUTER_RICHARDSON: rc = fh_krylov_richardson(op, mg->krylov, b, x, rtol, atol, dtol, maxit, &its, &rn); break;
+    case FH_OUTER_CG: rc = fh_krylov_cg(op, mg->krylov, b, x, rtol, atol, dtol, maxit, &its, &rn); break;
+    case FH_OUTER_FGMRES: rc = fh_krylov_gmres_host(op, mg->krylov, true, b, x, rtol, atol, dtol, maxit, restart, &its, &rn); break;
+    default:      // FH_OUTER_GMRES: device-resident unless option gmres_device is 0
+      rc = c->gmres_device ? fh_krylov_gmres_device(op, mg->krylov, b, x, rtol, atol, dtol, maxit, restart, &its, &rn)
+                           : fh_krylov_gmres_host(op, mg->krylov, false, b, x, rtol, atol, dtol, maxit, restart, &its, &rn);
   }
+  if (rc) return rc;
   FH_CHECK_HIP(hipStreamSynchronize(c->stream));
   if (iterations) *iterations = its;
   if (final_residual) *final_residual = rn;

@@ -115,20 +115,34 @@ def test_repeated_setup_with_new_values_keeps_or_rebuilds_the_captured_cycle(ctx
         ctx.set_option("mg_reuse_graph", 1)
 
 
+def gmres_device_settings(outer):
+    """option gmres_device picks the driver of the outer GMRES (1: recurrences on the device, 0: driven from the host); the other outer solvers ignore it"""
+    return (1, 0) if outer == "gmres" else (1,)
+
+
 @pytest.mark.parametrize("outer", ["richardson", "gmres", "cg", "fgmres"])
 def test_outer_solvers_reach_direct_solution(ctx, H3, outer):
     mg, mats = device_hierarchy(ctx, H3)
     n = H3.A[-1].shape[0]
     xd = spla.spsolve(H3.A[-1].tocsc(), H3.b)
-    b, x = ctx.vector_from(H3.b), ctx.vector(n)
-    its, rn = mg.solve(b, x, outer=outer, rtol=1e-12, maxit=60)
-    assert rel(x.to_numpy(), xd) < 1e-10            # north_star: 1e-10 relative on the FP solve
-    assert its <= 30
     xo, hist = {"richardson": fo.solve_richardson_mg, "gmres": fo.solve_gmres_mg, "cg": fo.solve_pcg_mg, "fgmres": fo.solve_fgmres_mg}[outer](H3, rtol=1e-12)
-    assert rel(x.to_numpy(), xo) < 1e-10
-    assert abs(its - (len(hist) - 1)) <= 2           # same convergence behaviour as the restated algorithm
-    if outer == "fgmres":                           # the same algorithm step by step: residual estimate of the last iteration
-        assert its == len(hist) - 1 and abs(rn - hist[-1]) <= 1e-6 * hist[0]
+    b, x = ctx.vector_from(H3.b), ctx.vector(n)
+    counts = []
+    try:
+        for dev in gmres_device_settings(outer):
+            ctx.set_option("gmres_device", dev)
+            its, rn = mg.solve(b, x, outer=outer, rtol=1e-12, maxit=60)
+            assert rel(x.to_numpy(), xd) < 1e-10            # north_star: 1e-10 relative on the FP solve
+            assert its <= 30
+            assert rel(x.to_numpy(), xo) < 1e-10
+            assert abs(its - (len(hist) - 1)) <= 2           # same convergence behaviour as the restated algorithm
+            if outer == "fgmres":                           # the same algorithm step by step: residual estimate of the last iteration
+                assert its == len(hist) - 1 and abs(rn - hist[-1]) <= 1e-6 * hist[0]
+            counts.append(its)
+    finally:
+        ctx.set_option("gmres_device", 1)
+    if len(counts) == 2:        # its0 == its1: the host-driven GMRES stops where the device-resident one does
+        assert counts[0] == counts[1]
     mg.destroy()
 
 
@@ -136,21 +150,25 @@ def test_outer_solvers_reach_direct_solution(ctx, H3, outer):
 def test_solvers_do_not_read_uninitialised_work_memory(ctx, H3, outer):
     """regression: the Krylov work vectors used to be raw allocations and `y = a x + 0 * y` read them -- NaN whenever the
     allocation landed on NaN bit patterns (seen as a rare failure of GMRES solves on freshly booted boxes).  With `debug_poison`
-    the work buffers of the hierarchy and of the solvers start as NaN: the results must not change."""
+    the work buffers of the hierarchy and of the solvers start as NaN: the results must not change.  Each driver of the outer GMRES
+    gets a hierarchy of its own, so that its work vectors are fresh (poisoned) allocations."""
     n = H3.A[-1].shape[0]
     xd = spla.spsolve(H3.A[-1].tocsc(), H3.b)
-    ctx.set_option("debug_poison", 1)
-    try:
-        mg, mats = device_hierarchy(ctx, H3)
-        b, x = ctx.vector_from(H3.b), ctx.vector(n)
-        mg.vcycle(b, x)
-        assert rel(x.to_numpy(), fo.vcycle(H3, len(H3.A) - 1, H3.b)) < 1e-11
-        its, rn = mg.solve(b, x, outer=outer, rtol=1e-12, maxit=60)
-    finally:
-        ctx.set_option("debug_poison", 0)
-    assert np.isfinite(x.to_numpy()).all() and np.isfinite(rn)
-    assert rel(x.to_numpy(), xd) < 1e-10
-    mg.destroy()
+    for dev in gmres_device_settings(outer):
+        ctx.set_option("debug_poison", 1)
+        ctx.set_option("gmres_device", dev)
+        try:
+            mg, mats = device_hierarchy(ctx, H3)
+            b, x = ctx.vector_from(H3.b), ctx.vector(n)
+            mg.vcycle(b, x)
+            assert rel(x.to_numpy(), fo.vcycle(H3, len(H3.A) - 1, H3.b)) < 1e-11
+            its, rn = mg.solve(b, x, outer=outer, rtol=1e-12, maxit=60)
+        finally:
+            ctx.set_option("debug_poison", 0)
+            ctx.set_option("gmres_device", 1)
+        assert np.isfinite(x.to_numpy()).all() and np.isfinite(rn)
+        assert rel(x.to_numpy(), xd) < 1e-10
+        mg.destroy()
 
 
 def test_preonly_is_one_cycle(ctx, H3):
@@ -175,12 +193,19 @@ def test_config1_2d_q1_three_levels(ctx):
 
 
 def test_gmres_restart_path(ctx, H3):
+    """more iterations than one restart cycle, under both drivers of the outer GMRES (host-driven: the restart branch of the shared loop and
+    its back substitution over a full cycle)"""
     mg, mats = device_hierarchy(ctx, H3, 0.3, 1, 0)      # deliberately weak smoother -> more iterations than restart
     n = H3.A[-1].shape[0]
     xd = spla.spsolve(H3.A[-1].tocsc(), H3.b)
     b, x = ctx.vector_from(H3.b), ctx.vector(n)
-    its, rn = mg.solve(b, x, outer="gmres", rtol=1e-11, maxit=200, restart=5)
-    assert its > 5 and rel(x.to_numpy(), xd) < 1e-9
+    try:
+        for dev in (1, 0):
+            ctx.set_option("gmres_device", dev)
+            its, rn = mg.solve(b, x, outer="gmres", rtol=1e-11, maxit=200, restart=5)
+            assert its > 5 and rel(x.to_numpy(), xd) < 1e-9
+    finally:
+        ctx.set_option("gmres_device", 1)
 
 
 def test_multicolour_sor_smoother(ctx, H3):
