@@ -434,6 +434,42 @@ class Poisson001:
         indptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=ndof_f))])
         return capi.Mat.from_csr(self.ctx, ndof_f, ndof_c, indptr, cols, vals)
 
+    def _prolongator_from_links(self, groups, ed_c, ed_f, ndof_c, ndof_f, father, child):
+        """PP into a level of mixed_mesh.refine_flagged, whose fine element f is child child[f] of father[f], or its unchanged copy (child -1).  First the
+        insertions of _prolongator_from_children over the REFINED elements e alone, the fine row taken from the element whose (father, child) is (e, j); then
+        the identity of the copies, ordered (shape, n < nc, e): exactly 1.0 at (ed_f[copy of e][n], ed_c[e][n]) (LinearImplicitSystem.cpp:761-811).  The last
+        insertion of an entry stays, so a node a copy shares with a refined neighbour keeps the exact 1.0"""
+        father, child = np.asarray(father, dtype=np.int64), np.asarray(child, dtype=np.int64)
+        nch = int(child.max()) + 1 if child.size else 0
+        fine_of = np.full((ed_c.shape[0], max(nch, 1)), -1, dtype=np.int64)       # [e, j] -> fine element; a copy sits at j = 0 of an element without children
+        kids = child >= 0
+        refined = np.zeros(ed_c.shape[0], dtype=bool)
+        refined[father[kids]] = True
+        fine_of[father, np.maximum(child, 0)] = np.arange(father.size)
+        rows_l, cols_l, vals_l = [], [], []
+        for geom, idx, nc in groups:
+            EP = capi.fe_elem_prolongator(geom, self.fe)
+            ref = idx[refined[idx]]
+            for j in range(EP.shape[0] if ref.size else 0):
+                for n in range(nc):
+                    rows = ed_f[fine_of[ref, j], n]
+                    for k in np.nonzero(EP[j, n, :nc])[0]:
+                        rows_l.append(rows)
+                        cols_l.append(ed_c[ref, k])
+                        vals_l.append(np.full(rows.size, EP[j, n, k]))
+        for geom, idx, nc in groups:
+            cp = idx[~refined[idx]]
+            for n in range(nc):
+                rows_l.append(ed_f[fine_of[cp, 0], n])
+                cols_l.append(ed_c[cp, n])
+                vals_l.append(np.full(cp.size, 1.0))
+        rows, cols, vals = np.concatenate(rows_l).astype(np.int64), np.concatenate(cols_l).astype(np.int64), np.concatenate(vals_l)
+        key = (rows * ndof_c + cols)[::-1]                          # INSERT_VALUES: the last insertion of an entry stays
+        uniq, last = np.unique(key, return_index=True)
+        rows, cols, vals = uniq // ndof_c, uniq % ndof_c, vals[::-1][last]
+        indptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=ndof_f))])
+        return capi.Mat.from_csr(self.ctx, ndof_f, ndof_c, indptr, cols, vals)
+
     # ---- the one-dimensional input (input/input1D.json: EDGE3 box) -------------------------------------------------------------------------------
     NU_1D, V_1D = 0.01, 1.0                      # main.cpp:392-395: in one dimension the callback is advection-diffusion with V = 1, nu = 0.01
 

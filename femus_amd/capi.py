@@ -743,6 +743,9 @@ class ElementMesh:
         own = (ctypes.c_int * 3)()
         _chk(self.L.fh_elem_mesh_info(self.h, ctypes.byref(dim), ctypes.byref(nel), ctypes.byref(nnode), own, ctypes.byref(lev)))
         self.dim, self.nel, self.nnode, self.level, self.own = dim.value, nel.value, nnode.value, lev.value, [int(k) for k in own]
+        hom = ctypes.c_int()
+        _chk(self.L.fh_elem_mesh_elem_levels(self.h, None, None, None, ctypes.byref(hom)))
+        self.homogeneous = bool(hom.value)
 
     @classmethod
     def from_arrays(cls, ctx, kind, ed, xs, ff, own):
@@ -766,10 +769,49 @@ class ElementMesh:
         _chk(ctx.L.fh_elem_mesh_create(ctx.h, int(xs.shape[1]), int(kind.shape[0]), int(xs.shape[0]), _p(code), _p(ed), _p(xs), _p(ff), _p(own), ctypes.byref(h)))
         return cls(ctx, h)
 
-    def refine(self):
+    def refine(self, flags=None):
+        """the uniform refinement, or with flags -- uint8 / bool [nel], or "resident": the ones flag() left on the device -- the selective one
+        (fh_elem_mesh_refine_flagged, the integers and bits of mixed_mesh.refine_flagged)"""
         h = ctypes.c_void_p()
-        _chk(self.L.fh_elem_mesh_refine(self.h, ctypes.byref(h)))
+        if flags is None:
+            _chk(self.L.fh_elem_mesh_refine(self.h, ctypes.byref(h)))
+        elif isinstance(flags, str):
+            if flags != "resident":
+                raise FemusHipError("ElementMesh.refine: flags must be an array of %d flags or \"resident\", not %r" % (self.nel, flags))
+            _chk(self.L.fh_elem_mesh_refine_flagged(self.h, None, ctypes.byref(h)))
+        else:
+            f = np.ascontiguousarray(np.asarray(flags) != 0, dtype=np.uint8)
+            if f.shape != (self.nel,):
+                raise FemusHipError("ElementMesh.refine: %s flags for %d elements" % (f.shape, self.nel))
+            _chk(self.L.fh_elem_mesh_refine_flagged(self.h, _p(f), ctypes.byref(h)))
         return ElementMesh(self.ctx, h)
+
+    def flag(self, expr):
+        """MeshRefinement::FlagElementsToRefine type 1 on the device (fh_elem_mesh_flag): an Expr over "x,y,z,level", or its text, at the mean of every element's
+        vertices; uint8[nel], 0 for elements of an older level.  The flags also stay on the device for refine("resident")"""
+        e = Expr(expr, "x,y,z,level") if isinstance(expr, str) else expr
+        out = np.empty(self.nel, np.uint8)
+        try:
+            _chk(self.L.fh_elem_mesh_flag(self.h, e.h, _p(out) if self.nel else None))
+        finally:
+            if e is not expr:
+                e.destroy()
+        return out
+
+    def set_levels(self, lev):
+        """the level of every element of a mesh uploaded non-homogeneous (fh_elem_mesh_set_levels); the mesh's level becomes their maximum"""
+        lev = _i32(lev)
+        if lev.shape != (self.nel,):
+            raise FemusHipError("ElementMesh.set_levels: %s levels for %d elements" % (lev.shape, self.nel))
+        _chk(self.L.fh_elem_mesh_set_levels(self.h, _p(lev) if self.nel else None))
+        ElementMesh.__init__(self, self.ctx, self.h)
+        return self
+
+    def elem_levels(self):
+        """(lev, father, child) of every element, int64: its level, the element of the coarser mesh it came from and which child of it it is (-1: its copy)"""
+        out = [np.empty(self.nel, np.int32) for _ in range(3)]
+        _chk(self.L.fh_elem_mesh_elem_levels(self.h, *[_p(a) if self.nel else None for a in out], None))
+        return tuple(a.astype(np.int64) for a in out)
 
     def arrays(self):
         """(kind, ed, xs, ff, own) as mixed_mesh holds them"""

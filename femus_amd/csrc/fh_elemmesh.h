@@ -32,9 +32,14 @@ struct fh_elem_mesh_s {
   int* d_ed = nullptr;            // [nel * 27], -1 beyond the shape's width
   double* d_x = nullptr;          // [nnode * dim]
   int* d_ff = nullptr;            // [nel * 6], -1 beyond the shape's faces
+  int* d_lev = nullptr;           // [nel] level of every element (a copy of a flagged refinement keeps its own)
+  int* d_father = nullptr;        // [nel] element of the mesh this one was refined from (-1: a mesh built from host arrays)
+  int* d_child = nullptr;         // [nel] which child of its father (-1: its unchanged copy, or no father)
+  unsigned char* d_flags = nullptr;               // [nel] what fh_elem_mesh_flag left (null until then)
+  bool homogeneous = true;        // every element is of the mesh's level
   std::shared_ptr<EmDevTables> tab;               // shared along a chain of refinements
   ~fh_elem_mesh_s() {
-    for (void* q : {(void*)d_geom, (void*)d_ed, (void*)d_x, (void*)d_ff})
+    for (void* q : {(void*)d_geom, (void*)d_ed, (void*)d_x, (void*)d_ff, (void*)d_lev, (void*)d_father, (void*)d_child, (void*)d_flags})
       if (q) hipFree(q);
   }
 };

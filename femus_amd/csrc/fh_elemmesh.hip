@@ -18,8 +18,19 @@
 //      product and every sum rounded on its own (mixed_mesh.py: refine; NOT the ascending-node-id order of the hex path).  The first touch is the child the
 //      host's first_touch calls the creator: the smallest fine element that holds the key.
 // Slot numbers depend on the race; ids, flags and coordinates do not.
+//
+// fh_elem_mesh_refine_flagged -- the same with an AMR flag per element (mixed_mesh.py: refine_flagged; MeshRefinement.cpp:197-493, Elem.hpp:358-370): an element
+// splits when its flag is set and it is of the mesh's level; every other element gives one unchanged copy.  The children of coarse element e start at an
+// exclusive scan of (split ? nch : 1); a first kernel writes every fine element's (father, child, level, shape) and all later ones read them where the
+// uniform path divides by nch.  A copy touches its own nodes, all old, in the first-touch order like any element and enters no hash table (its edges and faces
+// are at least father-sized, a child's new ones half that); the tables are sized from the children alone.  The class widths are scanned over the FINE
+// elements.  The numbers of fine and of split elements per shape -- integer sums, whatever the order -- come back in one copy after the marking pass and size
+// everything else; then the ends of the three classes, as in the uniform path.
+// fh_elem_mesh_flag -- MeshRefinement::FlagElementsToRefine type 1, one thread per element: the vertices added in local order from +0.0, each sum rounded on
+// its own, one division by their number, the expression over (x, y, z, level) at that point (mixed_mesh.py: flag_elements forms the same sum).
 #include "fh_elemmesh.h"
 #include "fh_fe.h"
+#include "fh_expr_device.h"
 #include <cmath>
 #include <mutex>
 
@@ -132,7 +143,9 @@ const EmTables& em_tables() {
 }
 
 struct Scratch {
+  const char* who;                // the entry point, for the message
   std::vector<void*> p;
+  explicit Scratch(const char* w) : who(w) {}
   ~Scratch() {
     for (void* q : p)
       if (q) hipFree(q);
@@ -141,7 +154,7 @@ struct Scratch {
   int get(T** out, size_t n) {
     void* q = nullptr;
     if (hipMalloc(&q, std::max<size_t>(n, 2) * sizeof(T)) != hipSuccess) {
-      fh_set_error("fh_elem_mesh_refine: out of device memory");
+      fh_set_error("%s: out of device memory", who);
       return 2;
     }
     p.push_back(q);
@@ -162,18 +175,85 @@ __global__ __launch_bounds__(256) void k_em_widths(const EmTab* __restrict__ T, 
   w2[e] = T->nl[g] - T->ne[g];
 }
 
+template <bool LINKS>              // LINKS: shape, father and child of every fine element are there (k_em_links); otherwise they are written here
 __global__ __launch_bounds__(256) void k_em_children(const EmTab* __restrict__ T, int nel_f, int nch, const int* __restrict__ geom_c, const int* __restrict__ ed_c,
-                                                     const int* __restrict__ ff_c, int* __restrict__ geom_f, int* __restrict__ ed_f, int* __restrict__ ff_f) {
+                                                     const int* __restrict__ ff_c, int* __restrict__ geom_f, int* __restrict__ ed_f, int* __restrict__ ff_f,
+                                                     int level_f, int* __restrict__ lev_f, int* __restrict__ father_f, int* __restrict__ child_f) {
   const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= (size_t)nel_f * EM_W) return;
-  const int jel = (int)(t / EM_W), i = (int)(t % EM_W), e = jel / nch, j = jel % nch;
+  const int jel = (int)(t / EM_W), i = (int)(t % EM_W);
+  const int e = LINKS ? father_f[jel] : jel / nch, j = LINKS ? child_f[jel] : jel % nch;
   const int g = geom_c[e];
-  if (i == 0) geom_f[jel] = g;
+  if (!LINKS && i == 0) {
+    geom_f[jel] = g;
+    lev_f[jel] = level_f;
+    father_f[jel] = e;
+    child_f[jel] = j;
+  }
+  if (LINKS && j < 0) {           // a copy: its rows as they are, padding included
+    ed_f[t] = ed_c[(size_t)e * EM_W + i];
+    if (i < EM_F) ff_f[(size_t)jel * EM_F + i] = ff_c[(size_t)e * EM_F + i];
+    return;
+  }
   ed_f[t] = i < T->nv[g] ? ed_c[(size_t)e * EM_W + T->f2c[g][j][i]] : -1;
   if (i < EM_F) {
     const int f = i < T->nf[g] ? T->cff[g][j][i] : -1;
     ff_f[(size_t)jel * EM_F + i] = f >= 0 ? ff_c[(size_t)e * EM_F + f] : -1;
   }
+}
+
+// ---- the flagged refinement: marks, links, children and copies ---------------------------------------------------------------------------------------------
+// counts[g] fine elements of shape g, counts[EM_G + g] split elements of shape g: integer sums, a block's in LDS first
+__global__ __launch_bounds__(256) void k_em_mark(int nel, int level, int nch, const int* __restrict__ lev, const unsigned char* __restrict__ flags,
+                                                 const int* __restrict__ geom, int* __restrict__ cnt, int* __restrict__ counts) {
+  __shared__ int part[2 * EM_G];
+  if (threadIdx.x < 2 * EM_G) part[threadIdx.x] = 0;
+  __syncthreads();
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e < nel) {
+    const int split = (flags[e] != 0 && lev[e] == level) ? 1 : 0, g = geom[e];
+    cnt[e] = split ? nch : 1;
+    atomicAdd(&part[g], split ? nch : 1);
+    atomicAdd(&part[EM_G + g], split);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * EM_G && part[threadIdx.x]) atomicAdd(&counts[threadIdx.x], part[threadIdx.x]);
+}
+
+// one thread per (coarse element, j < nch): the fine elements of e are start[e] .. start[e + 1] - 1
+__global__ __launch_bounds__(256) void k_em_links(int nel_c, int nch, int level_f, const int* __restrict__ start, const int* __restrict__ lev_c,
+                                                  const int* __restrict__ geom_c, int* __restrict__ geom_f, int* __restrict__ lev_f, int* __restrict__ father_f,
+                                                  int* __restrict__ child_f) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)nel_c * nch) return;
+  const int e = (int)(t / nch), j = (int)(t % nch);
+  const int s0 = start[e], split = start[e + 1] - s0 > 1;
+  if (!split && j > 0) return;
+  const int f = s0 + j;
+  geom_f[f] = geom_c[e];
+  lev_f[f] = split ? level_f : lev_c[e];
+  father_f[f] = e;
+  child_f[f] = split ? j : -1;
+}
+
+// one thread per element: the mean of its vertices, the expression there
+__global__ __launch_bounds__(256) void k_em_flag_elements(const EmTab* __restrict__ T, int nel, int dim, int level, const int* __restrict__ geom, const int* __restrict__ ed,
+                                                          const double* __restrict__ x, const int* __restrict__ lev, const int* __restrict__ code, int ncode,
+                                                          const double* __restrict__ consts, unsigned char* __restrict__ flags) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= nel) return;
+  if (lev[e] != level) {
+    flags[e] = 0;
+    return;
+  }
+  const int nv = T->nv[geom[e]];
+  double v[4] = {0.0, 0.0, 0.0, (double)level};
+  for (int k = 0; k < nv; k++) {
+    const double* p = x + (size_t)ed[(size_t)e * EM_W + k] * dim;
+    for (int d = 0; d < dim; d++) v[d] = __dadd_rn(v[d], p[d]);
+  }
+  for (int d = 0; d < dim; d++) v[d] = __ddiv_rn(v[d], (double)nv);
+  flags[e] = fhx_truth(fh_expr_device_eval(code, ncode, consts, v)) != 0.0 ? 1 : 0;
 }
 
 // plain read, then CAS, then the returned value: a stale plain read can only show "empty", and the CAS corrects it (fh_meshdev.hip: rf_insert)
@@ -192,11 +272,24 @@ __device__ __forceinline__ int em_insert(unsigned long long* keys, unsigned mask
 __device__ __forceinline__ unsigned long long em_pair(int a, int b) { return ((unsigned long long)(unsigned)a << 32) | (unsigned)b; }
 
 struct EmOcc {                    // the order (class, fine element, local node)
-  const int *o0, *o1, *o2;        // exclusive scans of the class widths over the coarse elements
+  const int *o0, *o1, *o2;        // exclusive scans of the class widths over the coarse elements (LINKS: over the fine elements)
   int base1, base2, nch;
+  const int *father, *child;      // LINKS: of every fine element
 };
-__device__ __forceinline__ int em_occ(const EmTab* T, const EmOcc& O, int g, int e, int j, int i) {
+template <bool LINKS>
+__device__ __forceinline__ void em_who(const EmOcc& O, int jel, int& e, int& j) {
+  if (LINKS) {
+    e = O.father[jel];
+    j = O.child[jel];
+  } else {
+    e = jel / O.nch;
+    j = jel % O.nch;
+  }
+}
+template <bool LINKS>
+__device__ __forceinline__ int em_occ(const EmTab* T, const EmOcc& O, int g, int jel, int e, int j, int i) {
   const int nv = T->nv[g], ne = T->ne[g];
+  if (LINKS) return i < nv ? O.o0[jel] + i : i < ne ? O.base1 + O.o1[jel] + (i - nv) : O.base2 + O.o2[jel] + (i - ne);
   if (i < nv) return O.nch * O.o0[e] + j * nv + i;
   if (i < ne) return O.base1 + O.nch * O.o1[e] + j * (ne - nv) + (i - nv);
   return O.base2 + O.nch * O.o2[e] + j * (T->nl[g] - ne) + (i - ne);
@@ -208,6 +301,7 @@ struct EmHash {
   int shift, id0;                 // id0: the first provisional id of the family
 };
 
+template <bool LINKS>
 __global__ __launch_bounds__(256) void k_em_touch(const EmTab* __restrict__ T, EmOcc O, int nel_f, const int* __restrict__ geom_f, const int* __restrict__ ed_f,
                                                   EmHash E, EmHash TR, EmHash Q, int C0, int* __restrict__ first, int* __restrict__ ident) {
   const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -217,8 +311,10 @@ __global__ __launch_bounds__(256) void k_em_touch(const EmTab* __restrict__ T, E
   const int nv = T->nv[g], ne = T->ne[g], nl = T->nl[g];
   if (i >= nl) return;
   const int* fd = ed_f + (size_t)jel * EM_W;
+  int e, j;
+  em_who<LINKS>(O, jel, e, j);
   int id;
-  if (i < nv) {
+  if (i < nv || (LINKS && j < 0)) {             // a coarse node: a child's vertex, any node of a copy
     id = fd[i];
   } else if (i < ne) {
     int a = fd[T->edge_v[g][i - nv][0]], b = fd[T->edge_v[g][i - nv][1]];
@@ -243,7 +339,7 @@ __global__ __launch_bounds__(256) void k_em_touch(const EmTab* __restrict__ T, E
   } else {
     id = C0 + jel;
   }
-  const int occ = em_occ(T, O, g, jel / O.nch, jel % O.nch, i);
+  const int occ = em_occ<LINKS>(T, O, g, jel, e, j, i);
   ident[occ] = id;
   atomicMin(&first[id], occ);
 }
@@ -253,6 +349,7 @@ __global__ __launch_bounds__(256) void k_em_flag(int nocc, const int* __restrict
   if (occ < nocc) flag[occ] = first[ident[occ]] == occ;
 }
 
+template <bool LINKS>
 __global__ __launch_bounds__(256) void k_em_number(const EmTab* __restrict__ T, EmOcc O, int nel_f, int dim, const int* __restrict__ geom_f, const int* __restrict__ first,
                                                    const int* __restrict__ ident, const int* __restrict__ pos, const int* __restrict__ ed_c,
                                                    const double* __restrict__ xc, const double* __restrict__ EP, int* __restrict__ ed_f, double* __restrict__ xf) {
@@ -262,14 +359,15 @@ __global__ __launch_bounds__(256) void k_em_number(const EmTab* __restrict__ T, 
   const int g = geom_f[jel];
   const int nl = T->nl[g];
   if (i >= nl) return;
-  const int e = jel / O.nch, j = jel % O.nch;
-  const int occ = em_occ(T, O, g, e, j, i);
+  int e, j;
+  em_who<LINKS>(O, jel, e, j);
+  const int occ = em_occ<LINKS>(T, O, g, jel, e, j, i);
   const int node = ident[occ], fo = first[node];
   const int id = pos[fo];
   ed_f[t] = id;
   if (fo != occ) return;
   double s[3] = {0.0, 0.0, 0.0};
-  if (i < T->nv[g]) {             // a coarse node keeps its coordinates
+  if (i < T->nv[g] || (LINKS && j < 0)) {       // a coarse node keeps its coordinates
     for (int d = 0; d < dim; d++) s[d] = xc[(size_t)node * dim + d];
   } else {
     const double* row = EP + T->ep[g] + ((size_t)j * nl + i) * nl;
@@ -293,6 +391,9 @@ static int em_alloc(fh_elem_mesh_s* m, bool coords) {
   FH_TRY(get((void**)&m->d_geom, (size_t)m->nel * sizeof(int)));
   FH_TRY(get((void**)&m->d_ed, (size_t)m->nel * EM_W * sizeof(int)));
   FH_TRY(get((void**)&m->d_ff, (size_t)m->nel * EM_F * sizeof(int)));
+  FH_TRY(get((void**)&m->d_lev, (size_t)m->nel * sizeof(int)));
+  FH_TRY(get((void**)&m->d_father, (size_t)m->nel * sizeof(int)));
+  FH_TRY(get((void**)&m->d_child, (size_t)m->nel * sizeof(int)));
   if (coords) FH_TRY(get((void**)&m->d_x, (size_t)m->nnode * m->dim * sizeof(double)));
   return 0;
 }
@@ -338,6 +439,9 @@ extern "C" int fh_elem_mesh_create(fh_ctx_t ctx, int dim, int nel, int nnode, co
     FH_CHECK_HIP(hipMemcpyAsync(m->d_geom, elem_geom, (size_t)nel * sizeof(int), hipMemcpyHostToDevice, st));
     FH_CHECK_HIP(hipMemcpyAsync(m->d_ed, elem_dof, (size_t)nel * EM_W * sizeof(int), hipMemcpyHostToDevice, st));
     FH_CHECK_HIP(hipMemcpyAsync(m->d_ff, face_flag, (size_t)nel * EM_F * sizeof(int), hipMemcpyHostToDevice, st));
+    FH_CHECK_HIP(hipMemsetAsync(m->d_lev, 0, (size_t)nel * sizeof(int), st));               // level 0, no father
+    FH_CHECK_HIP(hipMemsetAsync(m->d_father, 0xFF, (size_t)nel * sizeof(int), st));
+    FH_CHECK_HIP(hipMemsetAsync(m->d_child, 0xFF, (size_t)nel * sizeof(int), st));
   }
   if (nnode) FH_CHECK_HIP(hipMemcpyAsync(m->d_x, coords, (size_t)nnode * dim * sizeof(double), hipMemcpyHostToDevice, st));
   FH_CHECK_HIP(hipStreamSynchronize(st));       // the caller's arrays are free again
@@ -346,9 +450,11 @@ extern "C" int fh_elem_mesh_create(fh_ctx_t ctx, int dim, int nel, int nnode, co
   FH_GUARD_END("fh_elem_mesh_create")
 }
 
-extern "C" int fh_elem_mesh_refine(fh_elem_mesh_t C, fh_elem_mesh_t* out) {
-  FH_GUARD_BEGIN
-  FH_REQUIRE(C && out, "fh_elem_mesh_refine: null argument");
+// What both refinements do once the number of fine elements of every shape is known (F->nel, F->count; `fresh`: the children among them, who alone make keys):
+// sizes and refusals, the fine mesh's arrays, tables, first touches, numbering, coordinates.  LINKS: the fine elements of coarse element e start at d_start[e]
+// and are its children or its copy; otherwise fine element nch e + j is child j of e.
+template <bool LINKS>
+static int em_refine_finish(const char* who, fh_elem_mesh_t C, fh_elem_mesh_s* F, const int64_t fresh[EM_G], const int* d_start, Scratch& B) {
   const EmTab& H = em_tables().h;
   fh_ctx_t ctx = C->ctx;
   hipStream_t st = ctx->stream;
@@ -356,16 +462,16 @@ extern "C" int fh_elem_mesh_refine(fh_elem_mesh_t C, fh_elem_mesh_t* out) {
   // every size follows from the number of elements of each shape
   int64_t W[3] = {0, 0, 0}, nE = 0, nT = 0, nQ = 0;
   for (int g = 0; g < EM_G; g++) {
-    const int64_t n = C->count[g] * nch;
+    const int64_t n = F->count[g];
     if (!n) continue;
     W[0] += n * H.nv[g];
     W[1] += n * (H.ne[g] - H.nv[g]);
     W[2] += n * (H.nl[g] - H.ne[g]);
+    nE += fresh[g] * (H.ne[g] - H.nv[g]);
     if (dim == 3)
-      for (int f = 0; f < H.nf[g]; f++) (H.nvf[g][f] == 3 ? nT : nQ) += n;
+      for (int f = 0; f < H.nf[g]; f++) (H.nvf[g][f] == 3 ? nT : nQ) += fresh[g];
   }
-  nE = W[1];
-  const int64_t nel_f64 = (int64_t)nel_c * nch, nocc64 = W[0] + W[1] + W[2];
+  const int64_t nel_f64 = F->nel, nocc64 = W[0] + W[1] + W[2];
   auto log2cap = [](int64_t nkeys) {            // every key fits with load <= 1/2 even if no edge or face were shared
     int l = 6;
     while (((int64_t)1 << l) < 2 * nkeys) l++;
@@ -373,22 +479,18 @@ extern "C" int fh_elem_mesh_refine(fh_elem_mesh_t C, fh_elem_mesh_t* out) {
   };
   const int lE = log2cap(nE), lT = log2cap(nT), lQ = log2cap(nQ);
   const int64_t nident64 = (int64_t)C->nnode + ((int64_t)1 << lE) + ((int64_t)1 << lT) + ((int64_t)1 << lQ) + nel_f64;
-  FH_REQUIRE(nocc64 < (int64_t)EM_NONE && nel_f64 * EM_W < ((int64_t)1 << 31),
-             "fh_elem_mesh_refine: the %lld fine elements' first-touch order does not fit 32-bit integers", (long long)nel_f64);
-  FH_REQUIRE(nident64 < (int64_t)EM_NONE, "fh_elem_mesh_refine: the node table of %lld fine elements does not fit 32-bit ids", (long long)nel_f64);
-  const int nel_f = (int)nel_f64, nocc = (int)nocc64;
+  FH_REQUIRE(nocc64 < (int64_t)EM_NONE && nel_f64 * EM_W < ((int64_t)1 << 31), "%s: the %lld fine elements' first-touch order does not fit 32-bit integers", who,
+             (long long)nel_f64);
+  FH_REQUIRE(nident64 < (int64_t)EM_NONE, "%s: the node table of %lld fine elements does not fit 32-bit ids", who, (long long)nel_f64);
+  const int nel_f = F->nel, nocc = (int)nocc64;
   const size_t capE = (size_t)1 << lE, capT = (size_t)1 << lT, capQ = (size_t)1 << lQ, nident = (size_t)nident64, nthr = (size_t)nel_f * EM_W;
+  FH_TRY(em_alloc(F, false));
 
-  std::unique_ptr<fh_elem_mesh_s> F(new fh_elem_mesh_s());
-  F->ctx = ctx; F->dim = dim; F->nel = nel_f; F->level = C->level + 1; F->tab = C->tab;
-  for (int g = 0; g < EM_G; g++) F->count[g] = C->count[g] * nch;
-  FH_TRY(em_alloc(F.get(), false));
-
-  Scratch B;
   int *d_w, *d_off, *d_bsum, *d_first, *d_ident, *d_flag;
   unsigned long long *d_kE, *d_kT, *d_kQ;
-  const size_t nw = (size_t)nel_c + 1;
-  if (B.get(&d_w, 3 * nw) || B.get(&d_off, 3 * nw) || B.get(&d_bsum, (size_t)std::max(nocc, nel_c) / FH_SCAN_BLOCK + 2) || B.get(&d_first, nident) ||
+  const int nscan = LINKS ? nel_f : nel_c;      // the class widths are scanned over the fine elements, or over the coarse ones (children are consecutive)
+  const size_t nw = (size_t)nscan + 1;
+  if (B.get(&d_w, 3 * nw) || B.get(&d_off, 3 * nw) || B.get(&d_bsum, (size_t)std::max(nocc, nscan) / FH_SCAN_BLOCK + 2) || B.get(&d_first, nident) ||
       B.get(&d_ident, (size_t)nocc) || B.get(&d_flag, (size_t)nocc + 1) || B.get(&d_kE, capE) || B.get(&d_kT, capT) || B.get(&d_kQ, capQ))
     return 2;
   if (ctx->debug_poison) {
@@ -401,20 +503,26 @@ extern "C" int fh_elem_mesh_refine(fh_elem_mesh_t C, fh_elem_mesh_t* out) {
   FH_CHECK_HIP(hipMemsetAsync(d_kQ, 0xFF, capQ * sizeof(unsigned long long), st));
   FH_CHECK_HIP(hipMemsetAsync(d_first, 0x7f, nident * sizeof(int), st));
   const EmTab* dT = C->tab->d_tab;
-  if (nel_c) hipLaunchKernelGGL(k_em_widths, dim3(fh_div_up(nel_c, 256)), dim3(256), 0, st, dT, nel_c, C->d_geom, d_w, d_w + nw, d_w + 2 * nw);
-  for (int c = 0; c < 3; c++) FH_TRY(fh_device_exclusive_scan(st, d_w + c * nw, d_off + c * nw, nel_c, d_bsum));
-  EmOcc O{d_off, d_off + nw, d_off + 2 * nw, (int)W[0], (int)(W[0] + W[1]), nch};
+  if (LINKS && nel_c)
+    hipLaunchKernelGGL(k_em_links, dim3((unsigned)(((size_t)nel_c * nch + 255) / 256)), dim3(256), 0, st, nel_c, nch, F->level, d_start, C->d_lev, C->d_geom, F->d_geom,
+                       F->d_lev, F->d_father, F->d_child);
+  if (nscan)
+    hipLaunchKernelGGL(k_em_widths, dim3(fh_div_up(nscan, 256)), dim3(256), 0, st, dT, nscan, LINKS ? F->d_geom : C->d_geom, d_w, d_w + nw, d_w + 2 * nw);
+  FH_CHECK_HIP(hipGetLastError());
+  for (int c = 0; c < 3; c++) FH_TRY(fh_device_exclusive_scan(st, d_w + c * nw, d_off + c * nw, nscan, d_bsum));
+  EmOcc O{d_off, d_off + nw, d_off + 2 * nw, (int)W[0], (int)(W[0] + W[1]), nch, F->d_father, F->d_child};
   const int E0 = C->nnode, T0 = E0 + (int)capE, Q0 = T0 + (int)capT, C0 = Q0 + (int)capQ;
   EmHash hE{d_kE, (unsigned)(capE - 1), 64 - lE, E0}, hT{d_kT, (unsigned)(capT - 1), 64 - lT, T0}, hQ{d_kQ, (unsigned)(capQ - 1), 64 - lQ, Q0};
   const unsigned gb = (unsigned)((nthr + 255) / 256);
   if (nel_f) {
-    hipLaunchKernelGGL(k_em_children, dim3(gb), dim3(256), 0, st, dT, nel_f, nch, C->d_geom, C->d_ed, C->d_ff, F->d_geom, F->d_ed, F->d_ff);
-    hipLaunchKernelGGL(k_em_touch, dim3(gb), dim3(256), 0, st, dT, O, nel_f, F->d_geom, F->d_ed, hE, hT, hQ, C0, d_first, d_ident);
+    hipLaunchKernelGGL(k_em_children<LINKS>, dim3(gb), dim3(256), 0, st, dT, nel_f, nch, C->d_geom, C->d_ed, C->d_ff, F->d_geom, F->d_ed, F->d_ff, F->level,
+                       F->d_lev, F->d_father, F->d_child);
+    hipLaunchKernelGGL(k_em_touch<LINKS>, dim3(gb), dim3(256), 0, st, dT, O, nel_f, F->d_geom, F->d_ed, hE, hT, hQ, C0, d_first, d_ident);
     hipLaunchKernelGGL(k_em_flag, dim3(fh_div_up(nocc, 256)), dim3(256), 0, st, nocc, d_first, d_ident, d_flag);
   }
   FH_CHECK_HIP(hipGetLastError());
   FH_TRY(fh_device_exclusive_scan(st, d_flag, d_flag, nocc, d_bsum));
-  // the only numbers that come back: the ends of the three classes (the last one sizes the coordinates)
+  // the numbers that come back: the ends of the three classes (the last one sizes the coordinates)
   int own[3] = {0, 0, 0};
   FH_CHECK_HIP(hipMemcpyAsync(&own[0], d_flag + O.base1, sizeof(int), hipMemcpyDeviceToHost, st));
   FH_CHECK_HIP(hipMemcpyAsync(&own[1], d_flag + O.base2, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -425,13 +533,148 @@ extern "C" int fh_elem_mesh_refine(fh_elem_mesh_t C, fh_elem_mesh_t* out) {
   FH_CHECK_HIP(hipMalloc((void**)&F->d_x, std::max<size_t>((size_t)F->nnode * dim, 1) * sizeof(double)));
   if (ctx->debug_poison) FH_CHECK_HIP(hipMemsetAsync(F->d_x, 0xFF, std::max<size_t>((size_t)F->nnode * dim, 1) * sizeof(double), st));
   if (nel_f)
-    hipLaunchKernelGGL(k_em_number, dim3(gb), dim3(256), 0, st, dT, O, nel_f, dim, F->d_geom, d_first, d_ident, d_flag, C->d_ed, C->d_x, C->tab->d_EP, F->d_ed,
+    hipLaunchKernelGGL(k_em_number<LINKS>, dim3(gb), dim3(256), 0, st, dT, O, nel_f, dim, F->d_geom, d_first, d_ident, d_flag, C->d_ed, C->d_x, C->tab->d_EP, F->d_ed,
                        F->d_x);
   FH_CHECK_HIP(hipGetLastError());
   FH_CHECK_HIP(hipStreamSynchronize(st));       // the scratch is freed on return
+  return 0;
+}
+
+extern "C" int fh_elem_mesh_refine(fh_elem_mesh_t C, fh_elem_mesh_t* out) {
+  FH_GUARD_BEGIN
+  const char* who = "fh_elem_mesh_refine";
+  FH_REQUIRE(C && out, "%s: null argument", who);
+  FH_REQUIRE(C->homogeneous, "%s: the mesh of level %d holds elements of older levels (a flagged refinement or set_levels): refine it with flags "
+             "(fh_elem_mesh_refine_flagged), which leaves them alone", who, C->level);
+  const int nch = C->dim == 3 ? 8 : 4;
+  FH_REQUIRE((int64_t)C->nel * nch * EM_W < ((int64_t)1 << 31), "%s: the %lld fine elements' first-touch order does not fit 32-bit integers", who,
+             (long long)C->nel * nch);
+  std::unique_ptr<fh_elem_mesh_s> F(new fh_elem_mesh_s());
+  F->ctx = C->ctx; F->dim = C->dim; F->nel = C->nel * nch; F->level = C->level + 1; F->tab = C->tab;
+  int64_t fresh[EM_G];
+  for (int g = 0; g < EM_G; g++) fresh[g] = F->count[g] = C->count[g] * nch;
+  Scratch B(who);
+  FH_TRY(em_refine_finish<false>(who, C, F.get(), fresh, nullptr, B));
   *out = F.release();
   return 0;
   FH_GUARD_END("fh_elem_mesh_refine")
+}
+
+extern "C" int fh_elem_mesh_refine_flagged(fh_elem_mesh_t C, const unsigned char* flags, fh_elem_mesh_t* out) {
+  FH_GUARD_BEGIN
+  const char* who = "fh_elem_mesh_refine_flagged";
+  FH_REQUIRE(C && out, "%s: null argument", who);
+  FH_REQUIRE(flags || C->d_flags, "%s: no flags given and none resident on the mesh (fh_elem_mesh_flag leaves them)", who);
+  fh_ctx_t ctx = C->ctx;
+  hipStream_t st = ctx->stream;
+  const int nch = C->dim == 3 ? 8 : 4, nel_c = C->nel;
+  FH_REQUIRE((int64_t)nel_c * nch < ((int64_t)1 << 31), "%s: the children of %d elements do not fit 32-bit integers", who, nel_c);
+  Scratch B(who);
+  int *d_cnt, *d_start, *d_counts, *d_bsum;
+  unsigned char* d_fl = nullptr;
+  const size_t nwc = (size_t)nel_c + 1;
+  if (B.get(&d_cnt, nwc) || B.get(&d_start, nwc) || B.get(&d_counts, (size_t)2 * EM_G) || B.get(&d_bsum, (size_t)nel_c / FH_SCAN_BLOCK + 2)) return 2;
+  if (flags) {
+    if (B.get(&d_fl, (size_t)nel_c + 8)) return 2;
+    if (nel_c) FH_CHECK_HIP(hipMemcpyAsync(d_fl, flags, (size_t)nel_c, hipMemcpyHostToDevice, st));
+  }
+  if (ctx->debug_poison) FH_CHECK_HIP(hipMemsetAsync(d_start, 0xFF, nwc * sizeof(int), st));
+  FH_CHECK_HIP(hipMemsetAsync(d_counts, 0, 2 * EM_G * sizeof(int), st));
+  if (nel_c)
+    hipLaunchKernelGGL(k_em_mark, dim3(fh_div_up(nel_c, 256)), dim3(256), 0, st, nel_c, C->level, nch, C->d_lev, flags ? d_fl : C->d_flags, C->d_geom, d_cnt, d_counts);
+  FH_CHECK_HIP(hipGetLastError());
+  FH_TRY(fh_device_exclusive_scan(st, d_cnt, d_start, nel_c, d_bsum));
+  // the first numbers that come back: the fine and the split elements of every shape; every size follows from them
+  int counts[2 * EM_G];
+  FH_CHECK_HIP(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, st));
+  FH_CHECK_HIP(hipStreamSynchronize(st));
+  std::unique_ptr<fh_elem_mesh_s> F(new fh_elem_mesh_s());
+  F->ctx = ctx; F->dim = C->dim; F->level = C->level + 1; F->tab = C->tab;
+  int64_t fresh[EM_G], nel_f = 0, nsplit = 0;
+  for (int g = 0; g < EM_G; g++) {
+    F->count[g] = counts[g];
+    fresh[g] = (int64_t)counts[EM_G + g] * nch;
+    nel_f += counts[g];
+    nsplit += counts[EM_G + g];
+  }
+  F->nel = (int)nel_f;            // at most nch * nel_c
+  F->homogeneous = nsplit == nel_c;
+  FH_TRY(em_refine_finish<true>(who, C, F.get(), fresh, d_start, B));
+  *out = F.release();
+  return 0;
+  FH_GUARD_END("fh_elem_mesh_refine_flagged")
+}
+
+extern "C" int fh_elem_mesh_flag(fh_elem_mesh_t m, fh_expr_t expr, unsigned char* flags) {
+  FH_GUARD_BEGIN
+  const char* who = "fh_elem_mesh_flag";
+  FH_REQUIRE(m && expr, "%s: null argument", who);
+  std::vector<int> code;
+  std::vector<double> consts;
+  FH_TRY(fh_expr_fetch(expr, "fh_elem_mesh_flag: the flag expression", 4, code, consts));       // x, y, z, level
+  if (consts.empty()) consts.resize(1, 0.0);
+  hipStream_t st = m->ctx->stream;
+  const size_t nbytes = std::max<size_t>((size_t)m->nel, 8);
+  if (!m->d_flags) FH_CHECK_HIP(hipMalloc((void**)&m->d_flags, nbytes));
+  auto drop = [&]() {             // flags of a pass that failed are no flags: refine("resident") refuses
+    hipFree(m->d_flags);
+    m->d_flags = nullptr;
+  };
+  Scratch B(who);
+  int* d_code;
+  double* d_k;
+  if (B.get(&d_code, code.size()) || B.get(&d_k, consts.size())) {
+    drop();
+    return 2;
+  }
+  auto run = [&]() -> int {
+    if (m->ctx->debug_poison) FH_CHECK_HIP(hipMemsetAsync(m->d_flags, 0xFF, nbytes, st));        // every entry is written before it is read
+    if (!code.empty()) FH_CHECK_HIP(hipMemcpyAsync(d_code, code.data(), code.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    FH_CHECK_HIP(hipMemcpyAsync(d_k, consts.data(), consts.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if (m->nel)
+      hipLaunchKernelGGL(k_em_flag_elements, dim3(fh_div_up(m->nel, 256)), dim3(256), 0, st, m->tab->d_tab, m->nel, m->dim, m->level, m->d_geom, m->d_ed, m->d_x,
+                         m->d_lev, d_code, (int)code.size(), d_k, m->d_flags);
+    FH_CHECK_HIP(hipGetLastError());
+    if (flags && m->nel) FH_CHECK_HIP(hipMemcpyAsync(flags, m->d_flags, (size_t)m->nel, hipMemcpyDeviceToHost, st));
+    return 0;
+  };
+  const int rc = run();
+  const hipError_t hs = hipStreamSynchronize(st);       // the program is freed on return
+  if (rc || hs != hipSuccess) drop();
+  if (rc) return rc;
+  FH_CHECK_HIP(hs);
+  return 0;
+  FH_GUARD_END("fh_elem_mesh_flag")
+}
+
+extern "C" int fh_elem_mesh_set_levels(fh_elem_mesh_t m, const int* lev) {
+  FH_REQUIRE(m && (lev || m->nel == 0), "fh_elem_mesh_set_levels: null argument");
+  if (!m->nel) return 0;
+  int top = 0;
+  for (int e = 0; e < m->nel; e++) {
+    FH_REQUIRE(lev[e] >= 0, "fh_elem_mesh_set_levels: element %d has level %d", e, lev[e]);
+    top = std::max(top, lev[e]);
+  }
+  bool same = true;
+  for (int e = 0; e < m->nel; e++) same = same && lev[e] == top;
+  hipStream_t st = m->ctx->stream;
+  FH_CHECK_HIP(hipMemcpyAsync(m->d_lev, lev, (size_t)m->nel * sizeof(int), hipMemcpyHostToDevice, st));
+  FH_CHECK_HIP(hipStreamSynchronize(st));       // the caller's array is free again
+  m->level = top;
+  m->homogeneous = same;
+  return 0;
+}
+
+extern "C" int fh_elem_mesh_elem_levels(fh_elem_mesh_t m, int* lev, int* father, int* child, int* homogeneous) {
+  FH_REQUIRE(m, "fh_elem_mesh_elem_levels: null mesh");
+  hipStream_t st = m->ctx->stream;
+  if (homogeneous) *homogeneous = m->homogeneous ? 1 : 0;
+  if (!m->nel || !(lev || father || child)) return 0;
+  if (lev) FH_CHECK_HIP(hipMemcpyAsync(lev, m->d_lev, (size_t)m->nel * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (father) FH_CHECK_HIP(hipMemcpyAsync(father, m->d_father, (size_t)m->nel * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (child) FH_CHECK_HIP(hipMemcpyAsync(child, m->d_child, (size_t)m->nel * sizeof(int), hipMemcpyDeviceToHost, st));
+  FH_CHECK_HIP(hipStreamSynchronize(st));
+  return 0;
 }
 
 extern "C" int fh_elem_mesh_info(fh_elem_mesh_t m, int* dim, int* nel, int* nnode, int own[3], int* level) {

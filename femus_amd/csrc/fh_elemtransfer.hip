@@ -9,13 +9,17 @@
 //   1. fine dof -> the entries (fine element, local node) that hold it: the counting pass of fh_mat_create_from_elements (fh_dof_lists_build).  The order
 //      inside a list depends on the race; nothing below does.
 //   2. one wave per fine row, twice (lengths, then columns and values; the host scans the lengths in between as for every device-built pattern).  An entry
-//      (f, n) of the row gives the candidates k = 0 .. nc - 1 with a non-zero weight: column ed_c[f / nch][k] and the 64-bit ORDER KEY
-//      (rank of the shape, j = f % nch, n, k, e = f / nch), which no two candidates share.  The wave packs the candidates into LDS, sorts them by
+//      (f, n) of the row gives the candidates k = 0 .. nc - 1 with a non-zero weight: column ed_c[e][k] and the 64-bit ORDER KEY
+//      (rank of the shape, j, n, k, e), which no two candidates share; e = father[f], j = child[f], after a uniform refinement f / nch and f % nch.  The wave packs the candidates into LDS, sorts them by
 //      (column, key) -- a bitonic network, columns alone in the first pass -- and the last candidate of every run of equal columns is the entry: the
 //      insertion that came last.  Its value is read off its key (the weight EP_s[j][n][k]); no value is ever added, compared or touched by an atomic.
 //   3. a row whose entries hold more than `elem_transfer_lds_rows` candidate slots (27 per entry; 1024 at most) does not fit the wave's LDS: the host, which
 //      has the list lengths anyway, gives each such row a piece of global scratch, and one workgroup per row writes the candidates there, marks the one with
 //      the largest key of its column by comparing all pairs, and places it at the number of marked candidates with a smaller column.  Same rule, same bits.
+// A FLAGGED fine level (fh_elem_mesh_refine_flagged) is read through its links: fine element f is child j = child[f] of e = father[f], or its unchanged copy
+// (j = -1).  An entry (f, n) of a copy gives the single candidate k = n with the value 1.0 exactly, column ed_c[e][n] (LinearImplicitSystem.cpp:761-811); the
+// copies' insertions come after those of every child of every shape, ordered (shape, n, e), so a node a copy shares with a refined neighbour keeps the 1.0
+// (app_poisson.py: _prolongator_from_links).  The high word of the order key, from the top: copy (1 bit), rank of the shape (3), j (4), n (5), k (5).
 // The weights of the shapes present (family fe, |.| < 1e-14 already zero: fhfe::elem_prolongator) go up once per call.
 //
 // fh_elem_mesh_boundary_dofs -- one thread per (element, face, face node) marks the dof when the face's flag is one of the caller's; an exclusive scan of the
@@ -37,8 +41,8 @@ struct EtArgs {
   EtTab T;
   const double* EP;
   const int *aptr, *adj;          // fine dof -> entries f * 27 + n
-  const int *geom_f, *ed_c;
-  int m, ncols, nch;
+  const int *geom_f, *ed_c, *father, *child;    // of the fine elements
+  int m, ncols;
   int* err;
 };
 struct EtFaces {
@@ -51,18 +55,19 @@ __device__ __forceinline__ bool et_candidate(const EtArgs& A, int entry, int k, 
   const int f = entry / EM_W, n = entry % EM_W;
   const int g = A.geom_f[f], nc = A.T.nc[g];
   if (k >= nc || n >= nc) return false;
-  const int e = f / A.nch, j = f % A.nch;
-  if (A.EP[A.T.ep[g] + (j * nc + n) * nc + k] == 0.0) return false;
+  const int e = A.father[f], j = A.child[f];
+  if (j < 0 ? k != n : A.EP[A.T.ep[g] + (j * nc + n) * nc + k] == 0.0) return false;
   col = A.ed_c[(size_t)e * EM_W + k];
   if (col < 0 || col >= A.ncols) {              // not a mesh whose families own the leading ids: refused after the pass
     atomicExch(A.err, 1);
     return false;
   }
-  key = ((et_key)(((A.T.rank[g] * 8 + j) * 32 + n) * 32 + k) << 32) | (unsigned)e;
+  key = ((et_key)(((((j < 0 ? 8 : 0) + A.T.rank[g]) * 16 + (j < 0 ? 0 : j)) * 32 + n) * 32 + k) << 32) | (unsigned)e;
   return true;
 }
 __device__ __forceinline__ double et_value(const EtArgs& A, et_key key) {
-  const int c = (int)(key >> 32), k = c & 31, n = (c >> 5) & 31, j = (c >> 10) & 7, g = A.T.shape[c >> 13];
+  const int c = (int)(key >> 32), k = c & 31, n = (c >> 5) & 31, j = (c >> 10) & 15, g = A.T.shape[(c >> 14) & 7];
+  if (c >> 17) return 1.0;        // a copy
   return A.EP[A.T.ep[g] + (j * A.T.nc[g] + n) * A.T.nc[g] + k];
 }
 
@@ -252,25 +257,43 @@ extern "C" int fh_elem_mesh_prolongator(fh_elem_mesh_t C, fh_elem_mesh_t F, int 
   FH_REQUIRE(C->dim == F->dim, "%s: a %d-dimensional coarse and a %d-dimensional fine mesh", who, C->dim, F->dim);
   FH_REQUIRE(F->level == C->level + 1, "%s: the fine mesh is of level %d, the coarse one of level %d: not its refinement", who, F->level, C->level);
   const int nch = C->dim == 3 ? 8 : 4;
-  FH_REQUIRE((int64_t)F->nel == (int64_t)nch * C->nel, "%s: %d fine elements are not the %d children of each of %d coarse elements", who, F->nel, nch, C->nel);
-  for (int g = 0; g < EM_G; g++)
-    FH_REQUIRE(F->count[g] == nch * C->count[g], "%s: %lld fine elements of shape code %d are not the children of %lld coarse ones", who, (long long)F->count[g], g,
-               (long long)C->count[g]);
   fh_ctx_t ctx = C->ctx;
   hipStream_t st = ctx->stream;
-  {   // child j of e has the shape of e: two copies, no launch
-    std::vector<int> gc((size_t)C->nel), gf((size_t)F->nel);
-    if (C->nel) {
-      FH_CHECK_HIP(hipMemcpyAsync(gc.data(), C->d_geom, gc.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  {   // the links of the fine elements against the coarse mesh: four copies, no launch
+    std::vector<int> gc((size_t)C->nel), gf((size_t)F->nel), fa((size_t)F->nel), ch((size_t)F->nel);
+    if (C->nel) FH_CHECK_HIP(hipMemcpyAsync(gc.data(), C->d_geom, gc.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (F->nel) {
       FH_CHECK_HIP(hipMemcpyAsync(gf.data(), F->d_geom, gf.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+      FH_CHECK_HIP(hipMemcpyAsync(fa.data(), F->d_father, fa.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+      FH_CHECK_HIP(hipMemcpyAsync(ch.data(), F->d_child, ch.size() * sizeof(int), hipMemcpyDeviceToHost, st));
     }
     FH_CHECK_HIP(hipStreamSynchronize(st));
-    for (int e = 0; e < C->nel; e++) {
-      FH_REQUIRE(et_shape(gc[e]), "%s: coarse element %d has shape code %d", who, e, gc[e]);
-      for (int j = 0; j < nch; j++)
-        FH_REQUIRE(gf[(size_t)nch * e + j] == gc[e], "%s: fine element %d has shape code %d, its father %d shape code %d: not its refinement", who, nch * e + j,
-                   gf[(size_t)nch * e + j], e, gc[e]);
+    for (int e = 0; e < C->nel; e++) FH_REQUIRE(et_shape(gc[e]), "%s: coarse element %d has shape code %d", who, e, gc[e]);
+    std::vector<unsigned> seen((size_t)C->nel, 0);           // per coarse element: bit j = child j met, bit nch = its copy met
+    for (int f = 0; f < F->nel; f++) {
+      FH_REQUIRE(fa[f] >= 0 && fa[f] < C->nel && ch[f] >= -1 && ch[f] < nch,
+                 "%s: fine element %d is child %d of element %d, the coarse mesh has %d elements: not its refinement", who, f, ch[f], fa[f], C->nel);
+      const unsigned bit = 1u << (ch[f] < 0 ? nch : ch[f]);
+      FH_REQUIRE(!(seen[fa[f]] & bit), "%s: coarse element %d has two fine elements that are its child %d: not its refinement", who, fa[f], ch[f]);
+      seen[fa[f]] |= bit;
     }
+    int64_t nsplit = 0, fine_of[EM_G] = {0, 0, 0, 0, 0, 0};
+    for (int e = 0; e < C->nel; e++) {
+      const bool split = seen[e] != (1u << nch);
+      FH_REQUIRE(seen[e], "%s: coarse element %d has neither children nor a copy among the fine elements: not its refinement", who, e);
+      FH_REQUIRE(!split || seen[e] == (1u << nch) - 1u, "%s: coarse element %d has a copy and children, or not all of its %d children: not its refinement", who, e,
+                 nch);
+      nsplit += split;
+      fine_of[gc[e]] += split ? nch : 1;
+    }
+    FH_REQUIRE((int64_t)F->nel == (int64_t)C->nel + (nch - 1) * nsplit,
+               "%s: %d fine elements are not the %d children of each of %lld coarse elements and the copies of the other %lld", who, F->nel, nch, (long long)nsplit,
+               (long long)(C->nel - nsplit));
+    for (int g = 0; g < EM_G; g++)
+      FH_REQUIRE(F->count[g] == fine_of[g], "%s: %lld fine elements of shape code %d are not the children of and copies of %lld coarse ones, which give %lld",
+                 who, (long long)F->count[g], g, (long long)C->count[g], (long long)fine_of[g]);
+    for (int f = 0; f < F->nel; f++)
+      FH_REQUIRE(gf[f] == gc[fa[f]], "%s: fine element %d has shape code %d, its father %d shape code %d: not its refinement", who, f, gf[f], fa[f], gc[fa[f]]);
   }
   const int m = F->own[fe], ncols = C->own[fe];
   FH_REQUIRE(m >= 0 && m <= F->nnode && ncols >= 0 && ncols <= C->nnode, "%s: the family owns %d of %d fine and %d of %d coarse nodes", who, m, F->nnode, ncols,
@@ -332,7 +355,7 @@ extern "C" int fh_elem_mesh_prolongator(fh_elem_mesh_t C, fh_elem_mesh_t F, int 
     fh_set_error("%s: %s", who, hipGetErrorString(he));
     return fail(1);
   }
-  A.EP = d_EP; A.aptr = L.d_ptr; A.adj = L.d_adj; A.geom_f = F->d_geom; A.ed_c = C->d_ed; A.m = m; A.ncols = ncols; A.nch = nch; A.err = L.d_err;
+  A.EP = d_EP; A.aptr = L.d_ptr; A.adj = L.d_adj; A.geom_f = F->d_geom; A.ed_c = C->d_ed; A.father = F->d_father; A.child = F->d_child; A.m = m; A.ncols = ncols; A.err = L.d_err;
   if (m) hipLaunchKernelGGL(k_et_rows<false>, dim3(fh_div_up(m, 4)), dim3(256), 0, st, A, cap, (const int*)nullptr, d_len, (int*)nullptr, (double*)nullptr);
   if (ns) hipLaunchKernelGGL(k_et_slow_count, dim3(ns), dim3(256), 0, st, A, d_srow, d_soff, d_gcol, d_gkey, d_gwin, d_len);
   std::vector<int> rp((size_t)m + 1, 0);

@@ -11,6 +11,10 @@ tetrahedra and prisms in one file; the two-dimensional files of quadrilaterals a
                   -2 .. -5), the centre Mesh::AddBiquadraticNodesNotInMeshFile adds (-1/9 of the vertices + 4/9 of the middles, Mesh.cpp:124)
     refine        MeshRefinement::RefineMesh: children 8 e + j (4 e + j in two dimensions) of the father's shape, vertices through each shape's fine2CoarseVertexMapping (read off the element
                   prolongator), new edge / face nodes shared between neighbours of any shape, coordinates by the creating child's element prolongator
+    refine_flagged  MeshRefinement::RefineMesh with an AMR flag (MeshRefinement.cpp:197-493, Elem.hpp:358-370): the flagged elements of the mesh's level give their
+                  children, every other element one unchanged copy, in coarse element order; new nodes come from the children alone, by the keys and the
+                  creating child of refine; the numbering walks all fine elements, copies included
+    flag_elements   MeshRefinement::FlagElementsToRefine type 1: a function of the mean of an element's vertices and the level, elements of the level only
     numbering     vertices, then edge middles, then the rest, each class in order of first appearance walking the elements
 """
 import numpy as np
@@ -307,3 +311,119 @@ def refine(kind, ed, xs, ff):
     xf = np.empty((own[2], dim))
     xf[new[used]] = coords[used]
     return np.repeat(kind, nch), _apply(new, raw), xf, fff, own
+
+
+def refine_flagged(kind, ed, xs, ff, flags, lev=None, level=None):
+    """selective refinement: (kind_f, ed_f, xs_f, ff_f, own_f, lev_f, father, child).  An element splits when flags[e] != 0 and lev[e] == level (an element of
+    an older level never does); its nch children follow one another, of level + 1, father e, child j.  Every other element gives one copy -- its row of node
+    ids, its face row, its level; father e, child -1.  New nodes are made by the children only, with the keys and the creating child of refine (a copy's edges
+    and faces are at least father-sized: no child's new edge or face is one of them, so copies enter no key table); an old node keeps its coordinate bits.
+    With every element flagged the first five results are refine's, with none the mesh comes back."""
+    nel, dim = ed.shape[0], xs.shape[1]
+    nch = 8 if dim == 3 else 4
+    if lev is None:
+        lev = np.full(nel, 0 if level is None else level, dtype=np.int64)
+    lev = np.asarray(lev, dtype=np.int64)
+    if level is None:
+        level = int(lev.max()) if nel else 0
+    eff = (np.asarray(flags).reshape(-1) != 0) & (lev == level)
+    if eff.shape != (nel,):
+        raise ValueError("refine_flagged: %d flags for %d elements" % (eff.size, nel))
+    cnt = np.where(eff, nch, 1)
+    start = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    nel_f = int(start[-1])
+    father = np.repeat(np.arange(nel, dtype=np.int64), cnt)
+    child = np.where(eff[father], np.arange(nel_f) - start[father], -1)
+    code = _codes(kind)
+    cc = code[father]
+    raw = np.full((nel_f, 27), -1, dtype=np.int64)
+    fff = np.full((nel_f, 6), -1, dtype=np.int64)
+    keep = np.nonzero(~eff)[0]
+    raw[start[keep]], fff[start[keep]] = ed[keep], ff[keep]
+    lev_f = np.where(child >= 0, level + 1, lev[father])
+    ent = {2: [], 3: [], 4: []}                               # as in refine, over the children of the flagged elements
+    for i, s in enumerate(SHAPES):
+        sel = np.nonzero((code == i) & eff)[0]
+        if sel.size == 0:
+            continue
+        T = tables(s)
+        nv = CLASSES[s][0]
+        es = ed[sel]
+        for j in range(nch):
+            rows = start[sel] + j
+            raw[rows, :nv] = es[:, T["f2c"][j]]
+            for lf in range(NFACES[s]):
+                for f in range(NFACES[s]):
+                    if T["nvf"][lf] == T["nvf"][f] and all(int(T["f2c"][j][v]) in T["faces"][f].tolist() for v in T["faces"][lf][:T["nvf"][lf]]):
+                        fff[rows, lf] = ff[sel, f]
+        rows = (start[sel][:, None] + np.arange(nch)[None, :]).ravel()
+        v = raw[rows, :nv]
+        E = np.array(T["edges"])
+        a, b = v[:, E[:, 0]], v[:, E[:, 1]]
+        ent[2].append((np.repeat(rows, len(E)), np.tile(nv + np.arange(len(E)), rows.size),
+                       np.stack([np.minimum(a, b), np.maximum(a, b)], axis=2).reshape(-1, 2)))
+        for n in ((3, 4) if dim == 3 else ()):
+            fs = [f for f in range(NFACES[s]) if T["nvf"][f] == n]
+            if fs:
+                key = np.sort(v[:, np.array([T["faces"][f][:n] for f in fs])], axis=2).reshape(-1, n)
+                ent[n].append((np.repeat(rows, len(fs)), np.tile([T["face_local"][f] for f in fs], rows.size), key))
+    nxt = xs.shape[0]
+    oc, ol = [], []
+    for part in ent.values():
+        if not part:
+            continue
+        c, loc, key = (np.concatenate(t) for t in zip(*part))
+        if len(part) > 1:
+            order = np.argsort(c, kind="stable")
+            c, loc, key = c[order], loc[order], key[order]
+        ids, owner = first_touch(key)
+        raw[c, loc] = nxt + ids
+        nxt += owner.size
+        oc.append(c[owner])
+        ol.append(loc[owner])
+    fresh = np.nonzero(child >= 0)[0]
+    centre = _CLASSES[cc[fresh], 2] - 1
+    raw[fresh, centre] = nxt + np.arange(fresh.size)
+    oc, ol = np.concatenate(oc + [fresh]).astype(np.int64), np.concatenate(ol + [centre]).astype(np.int64)
+    pos = np.zeros((dim, oc.size))
+    occ = cc[oc]
+    xt = np.ascontiguousarray(xs.T)
+    for i, s in enumerate(SHAPES):
+        m = np.nonzero(occ == i)[0]
+        if m.size:
+            nl = NLOC[s]
+            e, j = father[oc[m]], child[oc[m]]
+            jl = j * nl + ol[m]
+            EPt = tables(s)["EP"].transpose(2, 0, 1).reshape(nl, -1)
+            edt = np.ascontiguousarray(ed[:, :nl].T)
+            acc = np.zeros((dim, m.size))
+            for k in range(nl):                                             # the sum over the father's nodes in their order
+                w, node = EPt[k][jl], edt[k][e]
+                for d in range(dim):
+                    acc[d] += w * xt[d][node]
+            pos[:, m] = acc
+    coords = np.concatenate([xs, pos.T])
+    new, own = _renumber(cc, raw, coords.shape[0])
+    used = new >= 0
+    xf = np.empty((own[2], dim))
+    xf[new[used]] = coords[used]
+    return kind[father], _apply(new, raw), xf, fff, own, lev_f, father, child
+
+
+def flag_elements(kind, ed, xs, lev, level, fn):
+    """fn(x[3], level) at the mean of the element's vertices, for the elements of the mesh's level; uint8[nel].  The mean is the vertices added in local order
+    from +0.0, then one division by their number: the sum the device forms, so a centroid on a threshold flags the same on both sides"""
+    nel, dim = ed.shape[0], xs.shape[1]
+    out = np.zeros(nel, dtype=np.uint8)
+    for e in range(nel):
+        if lev[e] != level:
+            continue
+        nv = CLASSES[kind[e]][0]
+        x = np.zeros(3)
+        for v in range(nv):
+            for d in range(dim):
+                x[d] = x[d] + xs[ed[e, v], d]
+        for d in range(dim):
+            x[d] = x[d] / float(nv)
+        out[e] = 1 if fn(x, level) else 0
+    return out

@@ -271,19 +271,46 @@ int fh_mesh_dirichlet_dofs(fh_mesh_t mesh, int fe, int* n, int* dofs);
  * class ends come back; the coarse mesh is unchanged.  Integers and coordinate bits are those of mixed_mesh.py: refine.  New nodes are found through three
  * hash tables (edges: two vertex ids; quadrilateral faces: the smallest vertex id and the one diagonal to it; triangular faces: the slot of the edge of the
  * two smallest vertices and the third vertex), exact for any 32-bit ids; a refinement whose first-touch order (27 entries per fine element at most) or
- * node table does not fit 32-bit integers is refused.  get downloads what is asked for (any pointer may be NULL). */
+ * node table does not fit 32-bit integers is refused.  get downloads what is asked for (any pointer may be NULL).
+ * Every element carries its level, the element of the coarser mesh it came from and which child of it it is: a mesh from create has level 0 and no fathers
+ * (-1, -1), the result of refine the uniform level + 1, f / nch and f % nch.  refine is for a homogeneous mesh: one that holds elements of older levels is
+ * refused with a message (it would split them too); refine_flagged is its refinement.
+ *   set_levels      lev[nel] >= 0 for a mesh from create that is already non-homogeneous; the mesh's level becomes their maximum.
+ *   flag            MeshRefinement::FlagElementsToRefine type 1, one thread per element: expr over the variables (x, y, z, level) at the mean of the element's
+ *                   vertices -- added in local order from +0.0, each sum rounded on its own, then one division by their number; z = 0 in two dimensions,
+ *                   level = the mesh's.  The flag is (|value| >= 0.5) for an element of the mesh's level and 0 for an older one.  The flags stay on the
+ *                   mesh, replacing earlier ones, and are copied to flags[nel] when it is not NULL.  The bits of mixed_mesh.py: flag_elements.
+ *   refine_flagged  MeshRefinement::RefineMesh with an AMR flag (MeshRefinement.cpp:197-493, Elem.hpp:358-370), flags[nel] from the host or, with NULL, the ones
+ *                   flag left on the mesh (none there: refused).  In coarse element order, an element whose flag is set and whose level is the mesh's gives
+ *                   its nch children as refine does; every other element one copy: the same 27 ids (renumbered), face row and level, father = the element,
+ *                   child = -1.  New nodes come from the children alone, with the keys and the creating child of refine; old nodes keep their coordinate
+ *                   bits; the numbering walks all fine elements, copies included.  The fine mesh has level + 1.  With every element flagged the result is
+ *                   refine's, with none the coarse mesh's.  Two small copies come back: the fine and the split elements per shape (integer sums), then the
+ *                   class ends.  Integers and coordinate bits are those of mixed_mesh.py: refine_flagged; the 32-bit refusals are refine's.
+ *   elem_levels     downloads lev / father / child [nel] (any pointer may be NULL); *homogeneous: every element is of the mesh's level.
+ * The hanging nodes of a flagged level are NOT constrained here (fh_mesh_amr_constraints does that for fh_mesh_t only). */
 typedef struct fh_elem_mesh_s* fh_elem_mesh_t;
 int fh_elem_mesh_create(fh_ctx_t ctx, int dim, int nel, int nnode, const int* elem_geom, const int* elem_dof, const double* coords, const int* face_flag,
                         const int own[3], fh_elem_mesh_t* mesh);
 int fh_elem_mesh_refine(fh_elem_mesh_t coarse, fh_elem_mesh_t* fine);
+int fh_elem_mesh_set_levels(fh_elem_mesh_t mesh, const int* lev /* [nel] */);
+struct fh_expr_s;
+int fh_elem_mesh_flag(fh_elem_mesh_t mesh, struct fh_expr_s* expr /* an fh_expr_t (run-time expressions, below) */, unsigned char* flags /* host [nel] or NULL */);
+int fh_elem_mesh_refine_flagged(fh_elem_mesh_t coarse, const unsigned char* flags /* host [nel], or NULL: the flags fh_elem_mesh_flag left on the device */,
+                                fh_elem_mesh_t* fine);
+int fh_elem_mesh_elem_levels(fh_elem_mesh_t mesh, int* lev, int* father, int* child, int* homogeneous);
 int fh_elem_mesh_info(fh_elem_mesh_t mesh, int* dim, int* nel, int* nnode, int own[3], int* level);
 int fh_elem_mesh_get(fh_elem_mesh_t mesh, int* elem_geom /* [nel] */, int* elem_dof /* [nel*27] */, double* coords /* [nnode*dim] */, int* face_flag /* [nel*6] */);
 int fh_elem_mesh_destroy(fh_elem_mesh_t mesh);
 
 /* ---- transfers and boundary lists of resident element meshes (fh_elemtransfer.hip) ----
  * prolongator: PP of the level `fine` from the element prolongators (ElemType.cpp:439-532), an ordinary fh_mat_t of fine.own[fe] rows and coarse.own[fe]
- * columns, resident and never on the host.  fe: 0 linear, 1 serendipity, 2 biquadratic.  fine must be the refinement of coarse: the same context and
- * dimension, level + 1, nch times the elements (8 / 4) and fine element nch * e + j of the shape of e; anything else is refused before a kernel is launched.
+ * columns, resident and never on the host.  fe: 0 linear, 1 serendipity, 2 biquadratic.  fine must be the refinement of coarse, uniform or flagged: the same
+ * context and dimension, level + 1, every fine element's father an element of coarse and of its shape, and nch (8 / 4) fine elements for every father with
+ * children -- each child number 0 .. nch - 1 once --, one copy for every other; anything else is refused before a kernel is launched.  The check reads the shapes
+ * of both meshes and the fine mesh's two link arrays on the host: four copies of one int per element, 12 bytes per fine element.  Fine element f is child j = child[f] of e = father[f] (nch e + j
+ * after a uniform refinement).  After the insertions below, over the fathers with children, every COPY f of an element e inserts exactly 1.0 at
+ * (ed_f[f][n], ed_c[e][n]), n < nc, ordered by (shape, n, e): a node a copy shares with a refined neighbour holds the 1.0.
  * For every shape s, child j, fine local node n and coarse local function k < nc(s, fe) with EP_s[j][n][k] != 0 (fh_fe_elem_prolongator(s, fe): |.| < 1e-14
  * is zero and adds no entry) and every coarse element e of shape s, EP_s[j][n][k] is inserted at (ed_f[nch e + j][n], ed_c[e][k]).  Insertions are ordered
  * by (shape, j, n, k, e) and the last one of an entry stays (INSERT_VALUES); shapes in the order of their names sorted as strings, hex < quad < tet < tri <
