@@ -1132,6 +1132,12 @@ class Assembler:
         _chk(self.L.fh_assembler_info(self.h, ctypes.byref(nco) if colors else None, ctypes.byref(by), ctypes.byref(fl)))
         return {"ncolors": nco.value if colors else None, "algorithmic_bytes": by.value, "flops": fl.value}
 
+    def geom_cache_info(self):
+        """geometry cache of the fused assembly (option assemble_geom_cache): whether this assembler holds one, and the device memory it takes"""
+        act, by = ctypes.c_int(), ctypes.c_int64()
+        _chk(self.L.fh_assembler_geom_cache_info(self.h, ctypes.byref(act), ctypes.byref(by)))
+        return {"active": bool(act.value), "bytes": by.value}
+
 
 class Direct:
     """sparse exact solve (fh_direct_*: multifrontal factorisation over a nested-dissection tree; symmetric operators on unpivoted fronts, unsymmetric /

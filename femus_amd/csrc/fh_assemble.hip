@@ -80,6 +80,10 @@ struct fh_assembler_s {
   uint64_t macro_uid = 0;                   // the matrix of that assembly (fh_mat_s::uid, not its address: it may be destroyed, and a later one may get the address)
   uint64_t macro_val_gen = 0;               // ... as long as nobody but SetPenalty has written the matrix since (fh_mat_s::val_gen)
   double* d_Pbuf = nullptr;
+  // geometry cache of the fused assembly (option assemble_geom_cache): what phase A computes from this assembler's node coordinates alone, [nel][7][64]:
+  // rows 0 .. 5 D_q, row 6 det * w, lane = Gauss point in the cluster kernel's order.  Made at the first fused assembly with a constant source.
+  double* d_geo = nullptr;
+  int geo_state = 0;                        // 0: not made yet, 1: made, -1: the allocation failed (phase A stays in the kernel)
   int* d_cl_prow = nullptr;                 // rows of the second pass
   unsigned* d_cl_pstart = nullptr;          // [nprow + 1] their segments of the partial-row buffer
   // arguments of the last assembly (the element-wise Galerkin product re-creates the element rows from them when the fused path ran)
@@ -1863,13 +1867,11 @@ constexpr int CL_NS_MAX = CL_T * CL_SPT;         // 5120 >= 4913
 constexpr int CL_NM_MAX = 128;                   // macro nodes (125), padded
 constexpr int CL_NBLK = 128;                     // address blocks of the entries with more than two contributions (49 used; one per lane 16 .. 31 of the eight waves)
 // LDS of the cluster kernel (doubles): the per-lane tables it reads from LDS -- rows CL_LC0 .. SF_NLC - 1 of the constants (the others live in registers) and
-// the integer rows --, the eight wave regions (xt + R), phase A's U / V scratch of the waves that run phase A one cluster AHEAD (waves 4 .. 7: their R
-// still holds the staging of the current cluster then), a zero cell (operand of absent contributions)
+// the integer rows --, the eight wave regions (xt + R), a zero cell (operand of absent contributions)
 constexpr int CL_LC0 = 43;
 constexpr int CL_TAB = (SF_NLC - CL_LC0) * 64 + SF_NLI * 32;
 constexpr int CL_UVS = 6 * SF_US + 9 * SF_VS;    // 672 doubles per wave
-constexpr int CL_UV = CL_TAB + CL_NE * SF_WAVE;
-constexpr int CL_ZC = CL_UV + (CL_NE / 2) * CL_UVS;
+constexpr int CL_ZC = CL_TAB + CL_NE * SF_WAVE;
 // behind them: the sums of the long entries (one cell each, written between the two barriers of the output phase), descriptors (8 B per template entry), row
 // destinations of the cluster (8 B), residual destinations (4 B), address blocks (8 x 2 B) of the residual sums and of the long sums
 constexpr int CL_LV = CL_ZC + 2;
@@ -1878,11 +1880,15 @@ constexpr size_t CL_OFF_RB = CL_OFF_DT + (size_t)CL_NS_MAX * 8;
 constexpr size_t CL_OFF_FB = CL_OFF_RB + (size_t)CL_NM_MAX * 8;
 constexpr size_t CL_OFF_FL = CL_OFF_FB + (size_t)CL_NM_MAX * 4;
 constexpr size_t CL_OFF_OV = CL_OFF_FL + (size_t)CL_NM_MAX * 16;
-constexpr size_t cl_lds_bytes() { return CL_OFF_OV + (size_t)CL_NBLK * 16; }
+// last, and only in the instantiations that compute phase A themselves (GEO = false): phase A's U / V scratch of the waves that run phase A one cluster
+// AHEAD (waves 4 .. 7: their R still holds the staging of the current cluster then).  Nothing the plan addresses lies behind it, so the instantiation that
+// reads the geometry cache simply asks for 21 kB less.
+constexpr size_t CL_OFF_UV = CL_OFF_OV + (size_t)CL_NBLK * 16;
+constexpr size_t cl_lds_bytes(bool geo) { return CL_OFF_UV + (geo ? 0 : (size_t)(CL_NE / 2) * CL_UVS * sizeof(double)); }
 static_assert((CL_LV + CL_NBLK) * 8 < (1 << 17), "cluster kernel: LDS byte addresses of the stagings and the long-sum cells fit 17 bits");
 static_assert(CL_ZC < (1 << 16), "cluster kernel: 16-bit double indices of the address blocks");
-static_assert(cl_lds_bytes() <= 160 * 1024, "cluster kernel: LDS budget");
-static_assert((CL_TAB % 2) == 0 && (CL_UVS % 2) == 0, "cluster kernel: 16-byte alignment of the wave regions");
+static_assert(cl_lds_bytes(false) <= 160 * 1024, "cluster kernel: LDS budget");
+static_assert((CL_TAB % 2) == 0 && (CL_UVS % 2) == 0 && (CL_OFF_UV % 16) == 0, "cluster kernel: 16-byte alignment of the wave regions");
 
 struct ClParams {
   int ncl, ns, nm;
@@ -1898,6 +1904,7 @@ struct ClParams {
   const uint4* mapb;           // CARRY kernels: [ncl][CL_T] byte i = position of the slot in its destination row
   double* Pbuf;
   double* res;
+  const double* geo;           // GEO kernels: the assembler's geometry cache [nel][7][64] (k_geom_cache)
   unsigned long long* stamps;  // instrumented build only (asm_debug bit 7): [workgroup][wave][16] summed phase cycles + [15] = clusters done
 };
 
@@ -1917,7 +1924,11 @@ __device__ __forceinline__ double cl_sum8(const char* S, const uint4 a, double t
 // between; ascending cluster order = the order of the second pass, so the bits are the ones the partial-row buffer gives) -- and only the rows on the surface
 // of the super-cluster go through the partial-row buffer.  (Measured and dropped: the add as a floating-point atomic without return, global_atomic_add_f64 --
 // same bits, no round trip for the wave, but 17 M of them per assembly took 1.2 ms.)
-template <int SRC, bool INS = false, bool ROT = true, bool CARRY = false>
+// GEO (constant source only): D_q and det * w at the Gauss points are READ from the assembler's geometry cache (k_geom_cache: what phase A returns for
+// p0 = 1, which depends on the assembler's node coordinates alone) instead of computed: no phase A, so no wave runs ahead, no constants of phase A in
+// registers, no U / V scratch, no coordinate gathers.  The seven values per lane of the wave's NEXT element are loaded behind the staging writes, into the
+// registers stage 1 has just freed, and arrive under the output phase.
+template <int SRC, bool INS = false, bool ROT = true, bool CARRY = false, bool GEO = false>
 __global__ __launch_bounds__(CL_T) void k_cluster_q2hex_sf(AsmParams P, SfTab tab, const double* __restrict__ lanec, const int* __restrict__ lanei, ClParams C) {
   constexpr int NC = 27, DIM = 3, KS = MF_KS, NW = CL_NE;
   constexpr bool REGC = true;
@@ -1944,15 +1955,18 @@ __global__ __launch_bounds__(CL_T) void k_cluster_q2hex_sf(AsmParams P, SfTab ta
   // LDS-bound and the arithmetic-bound phases of an element take turns on the compute unit (measured with the phase stamps: LDS busy 54 %, vector ALU 33 %,
   // together 87 % of the element time).  Waves 4 .. 7 therefore run phase A one cluster AHEAD -- after their staging is written, from a scratch region of
   // their own -- so that on every SIMD one wave is in the short, latency-bound phase A while the other is in the long stages 2-3 (asm_debug bit 8: off)
-  const bool ahead = ROT && ((P.debug & 1024) ? wave >= CL_NE / 2 : wave < CL_NE / 2) && !(P.debug & 256);
+  static_assert(!GEO || SRC == 0, "cluster kernel: the geometry cache serves the constant source only");
+  const bool ahead = !GEO && ROT && ((P.debug & 1024) ? wave >= CL_NE / 2 : wave < CL_NE / 2) && !(P.debug & 256);
   double* xt = SFl + CL_TAB + wave * SF_WAVE;
   double* R = xt + SF_XT;
-  double* UVa = ahead ? SFl + CL_UV + (wave & (CL_NE / 2 - 1)) * CL_UVS : R;
+  double* UVa = ahead ? reinterpret_cast<double*>(Sb + CL_OFF_UV) + (wave & (CL_NE / 2 - 1)) * CL_UVS : R;
   const double* LCl = SFl + lane - CL_LC0 * 64;       // row r of the constants at LCl[r * 64], r >= CL_LC0
   const int* LIl = SFi + lane;
-  double rcA[19], rcZ[8], rcY[16];
+  double rcA[19], rcZ[8], rcY[16];      // (GEO: rcA stays unset and unused -- `ahead` is false at compile time, every phase A below is dead code)
+  if constexpr (!GEO) {
 #pragma unroll
-  for (int r = 0; r < 19; r++) rcA[r] = lanec[r * 64 + lane];
+    for (int r = 0; r < 19; r++) rcA[r] = lanec[r * 64 + lane];
+  }
 #pragma unroll
   for (int r = 0; r < 8; r++) rcZ[r] = lanec[(19 + r) * 64 + lane];
 #pragma unroll
@@ -1982,16 +1996,20 @@ __global__ __launch_bounds__(CL_T) void k_cluster_q2hex_sf(AsmParams P, SfTab ta
     return ((((int)blockIdx.x + (it >> sh) * cstride)) << sh) + (it & ((1 << sh) - 1));
   };
   int cl = cl_at(0);
-  {
+  // GEO: xt keeps the solution values alone (for K_e u), and the node ids are read only for them
+  const bool nodes = !GEO || P.sol;
+  if (nodes) {
     const int dof = P.elem_dof[(size_t)(cl * NW + wave) * P.nloc + nodeofl];
     if (lane < NC) {
-      xt[lane] = P.coords[(size_t)dof * DIM];
-      xt[28 + lane] = P.coords[(size_t)dof * DIM + 1];
-      xt[56 + lane] = P.coords[(size_t)dof * DIM + 2];
+      if constexpr (!GEO) {
+        xt[lane] = P.coords[(size_t)dof * DIM];
+        xt[28 + lane] = P.coords[(size_t)dof * DIM + 1];
+        xt[56 + lane] = P.coords[(size_t)dof * DIM + 2];
+      }
       xt[84 + lane] = P.sol ? P.sol[dof] : 0.0;
     }
   }
-  int dof_n = P.elem_dof[(size_t)(cl_at(1) * NW + wave) * P.nloc + nodeofl];
+  int dof_n = nodes ? P.elem_dof[(size_t)(cl_at(1) * NW + wave) * P.nloc + nodeofl] : 0;
   wave_lds_sync();
   SfStamps st;
   if (INS) {
@@ -2001,7 +2019,20 @@ __global__ __launch_bounds__(CL_T) void k_cluster_q2hex_sf(AsmParams P, SfTab ta
   }
   int ndone = 0;
   double Dr[7];              // D_q and the source weight at this lane's Gauss point: phase A -> stage 1
-  if (ahead) {
+  // GEO: row r of element e of the cache, this lane's Gauss point; every value is read once per assembly (streaming loads)
+  auto geo_load = [&](const int c) {
+    const double* g = C.geo + (size_t)(c * NW + wave) * (7 * 64) + lane;
+#pragma unroll
+    for (int r = 0; r < 7; r++) Dr[r] = __builtin_nontemporal_load(g + r * 64);
+  };
+  auto geo_arrived = [&]() {
+#pragma unroll
+    for (int r = 0; r < 7; r++) asm volatile("" : "+v"(Dr[r]));
+  };
+  if constexpr (GEO) {
+    geo_load(cl);
+    geo_arrived();
+  } else if (ahead) {
     sf_phase_a<SRC, REGC, INS>(P, LCl, CL_IDXA(), rcA, xt, UVa, Dr, &st);
     wave_lds_sync();
   }
@@ -2016,11 +2047,17 @@ __global__ __launch_bounds__(CL_T) void k_cluster_q2hex_sf(AsmParams P, SfTab ta
     const int eout = (lane >> 4) * SF_ES + (lane & 15);
     // ---- prefetch (dependent gathers): coordinates / solution of the wave's next element, node ids of the one after ----
     const int cl_nn = cl_at(it + 2);
-    const double nx0 = P.coords[(size_t)dof_n * DIM], nx1 = P.coords[(size_t)dof_n * DIM + 1], nx2 = P.coords[(size_t)dof_n * DIM + 2];
+    double nx0 = 0.0, nx1 = 0.0, nx2 = 0.0;
+    if constexpr (!GEO) {
+      nx0 = P.coords[(size_t)dof_n * DIM];
+      nx1 = P.coords[(size_t)dof_n * DIM + 1];
+      nx2 = P.coords[(size_t)dof_n * DIM + 2];
+    }
     const double nu = P.sol ? P.sol[dof_n] : 0.0;
-    const int dof_nn = P.elem_dof[(size_t)(cl_nn * NW + wave) * P.nloc + nodeofl];
+    const int dof_nn = nodes ? P.elem_dof[(size_t)(cl_nn * NW + wave) * P.nloc + nodeofl] : 0;
     double Kb[3][3], fsrc;
-    if (!ahead) {
+    if constexpr (GEO) Dr[6] = Dr[6] * P.p0;      // cached det * w, times the constant source: phase A's (det * w) * f
+    else if (!ahead) {
       sf_phase_a<SRC, REGC, INS>(P, LCl, CL_IDXA(), rcA, xt, UVa, Dr, &st);
       wave_lds_sync();
     }
@@ -2053,6 +2090,7 @@ __global__ __launch_bounds__(CL_T) void k_cluster_q2hex_sf(AsmParams P, SfTab ta
           km[a2 * 9 * KS + a * 9] = v;
         }
     }
+    if constexpr (GEO) geo_load(cl_at(it + 1));      // the wave's next element (behind the last cluster: the clamped one again, unused)
     wave_lds_sync();
     sf_stamp<INS>(st, 7);
     double ku = 0.0;
@@ -2070,9 +2108,11 @@ __global__ __launch_bounds__(CL_T) void k_cluster_q2hex_sf(AsmParams P, SfTab ta
     }
     Ks[min(lane & 31, NC - 1) * KS + NC] = -(ku + fsrc);   // residual entry of tensor row t = lane & 31 in the staging's spare column (both halves hold the same value; lanes beyond 26 repeat row 26)
     if (lane < NC) {          // the next element's nodes
-      xt[lane] = nx0;
-      xt[28 + lane] = nx1;
-      xt[56 + lane] = nx2;
+      if constexpr (!GEO) {
+        xt[lane] = nx0;
+        xt[28 + lane] = nx1;
+        xt[56 + lane] = nx2;
+      }
       xt[84 + lane] = nu;
     }
     if (tid < CL_NM_MAX) {
@@ -2154,6 +2194,10 @@ __global__ __launch_bounds__(CL_T) void k_cluster_q2hex_sf(AsmParams P, SfTab ta
         asm volatile("" ::"v"(vv[CL_SPT - 1]), "v"(vv[0]));
         sf_stamp<INS>(st, 13);
       }
+      // GEO: the cached factors of the next element must be IN before the stores go out (geo_arrived: here, ahead of the loop and on the path that skips this
+      // block) -- the vector-memory counter completes in order, so a wait for them in front of stage 1 would also wait for this cluster's stores and for the
+      // gathers issued at the top of the loop (measured: stage 1 2 640 instead of 1 300 ticks)
+      if constexpr (GEO) geo_arrived();
 #pragma unroll
       for (int i = 0; i < CL_SPT; i++) {
         cl_gdouble* dst = (cl_gdouble*)vb[i];
@@ -2166,7 +2210,7 @@ __global__ __launch_bounds__(CL_T) void k_cluster_q2hex_sf(AsmParams P, SfTab ta
         *dst = (fvv >= 0 && (fvv & 0x40000000)) ? fold + fsum : fsum;
       }
       sf_stamp<INS>(st, 15);
-    }
+    } else if constexpr (GEO) geo_arrived();
     sf_stamp<INS>(st, 10);
     __syncthreads();          // the stagings are the next elements' scratch, rb / fb the next cluster's
     sf_stamp<INS>(st, 11);
@@ -2736,20 +2780,20 @@ static int cluster_plan_build(fh_assembler_t as, fh_mat_t A, const int* elem_dof
 
 // Instrumented launch (asm_debug bit 7, constant source only): the same kernel with the shader clock read at twelve phase boundaries; prints the
 // average cycles per cluster and phase over all waves.  A development aid -- the stamps cost about a tenth of the wave cycles themselves.
-template <bool CARRY>
+template <bool CARRY, bool GEO>
 static int launch_cluster_stamped(fh_assembler_t as, const AsmParams& P, const ClParams& C0, int grid) {
-  constexpr size_t lds = cl_lds_bytes();
+  constexpr size_t lds = cl_lds_bytes(GEO);
   static bool attr_set[64] = {};
   const int dev = as->ctx->device & 63;
   if (!attr_set[dev]) {
-    FH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cluster_q2hex_sf<0, true, true, CARRY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    FH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cluster_q2hex_sf<0, true, true, CARRY, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set[dev] = true;
   }
   ClParams C = C0;
   const size_t nst = (size_t)grid * CL_NE * 20;
   FH_CHECK_HIP(hipMalloc(&C.stamps, nst * sizeof(unsigned long long)));
   FH_CHECK_HIP(hipMemsetAsync(C.stamps, 0, nst * sizeof(unsigned long long), as->ctx->stream));
-  hipLaunchKernelGGL((k_cluster_q2hex_sf<0, true, true, CARRY>), dim3(grid), dim3(CL_T), lds, as->ctx->stream, P, as->sf_tab, as->d_sfLc, as->d_sfLi, C);
+  hipLaunchKernelGGL((k_cluster_q2hex_sf<0, true, true, CARRY, GEO>), dim3(grid), dim3(CL_T), lds, as->ctx->stream, P, as->sf_tab, as->d_sfLc, as->d_sfLi, C);
   FH_CHECK_HIP(hipGetLastError());
   std::vector<unsigned long long> h(nst);
   FH_CHECK_HIP(hipMemcpyAsync(h.data(), C.stamps, nst * sizeof(unsigned long long), hipMemcpyDeviceToHost, as->ctx->stream));
@@ -2771,7 +2815,8 @@ static int launch_cluster_stamped(fh_assembler_t as, const AsmParams& P, const C
     }
     for (int k = 0; k < 16; k++) tot += sum[k];
     fprintf(stderr, "k_cluster_q2hex_sf<0> phase stamps, waves %d..%d (%s): %d workgroups, %.0f wave-clusters, %.0f shader-clock ticks per cluster and wave\n", half * 4, half * 4 + 3,
-            half && !(P.debug & 256) ? "phase A one cluster ahead, i.e. rows 1-3 run behind row 8" : "phase A in place", grid, ncl, tot / std::max(ncl, 1.0));
+            GEO ? "geometry cache, no phase A" : half && !(P.debug & 256) ? "phase A one cluster ahead, i.e. rows 1-3 run behind row 8" : "phase A in place", grid, ncl,
+            tot / std::max(ncl, 1.0));
     for (int kk = 0; kk < 16; kk++) {
       const int k = order[kk];
       fprintf(stderr, "  %2d %-62s %9.1f  %5.1f %%\n", k, name[k], sum[k] / std::max(ncl, 1.0), 100.0 * sum[k] / std::max(tot, 1.0));
@@ -2780,18 +2825,18 @@ static int launch_cluster_stamped(fh_assembler_t as, const AsmParams& P, const C
   return 0;
 }
 
-template <int SRC, bool CARRY>
+template <int SRC, bool CARRY, bool GEO = false>
 static int launch_cluster_one(fh_assembler_t as, const AsmParams& P, const ClParams& C) {
-  constexpr size_t lds = cl_lds_bytes();
+  constexpr size_t lds = cl_lds_bytes(GEO);
   static bool attr_set[64] = {};
   const int dev = as->ctx->device & 63;
   if (!attr_set[dev]) {
-    FH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cluster_q2hex_sf<SRC, false, true, CARRY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    FH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cluster_q2hex_sf<SRC, false, true, CARRY, GEO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set[dev] = true;
   }
   const int grid = std::max(1, std::min(C.ncl >> (CARRY ? C.sup_shift : 0), as->ctx->num_cu * as->ctx->assemble_sf_grid));
-  if (SRC == 0 && (as->ctx->asm_debug & 128)) return launch_cluster_stamped<CARRY>(as, P, C, grid);     // dev aid: phase cycles of every wave on stderr
-  hipLaunchKernelGGL((k_cluster_q2hex_sf<SRC, false, true, CARRY>), dim3(grid), dim3(CL_T), lds, as->ctx->stream, P, as->sf_tab, as->d_sfLc, as->d_sfLi, C);
+  if (SRC == 0 && (as->ctx->asm_debug & 128)) return launch_cluster_stamped<CARRY, GEO>(as, P, C, grid);     // dev aid: phase cycles of every wave on stderr
+  hipLaunchKernelGGL((k_cluster_q2hex_sf<SRC, false, true, CARRY, GEO>), dim3(grid), dim3(CL_T), lds, as->ctx->stream, P, as->sf_tab, as->d_sfLc, as->d_sfLi, C);
   FH_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -2802,6 +2847,58 @@ __global__ void k_cluster_vdst(size_t n, const int* __restrict__ vdst, double* P
   if (k >= n) return;
   const int v = vdst[k];
   out[k] = reinterpret_cast<unsigned long long>(v < 0 ? Pbuf + (size_t)(v & 0x7fffffff) : val + (size_t)v);
+}
+
+// Fills the geometry cache: one wave per element runs the cluster kernel's own phase A (sf_phase_a<0>, the constants in registers as there) on the element's
+// nodes with the source p0 = 1 and stores what it returns -- D_q and (det * w) * 1 -- so the cached instantiation starts stage 1 from the same bits.
+__global__ __launch_bounds__(256) void k_geom_cache(AsmParams P, const double* __restrict__ lanec, const int* __restrict__ lanei, double* __restrict__ geo) {
+  constexpr int NC = 27, DIM = 3, NW = 4;
+  __shared__ __attribute__((aligned(16))) double sm[NW][SF_XT + CL_UVS];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int e = blockIdx.x * NW + wave;
+  if (e >= P.nelems) return;
+  double* xt = sm[wave];
+  double rcA[19];
+#pragma unroll
+  for (int r = 0; r < 19; r++) rcA[r] = lanec[r * 64 + lane];
+  const SfIdxA ia = {lanei[lane], lanei[64 + lane], lanei[2 * 64 + lane], lanei[3 * 64 + lane], lanei[4 * 64 + lane]};
+  const int dof = P.elem_dof[(size_t)e * P.nloc + lanei[14 * 64 + lane]];      // node of tensor index min(lane, 26)
+  if (lane < NC) {
+    xt[lane] = P.coords[(size_t)dof * DIM];
+    xt[28 + lane] = P.coords[(size_t)dof * DIM + 1];
+    xt[56 + lane] = P.coords[(size_t)dof * DIM + 2];
+  }
+  wave_lds_sync();
+  double Dr[7];
+  sf_phase_a<0, true>(P, nullptr, ia, rcA, xt, xt + SF_XT, Dr);
+  double* g = geo + (size_t)e * (7 * 64) + lane;
+#pragma unroll
+  for (int r = 0; r < 7; r++) g[r * 64] = Dr[r];
+}
+
+static AsmParams base_params(fh_assembler_t as);
+
+// Made at the first assembly that can use it (fused path, constant source, option on), kept until the assembler is destroyed: the assembler's coordinates
+// never change.  A failed allocation is no error: the assembly keeps phase A in the kernel.
+static int ensure_geom_cache(fh_assembler_t as) {
+  if (as->geo_state) return 0;
+  const size_t bytes = (size_t)as->nel * 7 * 64 * sizeof(double);
+  if (hipMalloc(&as->d_geo, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    as->d_geo = nullptr;
+    as->geo_state = -1;
+    FH_TRACE("fused assembly: no memory for the geometry cache (%zu bytes) -- phase A stays in the kernel", bytes);
+    return 0;
+  }
+  AsmParams P = base_params(as);
+  P.nelems = as->nel;
+  P.p0 = 1.0;
+  hipLaunchKernelGGL(k_geom_cache, dim3(fh_div_up(as->nel, 4)), dim3(256), 0, as->ctx->stream, P, as->d_sfLc, as->d_sfLi, as->d_geo);
+  FH_CHECK_HIP(hipGetLastError());
+  as->geo_state = 1;
+  FH_TRACE("fused assembly: geometry cache made (%d elements, %zu bytes)", as->nel, bytes);
+  return 0;
 }
 
 static int launch_cluster(fh_assembler_t as, const AsmParams& P, fh_mat_t A, double* res) {
@@ -2819,11 +2916,19 @@ static int launch_cluster(fh_assembler_t as, const AsmParams& P, fh_mat_t A, dou
   C.Pbuf = as->d_Pbuf; C.res = res;
   C.stamps = nullptr;
   C.sup_shift = as->cl_walk_shift;
+  // constant source: D_q from the geometry cache (option assemble_geom_cache, read per assembly); the other sources need the Gauss points' coordinates
+  C.geo = nullptr;
+  if (P.source_kind == 0 && as->ctx->assemble_geom_cache) {
+    FH_TRY(ensure_geom_cache(as));
+    if (as->geo_state == 1) C.geo = as->d_geo;
+  }
   if (as->cl_sup_shift > 0 || (as->ctx->assemble_carry >= 200 && as->d_cl_mapb)) {      // (>= 200: measurement aid, the CARRY kernel on a plan without carried rows)
-    if (P.source_kind == 4) FH_TRY((launch_cluster_one<2, true>(as, P, C)));
+    if (C.geo) FH_TRY((launch_cluster_one<0, true, true>(as, P, C)));
+    else if (P.source_kind == 4) FH_TRY((launch_cluster_one<2, true>(as, P, C)));
     else if (P.source_kind != 0) FH_TRY((launch_cluster_one<1, true>(as, P, C)));
     else FH_TRY((launch_cluster_one<0, true>(as, P, C)));
-  } else if (P.source_kind == 4) FH_TRY((launch_cluster_one<2, false>(as, P, C)));
+  } else if (C.geo) FH_TRY((launch_cluster_one<0, false, true>(as, P, C)));
+  else if (P.source_kind == 4) FH_TRY((launch_cluster_one<2, false>(as, P, C)));
   else if (P.source_kind != 0) FH_TRY((launch_cluster_one<1, false>(as, P, C)));
   else FH_TRY((launch_cluster_one<0, false>(as, P, C)));
   if (as->cl_nprow > 0 && !(as->ctx->asm_debug & (2 | 8))) {
@@ -3499,7 +3604,7 @@ extern "C" int fh_assembler_destroy(fh_assembler_t as) {
   if (as->d_prog_consts) hipFree(as->d_prog_consts);
   hipFree(as->d_iota);
   for (void* q : {(void*)as->d_cl_dtab, (void*)as->d_cl_fblk, (void*)as->d_cl_sinfo, (void*)as->d_cl_oblk, (void*)as->d_cl_gtab, (void*)as->d_cl_vdst, (void*)as->d_cl_vdst64, (void*)as->d_cl_fdst, (void*)as->d_cl_map, (void*)as->d_cl_mapb, (void*)as->d_cl_pmap,
-                  (void*)as->d_Pbuf, (void*)as->d_cl_prow, (void*)as->d_cl_pstart})
+                  (void*)as->d_Pbuf, (void*)as->d_geo, (void*)as->d_cl_prow, (void*)as->d_cl_pstart})
     if (q) hipFree(q);
   for (void* q : {(void*)as->d_adj_ptr, (void*)as->d_adj_ei, (void*)as->d_rowmap, (void*)as->d_Kbuf, (void*)as->d_Fbuf, (void*)as->d_slot, (void*)as->d_gal_child,
                   (void*)as->d_gal_cnt, (void*)as->d_gal_row, (void*)as->d_gal_fb, (void*)as->d_gal_cb, (void*)as->d_gal_val, (void*)as->d_gal_res, (void*)as->d_gal_dense,
@@ -3711,6 +3816,14 @@ extern "C" int fh_assembler_carry_info(fh_assembler_t as, int* clusters_per_supe
   const bool on = as->fused && as->ctx->assemble_fused && as->ctx->assemble_sf;
   if (clusters_per_super) *clusters_per_super = on ? 1 << as->cl_sup_shift : 0;
   if (carried_entries) *carried_entries = on ? (int64_t)as->cl_ncarried : 0;
+  return 0;
+}
+
+extern "C" int fh_assembler_geom_cache_info(fh_assembler_t as, int* active, int64_t* bytes) {
+  FH_REQUIRE(as, "fh_assembler_geom_cache_info: null argument");
+  const bool on = as->geo_state == 1;
+  if (active) *active = on ? 1 : 0;
+  if (bytes) *bytes = on ? (int64_t)as->nel * 7 * 64 * (int64_t)sizeof(double) : 0;
   return 0;
 }
 

@@ -107,6 +107,8 @@ struct fh_ctx_s {
   int assemble_carry = -1;           // fused cluster assembly: rows whose elements all lie in one SUPER-cluster of 8^k consecutive clusters (k = value / 3) are accumulated in the CSR array
                                      // itself by the one workgroup that walks the super-cluster (store / load-add-store, ascending cluster order), not through the partial-row buffer;
                                      // -1 = 64 or 8 clusters where every workgroup gets at least two super-clusters, 0 = off, 3 / 6 = forced (read when an assembler is created)
+  int assemble_geom_cache = 1;       // fused cluster assembly with a constant source: D_q and det * w at the Gauss points are read from a cache the assembler makes at its first such
+                                     // assembly (3584 bytes per element) instead of computed in the kernel's phase A; 0: phase A in the kernel (read at every assembly)
   int assemble_affine = 0;           // opt-in: affine HEX27/Q2 elements through precomputed reference matrices instead of quadrature
   int gj_symmetric = 1;              // coarse dense inverse: symmetric sweep on the upper block triangle when the operator is symmetric
   int galerkin_mfma = 1;             // element-wise Galerkin product on the FP64 matrix cores (0: sparse child tables on the vector ALU)

@@ -376,6 +376,16 @@ int fh_assembler_destroy(fh_assembler_t as);
 int fh_assembler_galerkin(fh_assembler_t fine, fh_assembler_t coarse, const int* child, int nfb, const int* fbdc, int ncb, const int* cbdc, fh_mat_t Ac);
 int fh_assemble_poisson(fh_assembler_t as, fh_vec_t sol, int source_kind, const double* params, fh_mat_t A, fh_vec_t res);
 int fh_assembler_info(fh_assembler_t as, int* ncolors, int64_t* algorithmic_bytes, double* flops);
+/* Geometry cache of the fused cluster assembly (fh_set_option(ctx, "assemble_geom_cache", v), default 1, read at every assembly; 0 = the kernel computes
+ * the factors itself): for a constant source (source_kind 0) the cluster kernel reads, per element and Gauss point, the six entries of
+ * D_q = w / det * Cf^T Cf and det * w instead of computing them from the node coordinates.  Layout [nel][7][64] doubles: rows 0 .. 5 = D_q (xx, xy, xz, yy,
+ * yz, zz), row 6 = det * w, column = Gauss point in the kernel's tensor order; 3584 bytes per element.  The values are the ones the kernel computes, bit
+ * for bit, so both settings assemble the same matrix and residual.  Lifetime: the cache belongs to the ASSEMBLER (it is made from the assembler's own
+ * copy of the coordinates, which never changes), is made at the first fused assembly with a constant source while the option is on -- never at create, so
+ * assemblers that do not take that path hold none -- and is freed by fh_assembler_destroy.  If the device memory cannot be had the assembler keeps the
+ * in-kernel computation; no assembly fails because of the cache.  *active = 1 when this assembler holds a cache, *bytes = the device memory it takes
+ * (0 when inactive).  Either pointer may be null. */
+int fh_assembler_geom_cache_info(fh_assembler_t as, int* active, int64_t* bytes);
 /* element-level entry (tests): K[nel*nc*nc], F[nel*nc] for the given elements, no scatter */
 int fh_element_matrices_poisson(fh_assembler_t as, fh_vec_t sol, int source_kind, const double* params, double* K, double* F);
 /* Optional fast path (fh_set_option(ctx, "assemble_affine", 1), default 0 = every element by quadrature as the reference does):
