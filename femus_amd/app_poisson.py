@@ -236,7 +236,7 @@ class Poisson001:
             return None
         return seen.pop() if seen in ({"tet"}, {"wedge"}) else "mixed"
 
-    def run_elements(self, log=None, smoother=capi.SMOOTH_GS_COLOR, omega=1.0, transfers="device"):
+    def run_elements(self, log=None, smoother=capi.SMOOTH_GS_COLOR, omega=1.0, transfers="device", selective_levels=0, flag=None, amr_mode="reference"):
         """LinearImplicitSystem::MGsolve on the meshes femus_amd/mixed_mesh.py builds, in all three Lagrange families: the TRI6 box (TRI7 inside; the box's
         boundary conditions and source), Gambit files of TET10 (input3D_Tet_*.json with input/cube_Tet.neu; TET15 inside), of WEDGE18 (input3D_Wedge_*.json with
         input/cube_Wedge.neu; WEDGE21 inside), of mixed shapes (input3D.json / input3D_All_first.json with input/cube_all_shapes_Six_boundary_groups.neu:
@@ -245,22 +245,51 @@ class Poisson001:
         the tetrahedral / prism files, fh_assemble_poisson_mixed on the mixed path, elem_dof rows padded with -1), transfers from the element prolongators,
         Galerkin operators below.  transfers: "device" builds every level's PP and Dirichlet list from the resident meshes (capi.ElementMesh.prolongator /
         boundary_dofs), "host" with _prolongator_from_children and the face loop below -- the same bits.
-        result["levels"]: (ed, xs, ff) of every level; ed and ff as wide as the shape, or padded to 27 and 6 on the mixed path"""
+        selective_levels > 0: the last so many of the nlevels come from a flagged refinement on the device (MultiLevelMesh::RefineMesh with a flag function:
+        resident.flag(flag), an expression over x, y, z, level, then refine("resident")); the levels before them are uniform as ever.  A non-homogeneous level l gets
+        its hanging dofs and P_amr[l] from the resident mesh (capi.ElementMesh.amr_constraints / amr_prolongator, amr_mode "reference" or "coarsest") and is wired
+        as LinearImplicitSystem does it (poisson.py for the box meshes): bdc[l] = Dirichlet + hanging, PP[l + 1] <- PP[l + 1] P_amr[l], and on the top level
+        RES <- P_amr^T RES, the operator P_amr^T KK P_amr, EPS <- P_amr EPS (_mgsolve).  The start vector is made conforming, SOL <- P_amr SOL, so that a hanging
+        dof with a master on the Dirichlet boundary starts from its masters' values.  Only with transfers "device".
+        result["levels"]: (ed, xs, ff) of every level; ed and ff as wide as the shape, or padded to 27 and 6 on the mixed path; result["hanging"]: the top
+        level's hanging dofs; result["elem_levels"]: the level of every element of the top level"""
         from . import mixed_mesh
         ctx = self.ctx
         levels = [mixed_mesh.tri_box(self.box[0], self.box[1], self.lo[:2], self.hi[:2]) if self.box is not None else mixed_mesh.read_gambit(self.mesh_file)]
         if transfers not in ("device", "host"):
             raise ValueError("transfers must be \"device\" or \"host\", not %r" % (transfers,))
         fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
+        selective_levels = int(selective_levels)
+        if selective_levels:
+            if transfers != "device":
+                raise ValueError("flagged levels (selective_levels = %d) are built on the device: transfers must be \"device\", not %r" % (selective_levels, transfers))
+            if not 0 < selective_levels < self.nlevels or flag is None:
+                raise ValueError("selective_levels must be 0 .. nlevels - 1 = %d and come with a flag expression over x, y, z, level" % (self.nlevels - 1))
+            if amr_mode not in ("reference", "coarsest"):
+                raise ValueError("amr_mode must be \"reference\" or \"coarsest\", not %r" % (amr_mode,))
+        n_uniform = self.nlevels - selective_levels
+        P_amr = [None] * self.nlevels
+        hanging = [np.zeros(0, np.int32)] * self.nlevels
+        elem_levels = None
         # level 0 goes up once and is refined on the device (capi.ElementMesh: the arrays of mixed_mesh.refine, integer for integer and bit for bit); the
         # transfers and the Dirichlet lists are built from the resident meshes; every level comes down once for result["levels"], the flux faces and the top
         # level's boundary values
         resident = [capi.ElementMesh.from_arrays(ctx, *levels[0])]
         P_dev, bdc_dev = [None], []
         try:
-            for _ in range(1, self.nlevels):
-                resident.append(resident[-1].refine())
+            for l in range(1, self.nlevels):
+                if l < n_uniform:
+                    resident.append(resident[-1].refine())
+                else:
+                    resident[-1].flag(flag)
+                    resident.append(resident[-1].refine("resident"))
                 levels.append(resident[-1].arrays())
+            for l, m in enumerate(resident):
+                if not m.homogeneous:
+                    hanging[l] = m.amr_constraints(fam, amr_mode)[0]
+                    P_amr[l] = m.amr_prolongator(fam, amr_mode)
+            if selective_levels:
+                elem_levels = resident[-1].elem_levels()[0]
             if transfers == "device":
                 # the flags a mesh carries are those of level 0: a child face inherits its father's
                 dirichlet = sorted({int(f) for f in np.unique(levels[0][3]) if f < -1 and self.face_bc(int(f))[0] == "dirichlet"})
@@ -269,7 +298,7 @@ class Poisson001:
                     if l:
                         P_dev.append(resident[l - 1].prolongator(m, fam))
         except BaseException:
-            for p in P_dev[1:]:
+            for p in P_dev[1:] + [q for q in P_amr if q is not None]:
                 p.destroy()
             raise
         finally:
@@ -321,6 +350,19 @@ class Poisson001:
         P = P_dev if transfers == "device" else [None] + [self._prolongator_from_children(groups[l - 1], levels[l - 1][1], levels[l][1], ndofs[l - 1], ndofs[l])
                                                           for l in range(1, self.nlevels)]
         SOL.upload(sol0)
+        if selective_levels:
+            bdc = [np.union1d(b, hanging[l]).astype(np.int32) for l, b in enumerate(bdc)]
+            for l in range(1, self.nlevels):                          # PP[l] <- PP[l] * PPamr[l - 1] (LinearImplicitSystem.cpp:253-258), before the Dirichlet zeroing
+                if P_amr[l - 1] is not None:
+                    PA = P[l].matmul(P_amr[l - 1])
+                    P[l].destroy()
+                    P[l] = PA
+            for q in P_amr[:top]:
+                if q is not None:
+                    q.destroy()
+            if P_amr[top] is not None:                                # a conforming start
+                RES.matrix_mult(SOL, P_amr[top])
+                SOL.assign(RES)
 
         # the plan of the element loop, made once: every linear iteration assembles on the same mesh and pattern
         gen = capi.GenericAssembler(ctx, kind if self.mixed else self.geom, self.fe, ed, xs, K)
@@ -336,18 +378,23 @@ class Poisson001:
                     capi.assemble_neumann_faces(ctx, fgeom, self.fe, np.array([tau_faces[k] for k in sel]), np.array([tau_vals[k] for k in sel]), xs, RES)
 
         try:
-            history = self._mgsolve(K, P, bdc, SOL, RES, assemble, log, smoother, omega)
+            history = self._mgsolve(K, P, bdc, SOL, RES, assemble, log, smoother, omega, P_amr=P_amr[top])
         finally:
             gen.destroy()
-        return {"solution": SOL.to_numpy(), "coords": xs[:ndof], "history": history, "converged": history[-1][1] < self.abs_tol, "dofs": ndof,
-                "levels": [lv[1:4] for lv in levels]}
+        out = {"solution": SOL.to_numpy(), "coords": xs[:ndof], "history": history, "converged": history[-1][1] < self.abs_tol, "dofs": ndof,
+               "levels": [lv[1:4] for lv in levels]}
+        if selective_levels:
+            out["hanging"], out["elem_levels"] = hanging[top], elem_levels
+        return out
 
-    def _mgsolve(self, K, P, bdc, SOL, RES, assemble, log, smoother, omega):
+    def _mgsolve(self, K, P, bdc, SOL, RES, assemble, log, smoother, omega, P_amr=None):
         """LinearImplicitSystem::MGsolve on a hierarchy built here: K the finest level's matrix, P[l] the transfer into level l (P[0] None), bdc[l] the Dirichlet
         dofs of level l, assemble() the callback that fills K and RES at SOL.  Rows of fine Dirichlet dofs and columns of coarse ones carry nothing in P
         (ZeroInterpolatorDirichletNodes).  Every linear iteration: the callback, the boundary rows, ||RES||_2 (stop below abs_conv_tol after the first, or after
         max_number_linear_iteration), the Galerkin chain PP^T KK PP and the boundary rows of every level, V-cycles under GMRES limited to 4 iterations (one level:
-        the exact solve), SOL += EPS.  Returns the history [(Krylov steps, ||RES||_2)]; K and P are destroyed"""
+        the exact solve), SOL += EPS.  P_amr: the projection of a non-homogeneous finest level (LinearImplicitSystem.cpp:329-342, 487-491): after the callback
+        RES <- P_amr^T RES and the operator of the cycle is P_amr^T K P_amr, whose boundary rows (bdc holds the hanging dofs too) are set; EPS <- P_amr EPS before
+        SOL += EPS.  Returns the history [(Krylov steps, ||RES||_2)]; K, P and P_amr are destroyed"""
         top = self.nlevels - 1
         for l in range(1, self.nlevels):
             if bdc[l].size:
@@ -357,13 +404,20 @@ class Poisson001:
         EPS = self.ctx.vector(RES.n_global)
         mg = capi.Multigrid(self.ctx, self.nlevels)
         A = [None] * self.nlevels
-        A[top] = K
+        A[top] = K if P_amr is None else None
         history = []
         its = 0
         for it in range(self.max_linear + 1):
             assemble()
+            if P_amr is not None:
+                EPS.matrix_mult_transpose(RES, P_amr)
+                RES.assign(EPS)
+                if A[top] is None:
+                    A[top] = capi.Mat.ptap(P_amr, K)
+                else:
+                    A[top].ptap_numeric(P_amr, K)
             if bdc[top].size:
-                K.mat_zero_rows(bdc[top], 1.0)
+                A[top].mat_zero_rows(bdc[top], 1.0)
                 RES.set(bdc[top], np.zeros(bdc[top].size))
             rn = RES.l2_norm()
             history.append((its, rn))
@@ -384,9 +438,12 @@ class Poisson001:
             mg.setup()
             EPS.zero()
             its, _ = mg.solve(RES, EPS, outer="gmres" if self.nlevels > 1 else "preonly", rtol=1e-12, atol=1e-20, maxit=4)
+            if P_amr is not None:
+                RES.matrix_mult(EPS, P_amr)
+                EPS.assign(RES)
             SOL.add(1.0, EPS)
         mg.destroy()
-        for m in A + P:
+        for m in A + P + ([K, P_amr] if P_amr is not None else []):
             if m is not None:
                 m.destroy()
         return history

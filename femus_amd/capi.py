@@ -838,6 +838,37 @@ class ElementMesh:
             _chk(self.L.fh_elem_mesh_boundary_dofs(self.h, k, int(fl.size), _p(fl), ctypes.byref(n), _p(out)))
         return out
 
+    _AMR_MODE = {"reference": 0, "coarsest": 1}
+
+    def _amr_mode(self, who, mode):
+        if mode not in self._AMR_MODE:
+            raise FemusHipError("ElementMesh.%s: mode must be \"reference\" or \"coarsest\", not %r" % (who, mode))
+        return self._AMR_MODE[mode]
+
+    def amr_constraints(self, fe, mode="reference"):
+        """the hanging dofs of a family on this level and their masters' weights (fh_elem_mesh_amr_constraints, searched on the device): (hanging[n], ptr[n + 1],
+        master[nnz], weight[nnz]), the lists of mixed_mesh.amr_constraints; empty on a homogeneous mesh"""
+        k, md = FE[fe] if isinstance(fe, str) else int(fe), self._amr_mode("amr_constraints", mode)
+        n, nnz = ctypes.c_int(0), ctypes.c_int(0)
+        _chk(self.L.fh_elem_mesh_amr_constraints(self.h, k, md, ctypes.byref(n), ctypes.byref(nnz), None, None, None, None))
+        hang, ptr = np.empty(n.value, np.int32), np.empty(n.value + 1, np.int32)
+        master, w = np.empty(nnz.value, np.int32), np.empty(nnz.value)
+        _chk(self.L.fh_elem_mesh_amr_constraints(self.h, k, md, ctypes.byref(n), ctypes.byref(nnz), _p(hang), _p(ptr), _p(master), _p(w)))
+        return hang, ptr, master, w
+
+    def amr_prolongator(self, fe, mode="reference"):
+        """P_amr of a family (fh_elem_mesh_amr_prolongator): a resident Mat of own[fe] rows and columns, the identity with the rows of the hanging dofs replaced by
+        their masters' weights and an explicit zero on the diagonal"""
+        h = ctypes.c_void_p()
+        _chk(self.L.fh_elem_mesh_amr_prolongator(self.h, FE[fe] if isinstance(fe, str) else int(fe), self._amr_mode("amr_prolongator", mode), ctypes.byref(h)))
+        return Mat(self.ctx, h)
+
+    def amr_timings(self):
+        """milliseconds of the last constraint search on this mesh: {"search", "download", "resolution"}"""
+        ms = (ctypes.c_double * 3)()
+        _chk(self.L.fh_elem_mesh_amr_timings(self.h, ms))
+        return {"search": ms[0], "download": ms[1], "resolution": ms[2]}
+
     def destroy(self):
         if self.h:
             _chk(self.L.fh_elem_mesh_destroy(self.h))

@@ -230,6 +230,7 @@ extern "C" int fh_set_option(fh_ctx_t c, const char* name, double value) {
   else if (!strcmp(name, "assemble_rows2")) c->assemble_rows2 = (int)value;
   else if (!strcmp(name, "generic_pack")) c->generic_pack = (int)value;
   else if (!strcmp(name, "elem_transfer_lds_rows")) c->elem_transfer_lds_rows = (int)value;
+  else if (!strcmp(name, "elem_constraints_host")) c->elem_constraints_host = (int)value;
   else if (!strcmp(name, "assemble_sf")) c->assemble_sf = (int)value;
   else if (!strcmp(name, "assemble_rows_nt")) c->assemble_rows_nt = (int)value;
   else if (!strcmp(name, "assemble_fused")) c->assemble_fused = (int)value;

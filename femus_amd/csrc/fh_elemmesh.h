@@ -1,4 +1,5 @@
-// The device-resident element mesh (fh_elemmesh.hip): what the builders of its transfers and boundary lists (fh_elemtransfer.hip) see of it.
+// The device-resident element mesh (fh_elemmesh.hip): what the builders of its transfers and boundary lists (fh_elemtransfer.hip) and of its hanging-node
+// constraints (fh_elemconstraints.hip) see of it.
 #pragma once
 #include "fh_internal.h"
 #include <memory>
@@ -38,8 +39,58 @@ struct fh_elem_mesh_s {
   unsigned char* d_flags = nullptr;               // [nel] what fh_elem_mesh_flag left (null until then)
   bool homogeneous = true;        // every element is of the mesh's level
   std::shared_ptr<EmDevTables> tab;               // shared along a chain of refinements
+  bool levels_unset = false;      // built from host arrays and fh_elem_mesh_set_levels never called: "homogeneous" is then only what nobody contradicted
+  std::shared_ptr<struct AmrRows> amr_pending;    // rows the sizing call of fh_elem_mesh_amr_constraints found, for the filling call that follows it (then dropped)
+  int amr_pending_key = -1;
+  double amr_ms[3] = {0.0, 0.0, 0.0};             // the last search: search (kernels, or the host search), download, resolution
   ~fh_elem_mesh_s() {
     for (void* q : {(void*)d_geom, (void*)d_ed, (void*)d_x, (void*)d_ff, (void*)d_lev, (void*)d_father, (void*)d_child, (void*)d_flags})
       if (q) hipFree(q);
+  }
+};
+
+// ---- the open-addressing tables of edge and face keys (the refinement's; the interface faces of fh_elemconstraints.hip are counted in tables of the same kind) ----
+constexpr unsigned long long EM_EMPTY = ~0ull;
+// plain read, then CAS, then the returned value: a stale plain read can only show "empty", and the CAS corrects it (fh_meshdev.hip: rf_insert)
+__device__ __forceinline__ int em_insert(unsigned long long* keys, unsigned mask, int shift, unsigned long long key) {
+  unsigned s = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> shift) & mask;
+  for (;;) {
+    unsigned long long old = keys[s];
+    if (old == key) return (int)s;
+    if (old == EM_EMPTY) {
+      old = atomicCAS(&keys[s], EM_EMPTY, key);
+      if (old == EM_EMPTY || old == key) return (int)s;
+    }
+    s = (s + 1) & mask;
+  }
+}
+__device__ __forceinline__ unsigned long long em_pair(int a, int b) { return ((unsigned long long)(unsigned)a << 32) | (unsigned)b; }
+
+struct EmHash {
+  unsigned long long* keys;
+  unsigned mask;
+  int shift, id0;                 // id0: the first provisional id of the family
+};
+
+
+// device work buffers of one entry point, freed on return
+struct EmScratch {
+  const char* who;                // the entry point, for the message
+  std::vector<void*> p;
+  explicit EmScratch(const char* w) : who(w) {}
+  ~EmScratch() {
+    for (void* q : p)
+      if (q) hipFree(q);
+  }
+  template <class T>
+  int get(T** out, size_t n) {
+    void* q = nullptr;
+    if (hipMalloc(&q, std::max<size_t>(n, 2) * sizeof(T)) != hipSuccess) {
+      fh_set_error("%s: out of device memory", who);
+      return 2;
+    }
+    p.push_back(q);
+    *out = (T*)q;
+    return 0;
   }
 };

@@ -35,7 +35,6 @@
 #include <mutex>
 
 namespace {
-constexpr unsigned long long EM_EMPTY = ~0ull;
 constexpr int EM_NONE = 0x7f7f7f7f;
 
 struct EmTables {
@@ -142,26 +141,6 @@ const EmTables& em_tables() {
   return T;
 }
 
-struct Scratch {
-  const char* who;                // the entry point, for the message
-  std::vector<void*> p;
-  explicit Scratch(const char* w) : who(w) {}
-  ~Scratch() {
-    for (void* q : p)
-      if (q) hipFree(q);
-  }
-  template <class T>
-  int get(T** out, size_t n) {
-    void* q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(n, 2) * sizeof(T)) != hipSuccess) {
-      fh_set_error("%s: out of device memory", who);
-      return 2;
-    }
-    p.push_back(q);
-    *out = (T*)q;
-    return 0;
-  }
-};
 }   // namespace
 
 // ---- kernels: one thread per (fine element, column of the padded row) ------------------------------------------------------------------------------------
@@ -256,21 +235,6 @@ __global__ __launch_bounds__(256) void k_em_flag_elements(const EmTab* __restric
   flags[e] = fhx_truth(fh_expr_device_eval(code, ncode, consts, v)) != 0.0 ? 1 : 0;
 }
 
-// plain read, then CAS, then the returned value: a stale plain read can only show "empty", and the CAS corrects it (fh_meshdev.hip: rf_insert)
-__device__ __forceinline__ int em_insert(unsigned long long* keys, unsigned mask, int shift, unsigned long long key) {
-  unsigned s = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> shift) & mask;
-  for (;;) {
-    unsigned long long old = keys[s];
-    if (old == key) return (int)s;
-    if (old == EM_EMPTY) {
-      old = atomicCAS(&keys[s], EM_EMPTY, key);
-      if (old == EM_EMPTY || old == key) return (int)s;
-    }
-    s = (s + 1) & mask;
-  }
-}
-__device__ __forceinline__ unsigned long long em_pair(int a, int b) { return ((unsigned long long)(unsigned)a << 32) | (unsigned)b; }
-
 struct EmOcc {                    // the order (class, fine element, local node)
   const int *o0, *o1, *o2;        // exclusive scans of the class widths over the coarse elements (LINKS: over the fine elements)
   int base1, base2, nch;
@@ -294,12 +258,6 @@ __device__ __forceinline__ int em_occ(const EmTab* T, const EmOcc& O, int g, int
   if (i < ne) return O.base1 + O.nch * O.o1[e] + j * (ne - nv) + (i - nv);
   return O.base2 + O.nch * O.o2[e] + j * (T->nl[g] - ne) + (i - ne);
 }
-
-struct EmHash {
-  unsigned long long* keys;
-  unsigned mask;
-  int shift, id0;                 // id0: the first provisional id of the family
-};
 
 template <bool LINKS>
 __global__ __launch_bounds__(256) void k_em_touch(const EmTab* __restrict__ T, EmOcc O, int nel_f, const int* __restrict__ geom_f, const int* __restrict__ ed_f,
@@ -426,7 +384,7 @@ extern "C" int fh_elem_mesh_create(fh_ctx_t ctx, int dim, int nel, int nnode, co
                  face_flag[(size_t)e * EM_F + f]);
     m->count[g]++;
   }
-  m->ctx = ctx; m->dim = dim; m->nel = nel; m->nnode = nnode; m->level = 0;
+  m->ctx = ctx; m->dim = dim; m->nel = nel; m->nnode = nnode; m->level = 0; m->levels_unset = true;
   for (int k = 0; k < 3; k++) m->own[k] = own[k];
   hipStream_t st = ctx->stream;
   m->tab = std::make_shared<EmDevTables>();
@@ -454,7 +412,7 @@ extern "C" int fh_elem_mesh_create(fh_ctx_t ctx, int dim, int nel, int nnode, co
 // sizes and refusals, the fine mesh's arrays, tables, first touches, numbering, coordinates.  LINKS: the fine elements of coarse element e start at d_start[e]
 // and are its children or its copy; otherwise fine element nch e + j is child j of e.
 template <bool LINKS>
-static int em_refine_finish(const char* who, fh_elem_mesh_t C, fh_elem_mesh_s* F, const int64_t fresh[EM_G], const int* d_start, Scratch& B) {
+static int em_refine_finish(const char* who, fh_elem_mesh_t C, fh_elem_mesh_s* F, const int64_t fresh[EM_G], const int* d_start, EmScratch& B) {
   const EmTab& H = em_tables().h;
   fh_ctx_t ctx = C->ctx;
   hipStream_t st = ctx->stream;
@@ -553,7 +511,7 @@ extern "C" int fh_elem_mesh_refine(fh_elem_mesh_t C, fh_elem_mesh_t* out) {
   F->ctx = C->ctx; F->dim = C->dim; F->nel = C->nel * nch; F->level = C->level + 1; F->tab = C->tab;
   int64_t fresh[EM_G];
   for (int g = 0; g < EM_G; g++) fresh[g] = F->count[g] = C->count[g] * nch;
-  Scratch B(who);
+  EmScratch B(who);
   FH_TRY(em_refine_finish<false>(who, C, F.get(), fresh, nullptr, B));
   *out = F.release();
   return 0;
@@ -569,7 +527,7 @@ extern "C" int fh_elem_mesh_refine_flagged(fh_elem_mesh_t C, const unsigned char
   hipStream_t st = ctx->stream;
   const int nch = C->dim == 3 ? 8 : 4, nel_c = C->nel;
   FH_REQUIRE((int64_t)nel_c * nch < ((int64_t)1 << 31), "%s: the children of %d elements do not fit 32-bit integers", who, nel_c);
-  Scratch B(who);
+  EmScratch B(who);
   int *d_cnt, *d_start, *d_counts, *d_bsum;
   unsigned char* d_fl = nullptr;
   const size_t nwc = (size_t)nel_c + 1;
@@ -620,7 +578,7 @@ extern "C" int fh_elem_mesh_flag(fh_elem_mesh_t m, fh_expr_t expr, unsigned char
     hipFree(m->d_flags);
     m->d_flags = nullptr;
   };
-  Scratch B(who);
+  EmScratch B(who);
   int* d_code;
   double* d_k;
   if (B.get(&d_code, code.size()) || B.get(&d_k, consts.size())) {
@@ -662,6 +620,8 @@ extern "C" int fh_elem_mesh_set_levels(fh_elem_mesh_t m, const int* lev) {
   FH_CHECK_HIP(hipStreamSynchronize(st));       // the caller's array is free again
   m->level = top;
   m->homogeneous = same;
+  m->levels_unset = false;
+  m->amr_pending.reset();
   return 0;
 }
 

@@ -97,6 +97,7 @@ struct fh_ctx_s {
   int assemble_rows2 = 1;            // row pass: two rows per 32-lane group when no row has more than 128 entries
   int elem_transfer_lds_rows = 1024;  // transfers of element meshes (fh_elemtransfer.hip): a row whose elements hold at most this many candidate slots (27 per element) is
                                      // sorted by one wave in LDS, any other by a workgroup in global scratch; same bits (1024 at most; lowered by the A/B of the bitwise test)
+  int elem_constraints_host = 0;     // hanging-node constraints of a resident element mesh (fh_elemconstraints.hip): 1 = the host search on the downloaded arrays (the A/B of the device search)
   int generic_pack = 1;              // generic assembler object (fh_generic.hip): 2 / 4 elements per wave for the narrow families; 0 = one element per wave for every shape (the A/B of the probe), read at create
   int assemble_kpad = 1;            // HEX27/Q2 two-pass assembly: element rows padded to 32 doubles (whole 64-byte lines per row)
   int assemble_sym = 1;              // symmetric-tile HEX27/Q2 element kernel (2 elements per wave)

@@ -7,6 +7,7 @@
 //   LinearEquation.cpp:407-548 (sparsity), LinearImplicitSystem.cpp:761-909,1032-1120 (prolongator)
 #include "fh_internal.h"
 #include "fh_fe.h"
+#include "fh_elemconstraints.h"
 #include <algorithm>
 #include <atomic>
 #include <thread>
@@ -809,12 +810,6 @@ extern "C" int fh_build_prolongator(fh_ctx_t ctx, fh_mesh_t mc, fh_mesh_t mf, in
 // resolved recursively.  A node on the interfaces with two coarser levels at once (3-D edges with a level jump of two)
 // has two mathematically identical descriptions; the one to the coarsest level is kept.
 // ---------------------------------------------------------------------------------------------------------------------
-struct AmrRows {
-  std::vector<int> hang;                 // sorted hanging dofs
-  std::vector<int> ptr;                  // CSR over hang
-  std::vector<int> master;
-  std::vector<double> w;
-};
 
 static bool inverse_map_q2(int geom, int dim, const double* xv /* [nloc*dim] */, const double* xp, double* xi) {
   const int nl = nloc_of(geom);
@@ -925,9 +920,7 @@ static void amr_constraints_compute(const fh_mesh_s* m, int fe, AmrRows& out) {
     inter[m->elem_level[iel]].push_back({iel, std::move(loc)});
   }
   const int ndof = mesh_ndofs(m, fe);
-  std::vector<int> owner_level(ndof, -1);
-  std::unordered_map<int, std::vector<std::pair<int, double>>> raw;
-  std::map<int, std::map<int, double>> rest;       // reference mode: master -> {son: value}, ordered like the reference's std::map
+  std::vector<AmrTriple> writes;
   for (int Lc = 0; Lc <= maxlev; Lc++) {
     if (inter[Lc].empty()) continue;
     for (int Lf = Lc + 1; Lf <= maxlev; Lf++) {
@@ -999,149 +992,20 @@ static void amr_constraints_compute(const fh_mesh_s* m, int fe, AmrRows& out) {
         for (int t = 0; t < nth; t++) th.emplace_back(search, cel.size() * t / nth, cel.size() * (t + 1) / nth);
         for (auto& x : th) x.join();
       }
-      // (2) in the order of the coarse elements: which level describes a node (mode 1), the rows, the reference's map
+      // (2) in the order of the coarse elements: the writes restriction[master][hanging] = value
       for (size_t q = 0; q < cel.size(); q++) {
         const IfaceElem& ie = cel[q];
         const int* ed = &m->elem_dof[(size_t)ie.iel * nl];
-        for (const Hit& hit : hits[q]) {
-          const int ldof = hit.ldof;
-          const double* phi = hit.phi;
-          if (m->amr_mode == 1) {
-            if (owner_level[ldof] < 0) owner_level[ldof] = Lc;
-            if (owner_level[ldof] != Lc) continue;
-          }
-          auto& row = raw[ldof];
+        for (const Hit& hit : hits[q])
           for (int n : ie.loc) {
-            if (std::fabs(phi[n]) < 1.0e-10) continue;
-            const int jd = ed[n];
-            if (m->amr_mode == 0) {          // the reference's map restriction[master][son] with its diagonal marks (Mesh.cpp:1560-1567)
-              auto& mrow = rest[jd];
-              if (mrow.find(jd) == mrow.end()) mrow[jd] = 1.;
-              mrow[ldof] = phi[n];
-              rest[ldof][ldof] = 10.;
-            }
-            bool found = false;
-            for (auto& e : row)
-              if (e.first == jd) {
-                e.second = phi[n];
-                found = true;
-              }
-            if (!found) row.emplace_back(jd, phi[n]);
+            if (std::fabs(hit.phi[n]) < 1.0e-10) continue;
+            writes.push_back({ed[n], hit.ldof, Lc, hit.phi[n]});
           }
-        }
       }
     }
   }
-  if (m->amr_mode == 0) {
-    // second half of the reference function as written (Mesh.cpp:1711-1801): for every real master (diagonal mark < 5) a depth-first
-    // walk through sons, grandsons, ...: restriction[master][son] += value * heredity(father); a son already present in the
-    // genealogy lists of the levels above the one being filled is skipped ("alreadyFound").  For a node on the interfaces with two
-    // coarser levels this keeps the direct entry and drops the path through the intermediate hanging node, so its row does not sum to
-    // one -- that is the reference's result, reproduced here.
-    const std::map<int, std::map<int, double>>& copy = rest;     // (read only from here on)
-    std::map<int, std::vector<std::pair<int, double>>> hrow;        // hanging dof -> (master, weight)
-    for (auto& kv : copy)
-      if (kv.second.at(kv.first) > 5.) hrow[kv.first];
-    std::vector<std::vector<int>> genealogy;
-    std::vector<std::vector<double>> heredity;
-    std::vector<size_t> index;
-    for (auto& kv : copy) {
-      const int inode = kv.first;
-      if (!(kv.second.at(inode) < 5.)) continue;
-      std::map<int, double> acc;
-      genealogy.assign(1, std::vector<int>(1, inode));
-      heredity.assign(1, std::vector<double>(1, 1.));
-      index.assign(1, 0);
-      size_t level = 1;
-      while (level > 0) {
-        const int father = genealogy[level - 1][index[level - 1]];
-        const double hf = heredity[level - 1][index[level - 1]];
-        genealogy.resize(level + 1);
-        heredity.resize(level + 1);
-        index.resize(level + 1);
-        genealogy[level].clear();
-        heredity[level].clear();
-        index[level] = 0;
-        for (auto& e : copy.at(father)) {
-          const int son = e.first;
-          bool found = false;
-          for (size_t kl = 0; kl < level && !found; kl++)
-            for (int g : genealogy[kl])
-              if (g == son) {
-                found = true;
-                break;
-              }
-          if (found) continue;
-          genealogy[level].push_back(son);
-          heredity[level].push_back(e.second * hf);
-          acc[son] += e.second * hf;
-        }
-        if (!genealogy[level].empty()) {
-          level++;
-        } else {
-          bool test = true;
-          while (test && level > 0) {
-            index[level - 1]++;
-            test = false;
-            if (index[level - 1] == genealogy[level - 1].size()) {
-              level--;
-              test = true;
-            }
-          }
-        }
-      }
-      for (auto& e : acc) hrow[e.first].emplace_back(inode, e.second);
-    }
-    for (auto& kv : hrow) {
-      out.hang.push_back(kv.first);
-      std::sort(kv.second.begin(), kv.second.end());
-      for (auto& e : kv.second) {
-        out.master.push_back(e.first);
-        out.w.push_back(e.second);
-      }
-      out.ptr.push_back((int)out.master.size());
-    }
-    return;
-  }
-  // resolve masters that hang themselves (depth-first, masters in increasing dof order)
-  std::unordered_map<int, std::vector<std::pair<int, double>>> res;
-  std::function<const std::vector<std::pair<int, double>>&(int, int)> expand = [&](int l, int depth) -> const std::vector<std::pair<int, double>>& {
-    auto it = res.find(l);
-    if (it != res.end()) return it->second;
-    std::vector<std::pair<int, double>> row = raw[l];
-    std::sort(row.begin(), row.end());
-    std::vector<std::pair<int, double>> acc;
-    auto add = [&](int j, double w) {
-      for (auto& e : acc)
-        if (e.first == j) {
-          e.second += w;
-          return;
-        }
-      acc.emplace_back(j, w);
-    };
-    for (auto& e : row) {
-      if (raw.count(e.first) && depth < 16) {
-        const auto sub = expand(e.first, depth + 1);   // copy: the map may rehash below
-        for (auto& s : sub) add(s.first, e.second * s.second);
-      } else {
-        add(e.first, e.second);
-      }
-    }
-    std::sort(acc.begin(), acc.end());
-    return res.emplace(l, std::move(acc)).first->second;
-  };
-  std::vector<int> hang;
-  for (auto& kv : raw) hang.push_back(kv.first);
-  std::sort(hang.begin(), hang.end());
-  for (int l : hang) {
-    const auto& row = expand(l, 0);
-    out.hang.push_back(l);
-    for (auto& e : row) {
-      out.master.push_back(e.first);
-      out.w.push_back(e.second);
-    }
-    out.ptr.push_back((int)out.master.size());
-  }
+  // which level describes a node (mode 1), the later write of a pair, masters that hang themselves: the resolution every search shares
+  fh_amr_resolve(writes, ndof, m->amr_mode, out);
 }
 
 extern "C" int fh_mesh_set_amr_mode(fh_mesh_t m, int mode) {
@@ -1171,9 +1035,7 @@ extern "C" int fh_mesh_amr_constraints(fh_mesh_t m, int fe, int* n_hanging, int*
   FH_GUARD_END("fh_mesh_amr_constraints")
 }
 
-// P_amr (n x n): identity rows for regular dofs; a hanging dof's row holds its master weights and an explicit zero on
-// the diagonal (the reference inserts restriction[son][son] = 0, which keeps (son, son) in the pattern of P^T K P so
-// that SetPenalty can put its 1 there)
+// P_amr (n x n): fh_amr_prolongator_csr (fh_elemconstraints.cpp)
 extern "C" int fh_build_amr_prolongator(fh_ctx_t ctx, fh_mesh_t m, int fe, fh_mat_t* out) {
   FH_GUARD_BEGIN
   FH_REQUIRE(ctx && m && out, "fh_build_amr_prolongator: null argument");
@@ -1181,27 +1043,9 @@ extern "C" int fh_build_amr_prolongator(fh_ctx_t ctx, fh_mesh_t m, int fe, fh_ma
   AmrRows R;
   amr_constraints(m, fe, R);
   const int n = mesh_ndofs(m, fe);
-  std::vector<int> rowptr(n + 1, 0), col;
+  std::vector<int> rowptr, col;
   std::vector<double> val;
-  size_t h = 0;
-  std::vector<std::pair<int, double>> row;
-  for (int i = 0; i < n; i++) {
-    if (h < R.hang.size() && R.hang[h] == i) {
-      row.clear();
-      row.emplace_back(i, 0.0);
-      for (int k = R.ptr[h]; k < R.ptr[h + 1]; k++) row.emplace_back(R.master[k], R.w[k]);
-      std::sort(row.begin(), row.end());
-      for (auto& e : row) {
-        col.push_back(e.first);
-        val.push_back(e.second);
-      }
-      h++;
-    } else {
-      col.push_back(i);
-      val.push_back(1.0);
-    }
-    rowptr[i + 1] = (int)col.size();
-  }
+  FH_REQUIRE(fh_amr_prolongator_csr(R, n, rowptr, col, val), "fh_build_amr_prolongator: a hanging dof beyond the %d dofs", n);
   return fh_mat_create_csr(ctx, n, n, rowptr.data(), col.data(), val.data(), out);
   FH_GUARD_END("fh_build_amr_prolongator")
 }

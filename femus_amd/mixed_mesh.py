@@ -15,6 +15,8 @@ tetrahedra and prisms in one file; the two-dimensional files of quadrilaterals a
                   children, every other element one unchanged copy, in coarse element order; new nodes come from the children alone, by the keys and the
                   creating child of refine; the numbering walks all fine elements, copies included
     flag_elements   MeshRefinement::FlagElementsToRefine type 1: a function of the mean of an element's vertices and the level, elements of the level only
+    amr_constraints  Mesh::GetAMRRestrictionAndAMRSolidMark (Mesh.cpp:1354-1830) for every shape, in the library on the host (fh_elem_amr_constraints_host): the hanging
+                  dofs of a flagged level and their masters' weights
     numbering     vertices, then edge middles, then the rest, each class in order of first appearance walking the elements
 """
 import numpy as np
@@ -427,3 +429,29 @@ def flag_elements(kind, ed, xs, lev, level, fn):
             x[d] = x[d] / float(nv)
         out[e] = 1 if fn(x, level) else 0
     return out
+
+
+def amr_constraints(kind, ed, xs, ff, lev, fe, mode="reference"):
+    """(hanging[n], ptr[n + 1], master[nnz], weight[nnz]) of a level whose elements have the levels lev[nel]: the hanging dofs of the family fe ("linear",
+    "serendipity", "biquadratic") ascending, the masters ascending within a row.  mode "reference": chains resolved as the reference does; "coarsest": a node is
+    described by the coarsest level that finds it and masters that hang themselves are expanded (rows sum to one).  Runs in the library, without a device"""
+    import ctypes
+    if mode not in ("reference", "coarsest"):
+        raise capi.FemusHipError("mixed_mesh.amr_constraints: mode must be \"reference\" or \"coarsest\", not %r" % (mode,))
+    kind, xs = np.asarray(kind), capi._f64(xs)
+    code = np.zeros(kind.shape[0], dtype=np.int32)
+    for name, c in capi.GEOM.items():
+        code[kind == name] = c
+    ed, ff, lev = capi._i32(ed), capi._i32(ff), capi._i32(lev)
+    nel = kind.shape[0]
+    if ed.shape != (nel, 27) or ff.shape != (nel, 6) or lev.shape != (nel,) or xs.ndim != 2:
+        raise capi.FemusHipError("mixed_mesh.amr_constraints: ed must be [%d, 27], ff [%d, 6], lev [%d] and xs [nnode, dim]" % (nel, nel, nel))
+    L = capi.load_library()
+    k, md = capi.FE[fe] if isinstance(fe, str) else int(fe), 0 if mode == "reference" else 1
+    args = (int(xs.shape[1]), nel, int(xs.shape[0]), capi._p(code), capi._p(ed), capi._p(xs), capi._p(ff), capi._p(lev), k, md)
+    n, nnz = ctypes.c_int(0), ctypes.c_int(0)
+    capi._chk(L.fh_elem_amr_constraints_host(*args, ctypes.byref(n), ctypes.byref(nnz), None, None, None, None))
+    hang, ptr = np.empty(n.value, np.int32), np.empty(n.value + 1, np.int32)
+    master, w = np.empty(nnz.value, np.int32), np.empty(nnz.value)
+    capi._chk(L.fh_elem_amr_constraints_host(*args, ctypes.byref(n), ctypes.byref(nnz), capi._p(hang), capi._p(ptr), capi._p(master), capi._p(w)))
+    return hang, ptr, master, w

@@ -288,7 +288,7 @@ int fh_mesh_dirichlet_dofs(fh_mesh_t mesh, int fe, int* n, int* dofs);
  *                   refine's, with none the coarse mesh's.  Two small copies come back: the fine and the split elements per shape (integer sums), then the
  *                   class ends.  Integers and coordinate bits are those of mixed_mesh.py: refine_flagged; the 32-bit refusals are refine's.
  *   elem_levels     downloads lev / father / child [nel] (any pointer may be NULL); *homogeneous: every element is of the mesh's level.
- * The hanging nodes of a flagged level are NOT constrained here (fh_mesh_amr_constraints does that for fh_mesh_t only). */
+ * The hanging nodes of a flagged level are constrained by fh_elem_mesh_amr_constraints / fh_elem_mesh_amr_prolongator, further down. */
 typedef struct fh_elem_mesh_s* fh_elem_mesh_t;
 int fh_elem_mesh_create(fh_ctx_t ctx, int dim, int nel, int nnode, const int* elem_geom, const int* elem_dof, const double* coords, const int* face_flag,
                         const int own[3], fh_elem_mesh_t* mesh);
@@ -321,6 +321,37 @@ int fh_elem_mesh_destroy(fh_elem_mesh_t mesh);
  * face)].  Two-call protocol: with dofs = NULL the number comes back in *ndofs; the second call takes it there and fills dofs[*ndofs]. */
 int fh_elem_mesh_prolongator(fh_elem_mesh_t coarse, fh_elem_mesh_t fine, int fe, fh_mat_t* P);
 int fh_elem_mesh_boundary_dofs(fh_elem_mesh_t mesh, int fe, int nflags, const int* flags, int* ndofs, int* dofs /* NULL on the first call */);
+
+/* ---- hanging-node constraints of element meshes of any shape (fh_elemconstraints.cpp, fh_elemconstraints.hip) ----
+ * Mesh::GetAMRRestrictionAndAMRSolidMark (Mesh.cpp:1354-1830) for every shape: what fh_mesh_amr_constraints is to fh_mesh_t.  A face is an interface face when
+ * its flag is -1 and no other element holds all of its vertices; an element with one is an interface element of its level, and the nodes of those faces that
+ * the family holds (fh_fe_face_nodes) are its interface local nodes.  For every pair of levels Lc < Lf, in that order, and every coarse interface element in
+ * element order, the finer level's interface nodes inside the element's 1 % padded bounding box and hull sphere that are no dofs of it are mapped back by a
+ * Newton inverse of the biquadratic map, started at the reference point of the nearest node; a node that lands inside the shape's reference domain (eps 1e-4)
+ * hangs on the element with the family's functions of the interface local nodes as weights (|v| >= 1e-10).  A later write of a (master, hanging) pair replaces
+ * an earlier one.  mode 0 resolves chains as the reference does (a node between two coarser levels keeps a row that does not sum to one), mode 1 keeps the
+ * description by the coarsest level and expands masters that hang themselves (rows sum to one).  fe: 0 linear, 1 serendipity, 2 biquadratic.
+ * Two-call protocol as fh_mesh_amr_constraints: with hanging = NULL the sizes come back; then hanging[n_hanging] ascending, ptr[n_hanging + 1],
+ * master[nnz] ascending within a row, weight[nnz] (an expanded row may hold an exact 0.0).
+ *   fh_elem_amr_constraints_host   the rule on plain arrays (elem_dof[nel*27], face_flag[nel*6], lev[nel]), no device; at most 16 threads.
+ *   fh_elem_mesh_amr_constraints   the same for a resident mesh with the search and the inverse maps on the device: interface faces through a hash table of
+ *                                  the face keys (one pass counts, one marks), interface elements and the finer levels' interface nodes compacted by scans, one
+ *                                  wave per coarse interface element streaming the node list through LDS, count / scan / fill, so that the entries come out
+ *                                  in the order above whatever the threads do (no floating-point atomics: bitwise repeatable).  The entries are downloaded
+ *                                  and resolved on the host.  A homogeneous mesh has none.  fh_set_option(ctx, "elem_constraints_host", 1) runs the host
+ *                                  search on the downloaded arrays instead (the A/B).  Refused before any launch: fe outside 0 .. 2, mode outside 0 / 1.  A mesh from
+ *                                  fh_elem_mesh_create whose levels were never set passes for homogeneous; the face count alone is run on it, and if it shows a
+ *                                  face with no neighbour and no boundary flag the call is refused before the search (fh_elem_mesh_set_levels was forgotten).
+ *   fh_elem_mesh_amr_prolongator   P_amr (own[fe] x own[fe]) as fh_build_amr_prolongator builds it: identity rows, a hanging dof's row = its masters plus an
+ *                                  explicit zero on the diagonal; the identity on a homogeneous mesh. */
+int fh_elem_amr_constraints_host(int dim, int nel, int nnode, const int* elem_geom, const int* elem_dof /* [nel*27] */, const double* coords,
+                                 const int* face_flag /* [nel*6] */, const int* lev /* [nel] */, int fe, int mode, int* n_hanging, int* nnz, int* hanging, int* ptr,
+                                 int* master, double* weight);
+int fh_elem_mesh_amr_constraints(fh_elem_mesh_t mesh, int fe, int mode, int* n_hanging, int* nnz, int* hanging, int* ptr, int* master, double* weight);
+int fh_elem_mesh_amr_prolongator(fh_elem_mesh_t mesh, int fe, int mode, fh_mat_t* P_amr);
+/* wall-clock milliseconds of the last search on this mesh: ms[0] the search (the kernels with their scans and size read-backs, or the host search), ms[1] the
+ * download of the entries (of the mesh, for the host search), ms[2] the resolution into rows */
+int fh_elem_mesh_amr_timings(fh_elem_mesh_t mesh, double ms[3]);
 
 /* ---- sparsity (a11): LinearEquation::GetSparsityPatternSize (03_solvers/LinearEquation.cpp:407-548) ----
  * CSR pattern of the element-connectivity graph: two-call protocol (rowptr first, then col). */
