@@ -1090,14 +1090,15 @@ def solve_pcg_mg(H, rtol=1e-10, maxit=100, **kw):
     return x, hist
 
 
-def solve_gmres_mg(H, rtol=1e-10, maxit=100, restart=30, **kw):
-    """left-preconditioned restarted GMRES, preconditioner = one V-cycle, zero initial guess
+def solve_gmres_mg(H, rtol=1e-10, maxit=100, restart=30, knoll=False, **kw):
+    """left-preconditioned restarted GMRES, preconditioner = one V-cycle, zero initial guess -- or, with knoll=True, the guess x0 = M b
+    (KSPSetInitialGuessKnoll, :308) the device's solvers start from
     (LinearEquationSolverPetsc.cpp:294-335; KSPGMRES default = classical Gram-Schmidt, left PC,
-    convergence on the preconditioned residual norm)."""
+    convergence on the preconditioned residual norm, relative to ||M b||)."""
     A, b = H.A[-1], H.b
     L = len(H.A) - 1
     M = lambda v: vcycle(H, L, v, **kw)
-    x = np.zeros_like(b)
+    x = M(b) if knoll else np.zeros_like(b)
     hist = []
     its = 0
     beta0 = None
