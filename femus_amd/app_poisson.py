@@ -236,7 +236,8 @@ class Poisson001:
             return None
         return seen.pop() if seen in ({"tet"}, {"wedge"}) else "mixed"
 
-    def run_elements(self, log=None, smoother=capi.SMOOTH_GS_COLOR, omega=1.0, transfers="device", selective_levels=0, flag=None, amr_mode="reference"):
+    def run_elements(self, log=None, smoother=capi.SMOOTH_GS_COLOR, omega=1.0, transfers="device", selective_levels=0, flag=None, amr_mode="reference",
+                     mesh_data="host"):
         """LinearImplicitSystem::MGsolve on the meshes femus_amd/mixed_mesh.py builds, in all three Lagrange families: the TRI6 box (TRI7 inside; the box's
         boundary conditions and source), Gambit files of TET10 (input3D_Tet_*.json with input/cube_Tet.neu; TET15 inside), of WEDGE18 (input3D_Wedge_*.json with
         input/cube_Wedge.neu; WEDGE21 inside), of mixed shapes (input3D.json / input3D_All_first.json with input/cube_all_shapes_Six_boundary_groups.neu:
@@ -252,12 +253,21 @@ class Poisson001:
         RES <- P_amr^T RES, the operator P_amr^T KK P_amr, EPS <- P_amr EPS (_mgsolve).  The start vector is made conforming, SOL <- P_amr SOL, so that a hanging
         dof with a master on the Dirichlet boundary starts from its masters' values.  Only with transfers "device".
         result["levels"]: (ed, xs, ff) of every level; ed and ff as wide as the shape, or padded to 27 and 6 on the mixed path; result["hanging"]: the top
-        level's hanging dofs; result["elem_levels"]: the level of every element of the top level"""
+        level's hanging dofs; result["elem_levels"]: the level of every element of the top level.
+        mesh_data: "host" downloads every level (capi.ElementMesh.arrays) and makes the pattern, the plan of the element loop and the boundary data from the
+        arrays.  "device" (only with transfers "device") makes them where the levels live -- capi.ElementMesh.matrix, capi.GenericAssembler.from_mesh,
+        boundary_owners and boundary_faces of the top level -- and brings down the top level's coordinates alone, for result["coords"] and the Neumann calls;
+        no level is downloaded, so result["levels"] is ABSENT in this mode.  Everything else in the result is the same, bit for bit."""
         from . import mixed_mesh
         ctx = self.ctx
         levels = [mixed_mesh.tri_box(self.box[0], self.box[1], self.lo[:2], self.hi[:2]) if self.box is not None else mixed_mesh.read_gambit(self.mesh_file)]
         if transfers not in ("device", "host"):
             raise ValueError("transfers must be \"device\" or \"host\", not %r" % (transfers,))
+        if mesh_data not in ("device", "host"):
+            raise ValueError("mesh_data must be \"device\" or \"host\", not %r" % (mesh_data,))
+        if mesh_data == "device" and transfers != "device":
+            raise ValueError("mesh_data \"device\" keeps the levels on the device: transfers must be \"device\", not %r" % (transfers,))
+        resident_data = mesh_data == "device"
         fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
         selective_levels = int(selective_levels)
         if selective_levels:
@@ -273,9 +283,10 @@ class Poisson001:
         elem_levels = None
         # level 0 goes up once and is refined on the device (capi.ElementMesh: the arrays of mixed_mesh.refine, integer for integer and bit for bit); the
         # transfers and the Dirichlet lists are built from the resident meshes; every level comes down once for result["levels"], the flux faces and the top
-        # level's boundary values
+        # level's boundary values -- or, with mesh_data "device", none does: pattern, plan and boundary data are made from the resident top level
         resident = [capi.ElementMesh.from_arrays(ctx, *levels[0])]
         P_dev, bdc_dev = [None], []
+        K = gen = top_data = None
         try:
             for l in range(1, self.nlevels):
                 if l < n_uniform:
@@ -283,7 +294,8 @@ class Poisson001:
                 else:
                     resident[-1].flag(flag)
                     resident.append(resident[-1].refine("resident"))
-                levels.append(resident[-1].arrays())
+                if not resident_data:
+                    levels.append(resident[-1].arrays())
             for l, m in enumerate(resident):
                 if not m.homogeneous:
                     hanging[l] = m.amr_constraints(fam, amr_mode)[0]
@@ -297,13 +309,23 @@ class Poisson001:
                     bdc_dev.append(m.boundary_dofs(fam, dirichlet))
                     if l:
                         P_dev.append(resident[l - 1].prolongator(m, fam))
+            if resident_data:
+                # pattern, plan and boundary data of the top level from its device copy; the faces of every flag that is not Dirichlet, each flag's list in
+                # (element, face) order, for the flux terms
+                m = resident[-1]
+                K = m.matrix(fam)
+                gen = capi.GenericAssembler.from_mesh(m, fam, K)
+                other = sorted({int(f) for f in np.unique(levels[0][3]) if f < -1} - set(dirichlet))
+                top_data = (m.boundary_owners(fam, dirichlet), {f: m.boundary_faces(fam, [f]) for f in other}, m.coords(), list(m.own), m.dim)
         except BaseException:
-            for p in P_dev[1:] + [q for q in P_amr if q is not None]:
+            for p in P_dev[1:] + [q for q in P_amr if q is not None] + [q for q in (gen, K) if q is not None]:
                 p.destroy()
             raise
         finally:
             for m in resident:
                 m.destroy()
+        if resident_data:
+            return self._run_resident(K, gen, top_data, P_dev, bdc_dev, P_amr, hanging, elem_levels, selective_levels, log, smoother, omega)
         if not self.mixed:
             g = self.geom
             levels = [(kind, ed[:, :mixed_mesh.NLOC[g]], xs, ff[:, :mixed_mesh.NFACES[g]], own) for kind, ed, xs, ff, own in levels]
@@ -316,7 +338,6 @@ class Poisson001:
         kind, ed, xs, ff, _ = levels[top]
         ndof = ndofs[top]
         K = self._pattern_from_elements([ed[idx][:, :nc] for _, idx, nc in groups[top]], ndof)
-        SOL, RES = ctx.vector(ndof), ctx.vector(ndof)
         sol0 = np.zeros(ndof)
         bdc = []
         flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals = [], [], [], [], []
@@ -349,6 +370,51 @@ class Poisson001:
                 sol0[idx] = [val[i] for i in idx]
         P = P_dev if transfers == "device" else [None] + [self._prolongator_from_children(groups[l - 1], levels[l - 1][1], levels[l][1], ndofs[l - 1], ndofs[l])
                                                           for l in range(1, self.nlevels)]
+        # the plan of the element loop, made once: every linear iteration assembles on the same mesh and pattern
+        out = self._solve_elements(K, lambda: capi.GenericAssembler(ctx, kind if self.mixed else self.geom, self.fe, ed, xs, K), xs, ndof, dim, sol0, bdc, P, P_amr,
+                                   hanging, elem_levels, selective_levels, (flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals), log, smoother, omega)
+        out["levels"] = [lv[1:4] for lv in levels]
+        return out
+
+    def _run_resident(self, K, gen, top_data, P, bdc, P_amr, hanging, elem_levels, selective_levels, log, smoother, omega):
+        """the rest of run_elements with mesh_data "device": K and gen were made from the resident top level; top_data = (boundary_owners of the Dirichlet flags,
+        {flag: boundary_faces} of the others, the top level's coordinates, own, dim).  The face loop of the host path, stated on the lists: a Dirichlet dof takes
+        the function of the last face that holds it; the flux faces go in (element, face) order"""
+        (b_dofs, b_flag, b_xy), faces, xs, own, dim = top_data
+        fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
+        ndof = own[fam]
+        sol0 = np.zeros(ndof)
+        for f in np.unique(b_flag):
+            fn = self.face_bc(int(f))[1]
+            if fn is not None:
+                sel = b_flag == f
+                x4 = np.zeros((int(sel.sum()), 4))
+                x4[:, :dim] = b_xy[sel]
+                sol0[b_dofs[sel]] = fn(x4)
+        flags = sorted(faces)
+        where = np.concatenate([6 * faces[f][0].astype(np.int64) + faces[f][1] for f in flags] + [np.zeros(0, np.int64)])
+        rows = [(f, faces[f][2][k, :faces[f][3][k]]) for f in flags for k in range(faces[f][0].size)]
+        flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals = [], [], [], [], []
+        for k in np.argsort(where, kind="stable"):                # the flux faces alone, in the order of the face loop
+            f, nodes = rows[k]
+            fn = self.face_bc(f)[1]
+            if fn is not None:                                    # parsed flux (box inputs)
+                if fn not in flux_exprs:
+                    flux_exprs.append(fn)
+                flux_faces.append(nodes)
+                flux_idx.append(flux_exprs.index(fn))
+            elif self.box is None and f in self.file_flux:        # the constant flux of SetBoundaryCondition (mesh-file inputs)
+                tau_faces.append(nodes)
+                tau_vals.append(self.file_flux[f])
+        return self._solve_elements(K, lambda: gen, xs, ndof, dim, sol0, list(bdc), P, P_amr, hanging, elem_levels, selective_levels,
+                                    (flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals), log, smoother, omega)
+
+    def _solve_elements(self, K, make_gen, xs, ndof, dim, sol0, bdc, P, P_amr, hanging, elem_levels, selective_levels, flux, log, smoother, omega):
+        """run_elements from the start vector on: K the top level's matrix, make_gen() its GenericAssembler, xs the top level's coordinates on the host, bdc[l] and
+        P[l] of every level, flux = (flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals) of the top level.  Returns the result dictionary without "levels" """
+        ctx, top = self.ctx, self.nlevels - 1
+        flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals = flux
+        SOL, RES = ctx.vector(ndof), ctx.vector(ndof)
         SOL.upload(sol0)
         if selective_levels:
             bdc = [np.union1d(b, hanging[l]).astype(np.int32) for l, b in enumerate(bdc)]
@@ -364,8 +430,7 @@ class Poisson001:
                 RES.matrix_mult(SOL, P_amr[top])
                 SOL.assign(RES)
 
-        # the plan of the element loop, made once: every linear iteration assembles on the same mesh and pattern
-        gen = capi.GenericAssembler(ctx, kind if self.mixed else self.geom, self.fe, ed, xs, K)
+        gen = make_gen()
 
         def assemble():
             gen.assemble(K, RES, sol=SOL, source=self.source, scale=1.0)
@@ -381,8 +446,7 @@ class Poisson001:
             history = self._mgsolve(K, P, bdc, SOL, RES, assemble, log, smoother, omega, P_amr=P_amr[top])
         finally:
             gen.destroy()
-        out = {"solution": SOL.to_numpy(), "coords": xs[:ndof], "history": history, "converged": history[-1][1] < self.abs_tol, "dofs": ndof,
-               "levels": [lv[1:4] for lv in levels]}
+        out = {"solution": SOL.to_numpy(), "coords": xs[:ndof], "history": history, "converged": history[-1][1] < self.abs_tol, "dofs": ndof}
         if selective_levels:
             out["hanging"], out["elem_levels"] = hanging[top], elem_levels
         return out

@@ -838,6 +838,45 @@ class ElementMesh:
             _chk(self.L.fh_elem_mesh_boundary_dofs(self.h, k, int(fl.size), _p(fl), ctypes.byref(n), _p(out)))
         return out
 
+    def coords(self):
+        """xs[nnode, dim] alone (fh_elem_mesh_get with the other arrays null)"""
+        xs = np.empty((self.nnode, self.dim))
+        _chk(self.L.fh_elem_mesh_get(self.h, None, None, _p(xs), None))
+        return xs
+
+    def matrix(self, fe):
+        """the square pattern of a family over its own[fe] dofs, built from the resident element table (fh_elem_mesh_matrix): a resident Mat with the rows and
+        columns of app_poisson._pattern_from_elements on the downloaded level"""
+        h = ctypes.c_void_p()
+        _chk(self.L.fh_elem_mesh_matrix(self.h, FE[fe] if isinstance(fe, str) else int(fe), ctypes.byref(h)))
+        return Mat(self.ctx, h)
+
+    def boundary_faces(self, fe, flags):
+        """the faces whose flag is one of `flags`, ascending by (element, face) (fh_elem_mesh_boundary_faces): (elem[n], face[n], nodes[n, 9], nn[n]), int32;
+        nodes: the family's dofs on the face in the order of fe_face_nodes, padded with -1; nn: how many"""
+        k = FE[fe] if isinstance(fe, str) else int(fe)
+        fl = _i32(np.asarray(list(flags), dtype=np.int64).reshape(-1))
+        args = (self.h, k, int(fl.size), _p(fl) if fl.size else None)
+        n = ctypes.c_int(0)
+        _chk(self.L.fh_elem_mesh_boundary_faces(*args, ctypes.byref(n), None, None, None, None))
+        elem, face, nodes, nn = (np.empty(n.value, np.int32), np.empty(n.value, np.int32), np.empty((n.value, 9), np.int32), np.empty(n.value, np.int32))
+        if n.value:
+            _chk(self.L.fh_elem_mesh_boundary_faces(*args, ctypes.byref(n), _p(elem), _p(face), _p(nodes), _p(nn)))
+        return elem, face, nodes, nn
+
+    def boundary_owners(self, fe, flags):
+        """(dofs[n], owner_flag[n], coords[n, dim]) (fh_elem_mesh_boundary_owners): the dofs of boundary_dofs, for each the flag of the last listed (element,
+        face) that holds it -- a later face overwrites an earlier one -- and its coordinates"""
+        k = FE[fe] if isinstance(fe, str) else int(fe)
+        fl = _i32(np.asarray(list(flags), dtype=np.int64).reshape(-1))
+        args = (self.h, k, int(fl.size), _p(fl) if fl.size else None)
+        n = ctypes.c_int(0)
+        _chk(self.L.fh_elem_mesh_boundary_owners(*args, ctypes.byref(n), None, None, None))
+        dofs, owner, xy = np.empty(n.value, np.int32), np.empty(n.value, np.int32), np.empty((n.value, self.dim))
+        if n.value:
+            _chk(self.L.fh_elem_mesh_boundary_owners(*args, ctypes.byref(n), _p(dofs), _p(owner), _p(xy)))
+        return dofs, owner, xy
+
     _AMR_MODE = {"reference": 0, "coarsest": 1}
 
     def _amr_mode(self, who, mode):
@@ -943,6 +982,29 @@ class GenericAssembler:
         self.h = ctypes.c_void_p()
         _chk(self.L.fh_generic_assembler_create(ctx.h, FE[fe], GAUSS_ORDER[order], ed.shape[0], ed.shape[1], None if eg is None else _p(eg), g, _p(ed),
                                                 x.shape[0], _p(x), K.h, ctypes.byref(self.h)))
+
+    @classmethod
+    def from_mesh(cls, mesh, fe, K, order="seventh"):
+        """the same object with its plan made on the device from a resident ElementMesh (fh_generic_assembler_create_from_mesh): nothing of the mesh comes to the
+        host, and the mesh may be destroyed afterwards.  K: square of mesh.own[fe] dofs, on the mesh's context"""
+        self = cls.__new__(cls)
+        self.ctx, self.L = mesh.ctx, mesh.ctx.L
+        self.h = ctypes.c_void_p()
+        _chk(self.L.fh_generic_assembler_create_from_mesh(mesh.h, FE[fe] if isinstance(fe, str) else int(fe), GAUSS_ORDER[order], K.h if K is not None else None,
+                                                          ctypes.byref(self.h)))
+        codes = (ctypes.c_int * 3)()
+        _chk(self.L.fh_generic_assembler_shapes(self.h, codes))
+        self.shapes = [str(ElementMesh._NAMES[c]) for c in codes if c >= 0]      # in the order of their first elements, as info() reports them
+        return self
+
+    def plan(self):
+        """(adj_ptr[ndof + 1], adj[nadj], pos[nent]), int32 (fh_generic_assembler_get_plan): the element-row ids of every dof in ascending element order and the
+        CSR position of every entry of every element row -- the same integers whichever way the plan was made"""
+        ndof, nadj, nent = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+        _chk(self.L.fh_generic_assembler_plan_sizes(self.h, ctypes.byref(ndof), ctypes.byref(nadj), ctypes.byref(nent)))
+        adj_ptr, adj, pos = np.empty(ndof.value + 1, np.int32), np.empty(nadj.value, np.int32), np.empty(nent.value, np.int32)
+        _chk(self.L.fh_generic_assembler_get_plan(self.h, _p(adj_ptr), _p(adj) if adj.size else None, _p(pos) if pos.size else None))
+        return adj_ptr, adj, pos
 
     def set_coords(self, coords):
         """other coordinates for the same nodes (the rest of the plan does not depend on them)"""

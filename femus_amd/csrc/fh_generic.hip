@@ -14,6 +14,8 @@
 //   Kb / Pos    element row (slot, i) of shape k starts at kb_base[k] + (slot nc_k + i) nc_k: its nc_k values, and beside them the CSR position of every
 //               one, found at create by a binary search of the (sorted) row on the device; a pair the pattern does not hold fails create
 //   Fb / adj    the element row's residual entry at row_base[k] + slot nc_k + i = the row's id; adj lists the ids of a dof in ascending ELEMENT order
+// The plan has two builders: fh_generic_assembler_create here, from host arrays, and fh_generic_assembler_create_from_mesh (fh_elemplan.hip), from a resident
+// element mesh; the object and the steps they share (gen_shape_tables, gp_plan_host, gp_plan_work) are declared in fh_generic.h.
 //
 // Element pass of the plan, one launch per shape (uniform waves on mixed meshes): workgroups of 256 threads, L = 64 / 32 / 16 lanes per element (1 / 2 / 4
 // elements per wave) from the shape's nc (nc + 1) / 2 pairs; dynamic LDS sized by the shape's nc and Gauss chunk, w / phi / dphi staged once per workgroup where
@@ -24,17 +26,13 @@
 // Row pass of the plan: lpr lanes per row (a group never leaves its wave), the row's sums in LDS: element rows in ascending element order, the lanes of the group
 // split one element row's entries (distinct positions), LDS operations of one wave complete in order -- so every entry sees its additions in ascending element
 // order, starting from 0.0 as the one-shot row thread does.  No search, no atomics, no read-modify-write of global memory.
-#include "fh_internal.h"
+#include "fh_generic.h"
 #include "fh_fe.h"
 #include "fh_expr_device.h"
 #include <algorithm>
 #include <climits>
 
 namespace {
-constexpr int GP_THREADS = 256;
-constexpr size_t GP_LDS_BUDGET = 64 * 1024;   // per workgroup: two workgroups and more per CU (160 KB of LDS), and no opt-in to large dynamic LDS needed
-constexpr size_t GP_PROG_BYTES = 4096;        // first size of the source program's buffer
-constexpr int GEN_NC = 27;                    // most nodes of an element (HEX27); the node stride of the one-shot kernel
 constexpr int GEN_GC = 32;                    // Gauss points per chunk of the one-shot kernel
 
 // doubles of LDS one element needs at node stride ns and chunk gc: X[ns][3], U[ns], JI[gc][9], WG[gc], FS[gc], GU[gc][3], G[gc][ns][3]
@@ -243,12 +241,6 @@ __global__ __launch_bounds__(256) void k_gen_positions(long long nent, int nc, c
   if (at < 0) atomicMin(miss, tag | (unsigned long long)idx);
 }
 
-struct GenRowShapes {
-  int row_base[3];        // first element-row id of the shape (INT_MAX: no such shape)
-  int nc[3];
-  long long kb_base[3];   // where its element rows start in Kb / Pos
-};
-
 // Row pass: lpr lanes (a power of two <= 64) per row, the row's sums in LDS (maxrow doubles per group).
 __global__ __launch_bounds__(GP_THREADS) void k_gen_rows(int ndof, int lpr, int maxrow, GenRowShapes sh, const int* __restrict__ adj_ptr, const int* __restrict__ adj,
                                                          const double* __restrict__ Kb, const int* __restrict__ Pos, const double* __restrict__ Fb,
@@ -277,15 +269,18 @@ __global__ __launch_bounds__(GP_THREADS) void k_gen_rows(int ndof, int lpr, int 
   if (t == 0) res[r] = racc;
 }
 
-// What both drivers make of a mesh before anything touches the device: the shapes in the order of their first element, the tables and checks of each, and how
-// many element rows every dof has.  Filled by gen_mesh, whose refusals begin with the entry point that was called (`who`).
-struct GenMesh {
-  int ns = 0, dim = 0, ncmax = 0;
-  int shapes[3] = {0, 0, 0}, nc[3] = {0, 0, 0}, nslot[3] = {0, 0, 0};     // nslot: elements of the shape
-  std::vector<unsigned char> eshape;                                      // [nel] the element's index into shapes
-  std::vector<double> w[3], phi[3], dphi[3];
-  std::vector<int> adj_ptr;                                               // [ndof + 1] the element rows of dof d are adj_ptr[d] .. adj_ptr[d + 1]
-};
+int gen_shape_tables(const char* who, int fe, int order, int nloc, GenMesh& m) {
+  FH_REQUIRE(order >= 0 && order <= 4, "%s: unsupported Gauss rule", who);       // fhfe::shape_tables sizes its arrays by the rule before it checks it
+  m.dim = fhfe::dim_of(m.shapes[0]);
+  for (int k = 0; k < m.ns; k++) {
+    FH_REQUIRE(fhfe::dim_of(m.shapes[k]) == m.dim, "%s: the shapes of one mesh have one dimension (shapes %d and %d)", who, m.shapes[0], m.shapes[k]);
+    m.nc[k] = fhfe::ndofs_of(m.shapes[k], fe);
+    FH_REQUIRE(m.nc[k] >= 1 && m.nc[k] <= GEN_NC && nloc >= m.nc[k], "%s: %d nodes per element given, the family has %d", who, nloc, m.nc[k]);
+    FH_REQUIRE(fhfe::shape_tables(m.shapes[k], fe, order, m.w[k], m.phi[k], m.dphi[k]) == 0, "%s: unsupported Gauss rule", who);
+    m.ncmax = std::max(m.ncmax, m.nc[k]);
+  }
+  return 0;
+}
 
 // elem_geom[nel] names the shape of every element (nullptr: every element is `geom`); the dofs of an element are the first nc of its nloc
 static int gen_mesh(const char* who, int fe, int order, int nel, int nloc, const int* elem_geom, int geom, const int* elem_dof, int nnode, int ndof, GenMesh& m) {
@@ -305,14 +300,7 @@ static int gen_mesh(const char* who, int fe, int order, int nel, int nloc, const
     FH_REQUIRE(geom >= 0 && geom <= 5, "%s: geom must be 0 (hex), 1 (quad), 2 (line), 3 (triangle), 4 (tetrahedron) or 5 (prism)", who);
     m.shapes[m.ns++] = geom;
   }
-  m.dim = fhfe::dim_of(m.shapes[0]);
-  for (int k = 0; k < m.ns; k++) {
-    FH_REQUIRE(fhfe::dim_of(m.shapes[k]) == m.dim, "%s: the shapes of one mesh have one dimension (shapes %d and %d)", who, m.shapes[0], m.shapes[k]);
-    m.nc[k] = fhfe::ndofs_of(m.shapes[k], fe);
-    FH_REQUIRE(m.nc[k] >= 1 && m.nc[k] <= GEN_NC && nloc >= m.nc[k], "%s: %d nodes per element given, the family has %d", who, nloc, m.nc[k]);
-    FH_REQUIRE(fhfe::shape_tables(m.shapes[k], fe, order, m.w[k], m.phi[k], m.dphi[k]) == 0, "%s: unsupported Gauss rule", who);
-    m.ncmax = std::max(m.ncmax, m.nc[k]);
-  }
+  FH_TRY(gen_shape_tables(who, fe, order, nloc, m));
   m.adj_ptr.assign((size_t)ndof + 1, 0);
   for (int e = 0; e < nel; e++) {
     const int k = m.eshape[e];
@@ -327,37 +315,7 @@ static int gen_mesh(const char* who, int fe, int order, int nel, int nloc, const
   return 0;
 }
 
-struct fh_generic_assembler_s {
-  fh_ctx_t ctx = nullptr;
-  uint64_t mat_uid = 0;          // the matrix of create: its uid and non-zero count, never its address
-  int mat_nnz = 0;
-  int ndof = 0, nnode = 0, dim = 0, ns = 0, nel = 0;
-  int nc[3] = {0, 0, 0}, ng[3] = {0, 0, 0}, lanes[3] = {0, 0, 0}, gcm[3] = {0, 0, 0}, nslot[3] = {0, 0, 0};
-  bool tl[3] = {false, false, false};
-  size_t lds[3] = {0, 0, 0};
-  GenRowShapes rows;
-  int* d_ed[3] = {nullptr, nullptr, nullptr};
-  double *d_w[3] = {nullptr, nullptr, nullptr}, *d_phi[3] = {nullptr, nullptr, nullptr}, *d_dphi[3] = {nullptr, nullptr, nullptr};
-  double* d_coords = nullptr;
-  int *d_adj_ptr = nullptr, *d_adj = nullptr, *d_Pos = nullptr;
-  double *d_Kb = nullptr, *d_Fb = nullptr;
-  unsigned long long* d_miss = nullptr;
-  int lpr = 1, maxrow = 1;
-  size_t row_lds = 0;
-  // the source program: consts (doubles) then code (ints) in one buffer, staged through pinned memory; uploaded only when it differs from the last one
-  char* d_prog = nullptr;
-  char* h_prog = nullptr;
-  size_t prog_cap = 0;
-  hipEvent_t prog_ev = nullptr;
-  bool prog_copied = false;
-  std::vector<int> code;
-  std::vector<double> consts;
-  bool have_prog = false;
-  int64_t device_bytes = 0, algorithmic_bytes = 0, device_allocations = 0;
-  std::vector<void*> dv;         // every device allocation but d_prog
-};
-
-static void* gp_alloc(fh_generic_assembler_t as, size_t bytes) {
+void* gp_alloc(fh_generic_assembler_t as, size_t bytes) {
   void* d = nullptr;
   bytes = std::max<size_t>(bytes, 8);
   if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
@@ -367,7 +325,7 @@ static void* gp_alloc(fh_generic_assembler_t as, size_t bytes) {
   return d;
 }
 
-static void gp_free(fh_generic_assembler_t as) {
+void gp_free(fh_generic_assembler_t as) {
   if (!as) return;
   if (as->ctx) hipStreamSynchronize(as->ctx->stream);     // no copy or kernel of this object in flight
   for (void* q : as->dv) hipFree(q);
@@ -392,17 +350,8 @@ static void gp_launch_pairs(fh_generic_assembler_t as, int k, const double* sol,
   }
 }
 
-extern "C" int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int order, int nel, int nloc, const int* elem_geom, int geom, const int* elem_dof, int nnode,
-                                           const double* coords, fh_mat_t KK, fh_generic_assembler_t* out) {
-  FH_GUARD_BEGIN
-  FH_REQUIRE(ctx && elem_dof && coords && KK && out && nel >= 1 && nnode >= 1 && nloc >= 1, "fh_generic_assembler_create: null or empty argument");
-  FH_REQUIRE(fe == fhfe::FE_LINEAR || fe == fhfe::FE_SERENDIPITY || fe == fhfe::FE_BIQUADRATIC, "fh_generic_assembler_create: fe must be 0, 1 or 2");
-  *out = nullptr;
-  // ---- every check first: nothing is allocated on the device before the last of them ----
+int gp_plan_host(const char* who, fh_ctx_t ctx, const GenMesh& m, int nel, int nnode, fh_mat_t KK, fh_generic_assembler_t* out) {
   const int ndof = KK->m;
-  FH_REQUIRE(KK->n == ndof && (int)KK->h_rowptr.size() == ndof + 1, "fh_generic_assembler_create: the matrix is not square with a host row table");
-  GenMesh m;
-  FH_TRY(gen_mesh("fh_generic_assembler_create", fe, order, nel, nloc, elem_geom, geom, elem_dof, nnode, ndof, m));
   const int ns = m.ns, dim = m.dim, ncmax = m.ncmax;
   const int *ncs = m.nc, *nslot = m.nslot;
   int64_t nrows = 0, nent = 0;
@@ -410,12 +359,12 @@ extern "C" int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int order, int 
     nrows += (int64_t)nslot[k] * ncs[k];
     nent += (int64_t)nslot[k] * ncs[k] * ncs[k];
   }
-  FH_REQUIRE(nrows < 2147483647ll && nent < (1ll << 40), "fh_generic_assembler_create: too many elements");
+  FH_REQUIRE(nrows < 2147483647ll && nent < (1ll << 40), "%s: too many elements", who);
   int maxrow = 1;
   for (int r = 0; r < ndof; r++) maxrow = std::max(maxrow, KK->h_rowptr[r + 1] - KK->h_rowptr[r]);
   int lpr = ncmax <= 6 ? 4 : ncmax <= 10 ? 8 : 16;
   while (lpr < 64 && (size_t)(GP_THREADS / lpr) * maxrow * sizeof(double) > GP_LDS_BUDGET) lpr *= 2;
-  FH_REQUIRE((size_t)(GP_THREADS / lpr) * maxrow * sizeof(double) <= GP_LDS_BUDGET, "fh_generic_assembler_create: a row of %d entries is longer than the row pass holds (%d)",
+  FH_REQUIRE((size_t)(GP_THREADS / lpr) * maxrow * sizeof(double) <= GP_LDS_BUDGET, "%s: a row of %d entries is longer than the row pass holds (%d)", who,
              maxrow, (int)(GP_LDS_BUDGET / sizeof(double) / (GP_THREADS / 64)));
 
   // ---- host side of the plan ----
@@ -435,6 +384,7 @@ extern "C" int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int order, int 
     int rb = 0;
     long long kb = 0;
     for (int k = 0; k < ns; k++) {
+      as->shapes[k] = m.shapes[k];
       as->nc[k] = ncs[k], as->ng[k] = (int)m.w[k].size(), as->nslot[k] = nslot[k];
       as->rows.row_base[k] = rb, as->rows.nc[k] = ncs[k], as->rows.kb_base[k] = kb;
       rb += nslot[k] * ncs[k];
@@ -450,11 +400,91 @@ extern "C" int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int order, int 
       as->lds[k] = base + (as->tl[k] ? tab : 0);
       if (as->lds[k] > GP_LDS_BUDGET) {
         delete as;
-        fh_set_error("fh_generic_assembler_create: shape %d does not fit the LDS of a workgroup", m.shapes[k]);
+        fh_set_error("%s: shape %d does not fit the LDS of a workgroup", who, m.shapes[k]);
         return 2;
       }
     }
   }
+  as->nrows = nrows, as->nent = nent;
+  // what one assembly cannot avoid moving: element tables, coordinates and state in; values and residual out
+  as->algorithmic_bytes = nrows * 4 + (int64_t)nnode * dim * 8 + (int64_t)ndof * 8 + (int64_t)KK->nnz * 8 + (int64_t)ndof * 8;
+  *out = as;
+  return 0;
+}
+
+int gp_plan_work(const char* who, fh_generic_assembler_t as, const GenMesh& m, fh_mat_t KK, unsigned long long* miss) {
+  hipStream_t st = as->ctx->stream;
+  const int64_t nent = as->nent, nrows = as->nrows;
+  bool bad = false;
+  auto up = [&](const void* h, size_t bytes) -> void* {
+    void* d = bad ? nullptr : gp_alloc(as, bytes);
+    if (!d) {
+      bad = true;
+      return nullptr;
+    }
+    if (h && bytes && hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st) != hipSuccess) bad = true;
+    return d;
+  };
+  for (int k = 0; k < as->ns; k++) {
+    as->d_w[k] = (double*)up(m.w[k].data(), m.w[k].size() * sizeof(double));
+    as->d_phi[k] = (double*)up(m.phi[k].data(), m.phi[k].size() * sizeof(double));
+    as->d_dphi[k] = (double*)up(m.dphi[k].data(), m.dphi[k].size() * sizeof(double));
+  }
+  as->d_Kb = (double*)up(nullptr, (size_t)nent * sizeof(double));
+  as->d_Fb = (double*)up(nullptr, (size_t)nrows * sizeof(double));
+  as->d_Pos = (int*)up(nullptr, (size_t)nent * sizeof(int));
+  as->d_miss = (unsigned long long*)up(nullptr, sizeof(unsigned long long));
+  if (!bad) {
+    if (hipMalloc((void**)&as->d_prog, GP_PROG_BYTES) == hipSuccess) {
+      as->prog_cap = GP_PROG_BYTES;
+      as->device_bytes += (int64_t)GP_PROG_BYTES;
+      as->device_allocations++;
+    } else {
+      bad = true;
+    }
+  }
+  if (!bad && (hipHostMalloc((void**)&as->h_prog, GP_PROG_BYTES) != hipSuccess || hipEventCreateWithFlags(&as->prog_ev, hipEventDisableTiming) != hipSuccess)) bad = true;
+  if (bad) {
+    hipGetLastError();
+    gp_free(as);
+    fh_set_error("%s: out of device memory (%.2f GB of element rows and positions)", who, (double)nent * 12 / 1e9);
+    return 2;
+  }
+  if (as->ctx->debug_poison) {   // tests: the row pass must read nothing the element pass has not written
+    hipMemsetAsync(as->d_Kb, 0xFF, (size_t)nent * sizeof(double), st);
+    hipMemsetAsync(as->d_Fb, 0xFF, (size_t)nrows * sizeof(double), st);
+  }
+  hipMemsetAsync(as->d_miss, 0xFF, sizeof(unsigned long long), st);
+  for (int k = 0; k < as->ns; k++) {
+    const long long ne = (long long)as->nslot[k] * as->nc[k] * as->nc[k];
+    hipLaunchKernelGGL(k_gen_positions, dim3(fh_div_up(ne, 256)), dim3(256), 0, st, ne, as->nc[k], as->d_ed[k], KK->d_rowptr, KK->d_col, as->d_Pos + as->rows.kb_base[k],
+                       as->d_miss, (unsigned long long)k << 56);
+  }
+  *miss = 0;
+  if (hipMemcpyAsync(miss, as->d_miss, sizeof(*miss), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
+    gp_free(as);
+    fh_set_error("%s: the position kernel failed", who);
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int order, int nel, int nloc, const int* elem_geom, int geom, const int* elem_dof, int nnode,
+                                           const double* coords, fh_mat_t KK, fh_generic_assembler_t* out) {
+  FH_GUARD_BEGIN
+  const char* who = "fh_generic_assembler_create";
+  FH_REQUIRE(ctx && elem_dof && coords && KK && out && nel >= 1 && nnode >= 1 && nloc >= 1, "fh_generic_assembler_create: null or empty argument");
+  FH_REQUIRE(fe == fhfe::FE_LINEAR || fe == fhfe::FE_SERENDIPITY || fe == fhfe::FE_BIQUADRATIC, "fh_generic_assembler_create: fe must be 0, 1 or 2");
+  *out = nullptr;
+  // ---- every check first: nothing is allocated on the device before the last of them ----
+  const int ndof = KK->m;
+  FH_REQUIRE(KK->n == ndof && (int)KK->h_rowptr.size() == ndof + 1, "fh_generic_assembler_create: the matrix is not square with a host row table");
+  GenMesh m;
+  FH_TRY(gen_mesh(who, fe, order, nel, nloc, elem_geom, geom, elem_dof, nnode, ndof, m));
+  const int ns = m.ns, dim = m.dim;
+  const int *ncs = m.nc, *nslot = m.nslot;
+  fh_generic_assembler_t as = nullptr;
+  FH_TRY(gp_plan_host(who, ctx, m, nel, nnode, KK, &as));
   // slot of every element inside its shape, the compact dof tables, the adjacency (ids of element rows, ascending element order per dof)
   std::vector<int> ed[3], slot_elem[3];
   for (int k = 0; k < ns; k++) {
@@ -487,48 +517,17 @@ extern "C" int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int order, int 
   as->d_adj_ptr = (int*)up(m.adj_ptr.data(), m.adj_ptr.size() * sizeof(int));
   as->d_adj = (int*)up(adj.data(), adj.size() * sizeof(int));
   as->d_coords = (double*)up(coords, (size_t)nnode * dim * sizeof(double));
-  for (int k = 0; k < ns; k++) {
-    as->d_ed[k] = (int*)up(ed[k].data(), ed[k].size() * sizeof(int));
-    as->d_w[k] = (double*)up(m.w[k].data(), m.w[k].size() * sizeof(double));
-    as->d_phi[k] = (double*)up(m.phi[k].data(), m.phi[k].size() * sizeof(double));
-    as->d_dphi[k] = (double*)up(m.dphi[k].data(), m.dphi[k].size() * sizeof(double));
-  }
-  as->d_Kb = (double*)up(nullptr, (size_t)nent * sizeof(double));
-  as->d_Fb = (double*)up(nullptr, (size_t)nrows * sizeof(double));
-  as->d_Pos = (int*)up(nullptr, (size_t)nent * sizeof(int));
-  as->d_miss = (unsigned long long*)up(nullptr, sizeof(unsigned long long));
-  if (!bad) {
-    if (hipMalloc((void**)&as->d_prog, GP_PROG_BYTES) == hipSuccess) {
-      as->prog_cap = GP_PROG_BYTES;
-      as->device_bytes += (int64_t)GP_PROG_BYTES;
-      as->device_allocations++;
-    } else {
-      bad = true;
-    }
-  }
-  if (!bad && (hipHostMalloc((void**)&as->h_prog, GP_PROG_BYTES) != hipSuccess || hipEventCreateWithFlags(&as->prog_ev, hipEventDisableTiming) != hipSuccess)) bad = true;
+  for (int k = 0; k < ns; k++) as->d_ed[k] = (int*)up(ed[k].data(), ed[k].size() * sizeof(int));
+  as->nadj = (int64_t)adj.size();
   if (bad) {
+    const int64_t nent = as->nent;
     hipGetLastError();
     gp_free(as);
     fh_set_error("fh_generic_assembler_create: out of device memory (%.2f GB of element rows and positions)", (double)nent * 12 / 1e9);
     return 2;
   }
-  if (ctx->debug_poison) {   // tests: the row pass must read nothing the element pass has not written
-    hipMemsetAsync(as->d_Kb, 0xFF, (size_t)nent * sizeof(double), st);
-    hipMemsetAsync(as->d_Fb, 0xFF, (size_t)nrows * sizeof(double), st);
-  }
-  hipMemsetAsync(as->d_miss, 0xFF, sizeof(unsigned long long), st);
-  for (int k = 0; k < ns; k++) {
-    const long long ne = (long long)nslot[k] * ncs[k] * ncs[k];
-    hipLaunchKernelGGL(k_gen_positions, dim3(fh_div_up(ne, 256)), dim3(256), 0, st, ne, ncs[k], as->d_ed[k], KK->d_rowptr, KK->d_col, as->d_Pos + as->rows.kb_base[k],
-                       as->d_miss, (unsigned long long)k << 56);
-  }
   unsigned long long miss = 0;
-  if (hipMemcpyAsync(&miss, as->d_miss, sizeof(miss), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
-    gp_free(as);
-    fh_set_error("fh_generic_assembler_create: the position kernel failed");
-    return 1;
-  }
+  FH_TRY(gp_plan_work(who, as, m, KK, &miss));
   if (miss != ~0ull) {
     const int k = (int)(miss >> 56);
     const long long idx = (long long)(miss & ((1ull << 56) - 1));
@@ -539,11 +538,33 @@ extern "C" int fh_generic_assembler_create(fh_ctx_t ctx, int fe, int order, int 
     fh_set_error("fh_generic_assembler_create: element %d: the pair (%d, %d) = dofs (%d, %d) is not in the pattern of the matrix", e, i, j, ed[k][s * nc + i], ed[k][s * nc + j]);
     return 2;
   }
-  // what one assembly cannot avoid moving: element tables, coordinates and state in; values and residual out
-  as->algorithmic_bytes = nrows * 4 + (int64_t)nnode * dim * 8 + (int64_t)ndof * 8 + (int64_t)KK->nnz * 8 + (int64_t)ndof * 8;
   *out = as;
   return 0;
   FH_GUARD_END("fh_generic_assembler_create")
+}
+
+extern "C" int fh_generic_assembler_shapes(fh_generic_assembler_t as, int shapes[3]) {
+  FH_REQUIRE(as && shapes, "fh_generic_assembler_shapes: null argument");
+  for (int k = 0; k < 3; k++) shapes[k] = k < as->ns ? as->shapes[k] : -1;
+  return 0;
+}
+
+extern "C" int fh_generic_assembler_plan_sizes(fh_generic_assembler_t as, int* ndof, int64_t* nadj, int64_t* nent) {
+  FH_REQUIRE(as, "fh_generic_assembler_plan_sizes: null argument");
+  if (ndof) *ndof = as->ndof;
+  if (nadj) *nadj = as->nadj;
+  if (nent) *nent = as->nent;
+  return 0;
+}
+
+extern "C" int fh_generic_assembler_get_plan(fh_generic_assembler_t as, int* adj_ptr, int* adj, int* pos) {
+  FH_REQUIRE(as, "fh_generic_assembler_get_plan: null argument");
+  hipStream_t st = as->ctx->stream;
+  if (adj_ptr) FH_CHECK_HIP(hipMemcpyAsync(adj_ptr, as->d_adj_ptr, ((size_t)as->ndof + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (adj && as->nadj) FH_CHECK_HIP(hipMemcpyAsync(adj, as->d_adj, (size_t)as->nadj * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (pos && as->nent) FH_CHECK_HIP(hipMemcpyAsync(pos, as->d_Pos, (size_t)as->nent * sizeof(int), hipMemcpyDeviceToHost, st));
+  FH_CHECK_HIP(hipStreamSynchronize(st));
+  return 0;
 }
 
 extern "C" int fh_generic_assembler_set_coords(fh_generic_assembler_t as, int nnode, const double* coords) {

@@ -221,6 +221,9 @@ struct fh_dof_lists {
   ~fh_dof_lists();
 };
 int fh_dof_lists_build(fh_ctx_t c, const char* who, size_t ne, int div, const int* d_ed, int m, int ncols, bool padded, fh_dof_lists* L);
+// the pattern builder behind fh_mat_create_from_elements (fh_mat.hip): elem_dof a host table [nel * nloc], or null when dev_elem_dof -- the same table already
+// in device memory, not owned -- is given (the host builder that serves a dof with more than 1024 candidate columns fetches it)
+int mat_create_from_elements_impl(fh_ctx_t c, int nel, int nloc, const int* elem_dof, const int* dev_elem_dof, int m, int n, fh_mat_t* out);
 static inline const std::vector<int>& fh_hcol(fh_mat_t A) {
   if (A->h_col.size() != (size_t)A->nnz) fh_mat_fetch_host_cols(A);
   return A->h_col;

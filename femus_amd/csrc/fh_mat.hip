@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256) void k_pe_rows(int m, const int* __restrict__ 
 }
 
 // elem_dof: host array [nel * nloc], or null when dev_elem_dof -- the same array already in device memory (not owned) -- is given
-static int mat_create_from_elements_impl(fh_ctx_t c, int nel, int nloc, const int* elem_dof, const int* dev_elem_dof, int m, int n, fh_mat_t* out) {
+int mat_create_from_elements_impl(fh_ctx_t c, int nel, int nloc, const int* elem_dof, const int* dev_elem_dof, int m, int n, fh_mat_t* out) {
   FH_GUARD_BEGIN
   FH_REQUIRE(c && out && nel >= 0 && nloc > 0 && m >= 0 && n >= m && (elem_dof || dev_elem_dof || nel == 0), "fh_mat_create_from_elements: bad arguments");
   const size_t ne = (size_t)nel * nloc;

@@ -17,6 +17,8 @@ tetrahedra and prisms in one file; the two-dimensional files of quadrilaterals a
     flag_elements   MeshRefinement::FlagElementsToRefine type 1: a function of the mean of an element's vertices and the level, elements of the level only
     amr_constraints  Mesh::GetAMRRestrictionAndAMRSolidMark (Mesh.cpp:1354-1830) for every shape, in the library on the host (fh_elem_amr_constraints_host): the hanging
                   dofs of a flagged level and their masters' weights
+    boundary_faces / boundary_owners  the walk of GenerateBdc (MultiLevelSolution.cpp:762-800) as arrays: the faces of some flags in (element, face) order with the
+                  family's nodes on them, and for every dof on them the flag of the last face that holds it -- the host statement of capi.ElementMesh's calls
     numbering     vertices, then edge middles, then the rest, each class in order of first appearance walking the elements
 """
 import numpy as np
@@ -429,6 +431,54 @@ def flag_elements(kind, ed, xs, lev, level, fn):
             x[d] = x[d] / float(nv)
         out[e] = 1 if fn(x, level) else 0
     return out
+
+
+_FACE_T = {}
+
+
+def _face_tables(fam):
+    """per shape code: loc[SHAPES, 6, 9] the family's local nodes on every face in the order of capi.fe_face_nodes, padded with -1, and n[SHAPES, 6] how many
+    (0: the shape has no such face)"""
+    if fam not in _FACE_T:
+        fe = ("linear", "serendipity", "biquadratic")[fam]
+        loc, n = np.full((len(SHAPES), 6, 9), -1, dtype=np.int64), np.zeros((len(SHAPES), 6), dtype=np.int64)
+        for i, s in enumerate(SHAPES):
+            for f in range(NFACES[s]):
+                nodes = capi.fe_face_nodes(s, fe, f)
+                loc[i, f, :nodes.size], n[i, f] = nodes, nodes.size
+        _FACE_T[fam] = (loc, n)
+    return _FACE_T[fam]
+
+
+def _fam(fam):
+    return capi.FE[fam] if isinstance(fam, str) else int(fam)
+
+
+def boundary_faces(level, fam, flags):
+    """the walk of GenerateBdc (MultiLevelSolution.cpp:762-800) over a level (kind, ed, xs, ff, ...): the faces whose flag is one of `flags`, elements in order
+    and faces in order inside an element.  (elem[n], face[n], nodes[n, 9], nn[n]): nodes = ed[elem, fe_face_nodes(shape, family, face)] padded with -1, nn how
+    many of them -- what the face loop of app_poisson.run_elements visits, in its order"""
+    kind, ed, ff = level[0], np.asarray(level[1]), np.asarray(level[3])
+    loc, n = _face_tables(_fam(fam))
+    code = _codes(kind)
+    hit = np.isin(ff, np.asarray(list(flags), dtype=np.int64)) & (np.arange(6)[None, :] < np.array([NFACES[s] for s in SHAPES])[code][:, None])
+    elem, face = np.nonzero(hit)                                  # row-major: ascending (element, face)
+    l = loc[code[elem], face]
+    nodes = np.where(l >= 0, ed[elem[:, None], np.maximum(l, 0)], -1)
+    return elem, face, nodes, n[code[elem], face]
+
+
+def boundary_owners(level, fam, flags):
+    """(dofs[n] ascending, owner_flag[n], coords[n, dim]): the dofs on the faces of boundary_faces, for each the flag of the LAST of those faces that holds it --
+    in GenerateBdc a later face overwrites an earlier one, the rule of the dictionary in run_elements' face loop -- and its coordinates"""
+    xs, ff = level[2], np.asarray(level[3])
+    elem, face, nodes, nn = boundary_faces(level, fam, flags)
+    k = np.broadcast_to(np.arange(elem.size)[:, None], nodes.shape)
+    on = np.arange(9)[None, :] < nn[:, None]
+    last = np.full(xs.shape[0], -1, dtype=np.int64)
+    np.maximum.at(last, nodes[on], k[on])                         # faces are listed in ascending order: the last one is the largest index
+    dofs = np.nonzero(last >= 0)[0]
+    return dofs, ff[elem[last[dofs]], face[last[dofs]]], xs[dofs]
 
 
 def amr_constraints(kind, ed, xs, ff, lev, fe, mode="reference"):

@@ -322,6 +322,22 @@ int fh_elem_mesh_destroy(fh_elem_mesh_t mesh);
 int fh_elem_mesh_prolongator(fh_elem_mesh_t coarse, fh_elem_mesh_t fine, int fe, fh_mat_t* P);
 int fh_elem_mesh_boundary_dofs(fh_elem_mesh_t mesh, int fe, int nflags, const int* flags, int* ndofs, int* dofs /* NULL on the first call */);
 
+/* ---- pattern and boundary data of resident element meshes (fh_elemplan.hip) ----
+ * What stands between a resident level and its first assembly, made where the mesh lives; the plan of the assembly itself is
+ * fh_generic_assembler_create_from_mesh, further down.  fe: 0 linear, 1 serendipity, 2 biquadratic.  Nothing here depends on the order the threads run in.
+ * matrix: the square pattern over the own[fe] dofs of the family that holds every (i, j) of every element (LinearEquation::GetSparsityPatternSize +
+ * SparseMatrix::init, LinearEquation.cpp:407-548), values zero: a kernel writes the table of every element's first nc(shape, fe) dofs, padded to the widest
+ * shape of the mesh with the element's first dof, and the builder of fh_mat_create_from_elements takes it where it is -- the rows and columns that call gives
+ * for the downloaded table.  A dof with more than 1024 candidate columns is served by that builder's host path, which fetches the table.
+ * boundary_faces: the faces whose flag is one of flags[nflags], in ascending (element, face) order -- the walk of GenerateBdc (MultiLevelSolution.cpp:762-800):
+ * elem[k], face[k], nn[k] = the number of nodes the family has on the face, nodes[9 k ..] = ed[elem][fh_fe_face_nodes(shape, fe, face)] in that order, padded
+ * with -1.  Two-call protocol: with the four arrays NULL the number comes back in *nfaces; the second call takes it there and fills the arrays.
+ * boundary_owners: dofs[] = the list of boundary_dofs; owner_flag[k] = the flag of the LAST listed (element, face) that holds dofs[k] -- in GenerateBdc a later
+ * face overwrites an earlier one --; coords[dim k ..] = the dof's coordinates.  Two-call protocol with *ndofs as above. */
+int fh_elem_mesh_matrix(fh_elem_mesh_t mesh, int fe, fh_mat_t* K);
+int fh_elem_mesh_boundary_faces(fh_elem_mesh_t mesh, int fe, int nflags, const int* flags, int* nfaces, int* elem, int* face, int* nodes /* [9 nfaces] */, int* nn);
+int fh_elem_mesh_boundary_owners(fh_elem_mesh_t mesh, int fe, int nflags, const int* flags, int* ndofs, int* dofs, int* owner_flag, double* coords /* [dim ndofs] */);
+
 /* ---- hanging-node constraints of element meshes of any shape (fh_elemconstraints.cpp, fh_elemconstraints.hip) ----
  * Mesh::GetAMRRestrictionAndAMRSolidMark (Mesh.cpp:1354-1830) for every shape: what fh_mesh_amr_constraints is to fh_mesh_t.  A face is an interface face when
  * its flag is -1 and no other element holds all of its vertices; an element with one is an interface element of its level, and the nodes of those faces that
@@ -531,6 +547,17 @@ int fh_generic_assembler_set_coords(fh_generic_assembler_t as, int nnode, const 
 int fh_generic_assembler_assemble(fh_generic_assembler_t as, fh_vec_t sol, fh_expr_t source, double scale, fh_mat_t KK, fh_vec_t RES);
 int fh_generic_assembler_info(fh_generic_assembler_t as, int elems_per_workgroup[3], int64_t* device_bytes, int64_t* algorithmic_bytes, int64_t* device_allocations);
 int fh_generic_assembler_destroy(fh_generic_assembler_t as);
+/* The same object from a RESIDENT element mesh (fh_elemplan.hip): nothing of the mesh visits the host.  The k-th shape is the k-th to appear walking the
+ * elements, an element's slot its rank among the elements of its shape, the rows of a dof ascend by ELEMENT as in the element loop of main.cpp:355-480 (where
+ * shapes interleave that is not the order of the row ids), the coordinates are a copy: the object outlives the mesh.  KK must be square of the own[fe] dofs of
+ * the family and live on the mesh's context.  Every refusal but the missing pair comes before the first allocation: fe outside 0 .. 2, the matrix's size or
+ * context, more than three shapes or shapes of two dimensions, an unsupported Gauss rule, a shape or a row that does not fit the LDS.
+ * plan_sizes / get_plan read a plan made either way: adj_ptr[ndof + 1], adj[nadj] (the element-row ids of every dof) and pos[nent] (the CSR position of every
+ * entry of every element row, shape after shape); a NULL array is skipped.  shapes: the geom ids in the order info counts them (-1 beyond the last). */
+int fh_generic_assembler_shapes(fh_generic_assembler_t as, int shapes[3]);
+int fh_generic_assembler_create_from_mesh(fh_elem_mesh_t mesh, int fe, int gauss_order, fh_mat_t KK, fh_generic_assembler_t* out);
+int fh_generic_assembler_plan_sizes(fh_generic_assembler_t as, int* ndof, int64_t* nadj, int64_t* nent);
+int fh_generic_assembler_get_plan(fh_generic_assembler_t as, int* adj_ptr, int* adj, int* pos);
 /* Open-boundary pressure term of the steady Navier-Stokes residual (src/08_equations/assemble/03_navier_stokes.hpp:185-290): on every listed boundary
  * face  aResV[k][node_i] += phi_i * tau * normal[k] * weight  for the dim velocity components (Q2 face nodes), tau = the prescribed pressure -- one
  * number per face (tau) or expression face_expr[f] of the nexpr expressions evaluated at the face Gauss point, as the bdc callback is (:280) -- and
