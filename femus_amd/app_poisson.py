@@ -376,7 +376,113 @@ class Poisson001:
         out["levels"] = [lv[1:4] for lv in levels]
         return out
 
-    def _run_resident(self, K, gen, top_data, P, bdc, P_amr, hanging, elem_levels, selective_levels, log, smoother, omega):
+    def run_elements_adaptive(self, max_amr_levels, threshold, norm="H1", neighbor_threshold=0.0, amr_mode="reference", log=None, smoother=capi.SMOOTH_GS_COLOR,
+                              omega=1.0, keep_steps=False):
+        """MGsolve with _AMRtest (LinearImplicitSystem.cpp:309-404, 529-558; SetAMRSetOptions(AMR, AMRlevels = max_amr_levels, AMRnorm = norm, AMRthreshold =
+        threshold)): the nlevels uniform levels are built on the device and solved on the top one as run_elements(mesh_data="device") does; then, until the flags
+        say converged or max_amr_levels levels have been added: AMREps = what the solve added to the top level's solution (the final solution minus the start
+        vector, EPS <- P_amr EPS included); capi.ElementMesh.flag_by_error with the current threshold; refine("resident"); constraints, P_amr, transfer
+        (PP <- PP P_amr of the level below where that one is non-homogeneous), pattern, plan and boundary data of the new level from the resident meshes; the
+        solution prolonged with the transfer before its Dirichlet rows are zeroed, the boundary values imposed as run_elements does for its start vector; the
+        solve on the new top level, with the adjusted threshold for the next step.  The set-up of the lower levels is rebuilt at every step.  The resident levels
+        live until the method returns; none is downloaded but the final coordinates (keep_steps=True also brings down, for every step, "sol", "eps" and the
+        level's (kind, ed, xs, ff, lev, level): result["steps"], for tests).
+        The result is run_elements(mesh_data="device")'s of the last solve, with "amr_history" (per step: nflagged, nel, threshold_in, threshold_out, sums,
+        converged), "elem_levels" and "hanging" of the final level and "nlevels"."""
+        from . import mixed_mesh
+        ctx = self.ctx
+        max_amr_levels = int(max_amr_levels)
+        if max_amr_levels < 0:
+            raise ValueError("max_amr_levels must not be negative, not %d" % max_amr_levels)
+        if amr_mode not in ("reference", "coarsest"):
+            raise ValueError("amr_mode must be \"reference\" or \"coarsest\", not %r" % (amr_mode,))
+        norm_code = capi.amr_norm("run_elements_adaptive", norm)
+        fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
+        level0 = mixed_mesh.tri_box(self.box[0], self.box[1], self.lo[:2], self.hi[:2]) if self.box is not None else mixed_mesh.read_gambit(self.mesh_file)
+        all_flags = sorted({int(f) for f in np.unique(level0[3]) if f < -1})
+        dirichlet = [f for f in all_flags if self.face_bc(f)[0] == "dirichlet"]
+        other = sorted(set(all_flags) - set(dirichlet))
+        resident = [capi.ElementMesh.from_arrays(ctx, *level0)]
+        nlevels0, thr = self.nlevels, float(threshold)
+        amr_history, steps, prev, out = [], [], None, None
+        try:
+            for _ in range(1, nlevels0):
+                resident.append(resident[-1].refine())
+            while True:
+                nl, m = len(resident), resident[-1]
+                top = nl - 1
+                owned = []              # what this step made and has not handed to the solve yet
+                try:
+                    hanging, P_amr = [np.zeros(0, np.int32)] * nl, [None] * nl
+                    for l, lv in enumerate(resident):
+                        if not lv.homogeneous:
+                            hanging[l] = lv.amr_constraints(fam, amr_mode)[0]
+                            P_amr[l] = lv.amr_prolongator(fam, amr_mode)
+                            owned.append(P_amr[l])
+                    bdc, P = [], [None]
+                    for l, lv in enumerate(resident):
+                        bdc.append(lv.boundary_dofs(fam, dirichlet))
+                        if l:
+                            P.append(resident[l - 1].prolongator(lv, fam))
+                            owned.append(P[-1])
+                    start = None
+                    if prev is not None:                              # the solution of the level below, through PP P_amr before any row is zeroed
+                        v, w, s = ctx.vector_from(prev), ctx.vector(prev.size), ctx.vector(m.own[fam])
+                        try:
+                            if P_amr[top - 1] is not None:
+                                w.matrix_mult(v, P_amr[top - 1])
+                                v.assign(w)
+                            s.matrix_mult(v, P[top])
+                            start = s.to_numpy()
+                        finally:
+                            for q in (v, w, s):
+                                q.destroy()
+                    K = m.matrix(fam)
+                    owned.append(K)
+                    gen = capi.GenericAssembler.from_mesh(m, fam, K)
+                    owned.append(gen)
+                    top_data = (m.boundary_owners(fam, dirichlet), {f: m.boundary_faces(fam, [f]) for f in other}, m.coords(), list(m.own), m.dim)
+                    elem_levels = m.elem_levels()[0]
+                except BaseException:
+                    for q in owned:
+                        q.destroy()
+                    raise
+                keep = {}
+                self.nlevels = nl                                     # the helpers below count the levels of the hierarchy they are given by this
+                try:
+                    out = self._run_resident(K, gen, top_data, P, bdc, P_amr, hanging, elem_levels, nl - nlevels0, log, smoother, omega, start=start, keep=keep)
+                finally:
+                    self.nlevels = nlevels0
+                sol = out["solution"]
+                eps = sol - keep["start"]
+                SOLv, EPSv = ctx.vector_from(sol), ctx.vector_from(eps)
+                try:
+                    r = m.flag_by_error(fam, SOLv, EPSv, thr, norm_code, neighbor_threshold)
+                finally:
+                    SOLv.destroy()
+                    EPSv.destroy()
+                amr_history.append({"nflagged": r["nflagged"], "nel": m.nel, "threshold_in": thr, "threshold_out": r["threshold"], "sums": r["sums"],
+                                    "converged": r["converged"]})
+                if log:
+                    log("AMR step %d: %d of %d elements flagged, threshold %.6e -> %.6e%s" % (len(amr_history) - 1, r["nflagged"], m.nel, thr, r["threshold"],
+                                                                                           ", converged" if r["converged"] else ""))
+                if keep_steps:
+                    kind, ed, xs, ff, _ = m.arrays()
+                    steps.append({"sol": sol, "eps": eps, "flags": r["flags"], "mesh": (kind, ed, xs, ff, elem_levels, m.level)})
+                if r["converged"] or nl - nlevels0 >= max_amr_levels:
+                    break
+                resident.append(m.refine("resident"))
+                thr, prev = r["threshold"], sol
+            out["amr_history"], out["nlevels"] = amr_history, len(resident)
+            out["elem_levels"], out["hanging"] = elem_levels, hanging[-1]
+            if keep_steps:
+                out["steps"] = steps
+            return out
+        finally:
+            for lv in resident:
+                lv.destroy()
+
+    def _run_resident(self, K, gen, top_data, P, bdc, P_amr, hanging, elem_levels, selective_levels, log, smoother, omega, start=None, keep=None):
         """the rest of run_elements with mesh_data "device": K and gen were made from the resident top level; top_data = (boundary_owners of the Dirichlet flags,
         {flag: boundary_faces} of the others, the top level's coordinates, own, dim).  The face loop of the host path, stated on the lists: a Dirichlet dof takes
         the function of the last face that holds it; the flux faces go in (element, face) order"""
@@ -384,6 +490,9 @@ class Poisson001:
         fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
         ndof = own[fam]
         sol0 = np.zeros(ndof)
+        if start is not None:                                     # run_elements_adaptive: a prolonged solution; every Dirichlet dof takes its boundary value
+            sol0[:] = start
+            sol0[b_dofs] = 0.0
         for f in np.unique(b_flag):
             fn = self.face_bc(int(f))[1]
             if fn is not None:
@@ -407,11 +516,12 @@ class Poisson001:
                 tau_faces.append(nodes)
                 tau_vals.append(self.file_flux[f])
         return self._solve_elements(K, lambda: gen, xs, ndof, dim, sol0, list(bdc), P, P_amr, hanging, elem_levels, selective_levels,
-                                    (flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals), log, smoother, omega)
+                                    (flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals), log, smoother, omega, keep)
 
-    def _solve_elements(self, K, make_gen, xs, ndof, dim, sol0, bdc, P, P_amr, hanging, elem_levels, selective_levels, flux, log, smoother, omega):
+    def _solve_elements(self, K, make_gen, xs, ndof, dim, sol0, bdc, P, P_amr, hanging, elem_levels, selective_levels, flux, log, smoother, omega, keep=None):
         """run_elements from the start vector on: K the top level's matrix, make_gen() its GenericAssembler, xs the top level's coordinates on the host, bdc[l] and
-        P[l] of every level, flux = (flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals) of the top level.  Returns the result dictionary without "levels" """
+        P[l] of every level, flux = (flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals) of the top level.  Returns the result dictionary without "levels".
+        keep: a dict that receives "start", the vector the solve starts from (after it was made conforming)"""
         ctx, top = self.ctx, self.nlevels - 1
         flux_faces, flux_idx, flux_exprs, tau_faces, tau_vals = flux
         SOL, RES = ctx.vector(ndof), ctx.vector(ndof)
@@ -430,6 +540,8 @@ class Poisson001:
                 RES.matrix_mult(SOL, P_amr[top])
                 SOL.assign(RES)
 
+        if keep is not None:
+            keep["start"] = SOL.to_numpy()
         gen = make_gen()
 
         def assemble():

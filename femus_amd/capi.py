@@ -798,6 +798,28 @@ class ElementMesh:
                 e.destroy()
         return out
 
+    def flag_by_error(self, fe, sol, eps, threshold, norm="H1", neighbor_threshold=0.0, order="seventh"):
+        """Solution::FlagAMRRegionBasedOnErroNormAdaptive on the device (fh_elem_mesh_error_flag) for one variable of the family fe: sol and eps (the last
+        correction) are Vecs over own[fe] dofs, norm one of the spellings of SetAMRSetOptions ("L2" / "l2" / "H0" / "h0", "H1" / "h1").  Returns {"flags":
+        uint8[nel], "sums": [solNorm2, volume, volumeRefined, volumeTestFalse, errTestTrue2], "threshold": the adjusted one, "nflagged", "converged"}; the flags
+        also stay on the device for refine("resident")"""
+        k = FE[fe] if isinstance(fe, str) else int(fe)
+        flags, sums = np.empty(self.nel, np.uint8), np.zeros(5)
+        thr, n, conv = ctypes.c_double(0.0), ctypes.c_longlong(0), ctypes.c_int(0)
+        _chk(self.L.fh_elem_mesh_error_flag(self.h, k, _gauss_order("ElementMesh.flag_by_error", order), sol.h, eps.h, amr_norm("ElementMesh.flag_by_error", norm),
+                                            float(threshold), float(neighbor_threshold), _p(flags) if self.nel else None, _p(sums), ctypes.byref(thr),
+                                            ctypes.byref(n), ctypes.byref(conv)))
+        return {"flags": flags, "sums": sums, "threshold": thr.value, "nflagged": int(n.value), "converged": bool(conv.value)}
+
+    def error_indicators(self, fe, eps, norm="H1", order="seventh"):
+        """(err2[nel], vol[nel]) of flag_by_error alone (fh_elem_mesh_error_indicators): the scaled norm of eps over every refinable element and the element's
+        volume; zero for an element of an older level"""
+        k = FE[fe] if isinstance(fe, str) else int(fe)
+        err2, vol = np.zeros(self.nel), np.zeros(self.nel)
+        _chk(self.L.fh_elem_mesh_error_indicators(self.h, k, _gauss_order("ElementMesh.error_indicators", order), eps.h, amr_norm("ElementMesh.error_indicators", norm),
+                                                  _p(err2) if self.nel else None, _p(vol) if self.nel else None))
+        return err2, vol
+
     def set_levels(self, lev):
         """the level of every element of a mesh uploaded non-homogeneous (fh_elem_mesh_set_levels); the mesh's level becomes their maximum"""
         lev = _i32(lev)
@@ -912,6 +934,52 @@ class ElementMesh:
         if self.h:
             _chk(self.L.fh_elem_mesh_destroy(self.h))
             self.h = None
+
+
+_AMR_NORM = {"L2": 0, "l2": 0, "H0": 0, "h0": 0, "H1": 1, "h1": 1}
+_NDOFS = {"hex": (8, 20, 27), "tet": (4, 10, 15), "wedge": (6, 15, 21), "quad": (4, 8, 9), "tri": (3, 6, 7)}        # dofs per element of the three Lagrange families
+
+
+def amr_norm(who, norm):
+    """the norm of SetAMRSetOptions as the library's number: "L2" / "l2" / "H0" / "h0" -> 0, "H1" / "h1" -> 1; a number goes through (the library refuses others)"""
+    if isinstance(norm, str):
+        if norm not in _AMR_NORM:
+            raise FemusHipError("%s: norm must be one of %s, not %r" % (who, sorted(_AMR_NORM), norm))
+        return _AMR_NORM[norm]
+    return int(norm)
+
+
+def _gauss_order(who, order):
+    if isinstance(order, str):
+        if order not in GAUSS_ORDER:
+            raise FemusHipError("%s: unsupported Gauss rule %r" % (who, order))
+        return GAUSS_ORDER[order]
+    return int(order)
+
+
+def error_flag_host(kind, ed, xs, lev, level, fe, sol, eps, threshold, norm="H1", neighbor_threshold=0.0, order="seventh"):
+    """ElementMesh.flag_by_error on the arrays of mixed_mesh, in the library without a device (fh_elem_error_flag_host): the same element body, so the same
+    bits.  lev[nel] the elements' levels, level the mesh's.  Returns the dict of flag_by_error with "err2" and "vol" (per element, zero where not refinable)"""
+    who = "error_flag_host"
+    kind, xs = np.asarray(kind), _f64(xs)
+    code = np.zeros(kind.shape[0], dtype=np.int32)
+    for name, c in GEOM.items():
+        code[kind == name] = c
+    ed, lev, sol, eps = _i32(ed), _i32(lev), _f64(sol), _f64(eps)
+    nel = kind.shape[0]
+    if ed.shape != (nel, 27) or lev.shape != (nel,) or xs.ndim != 2:
+        raise FemusHipError("%s: ed must be [%d, 27], lev [%d] and xs [nnode, dim]" % (who, nel, nel))
+    k = FE[fe] if isinstance(fe, str) else int(fe)
+    if 0 <= k <= 2 and nel:
+        ndof = 1 + max(int(ed[kind == s][:, :_NDOFS[s][k]].max()) for s in set(kind.tolist()) if s in _NDOFS)
+        if sol.shape != (ndof,) or eps.shape != (ndof,):
+            raise FemusHipError("%s: vectors of %s and %s entries, the family has %d dofs on this mesh" % (who, sol.shape, eps.shape, ndof))
+    flags, err2, vol, sums = np.zeros(nel, np.uint8), np.zeros(nel), np.zeros(nel), np.zeros(5)
+    thr, n, conv = ctypes.c_double(0.0), ctypes.c_longlong(0), ctypes.c_int(0)
+    _chk(load_library().fh_elem_error_flag_host(int(xs.shape[1]), nel, _p(code), _p(ed), _p(lev), int(level), int(xs.shape[0]), _p(xs), k, _gauss_order(who, order),
+                                                _p(sol), _p(eps), amr_norm(who, norm), float(threshold), float(neighbor_threshold), _p(flags), _p(err2), _p(vol),
+                                                _p(sums), ctypes.byref(thr), ctypes.byref(n), ctypes.byref(conv)))
+    return {"flags": flags, "err2": err2, "vol": vol, "sums": sums, "threshold": thr.value, "nflagged": int(n.value), "converged": bool(conv.value)}
 
 
 def fe_elem_prolongator(geom, fe):

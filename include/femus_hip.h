@@ -298,6 +298,28 @@ struct fh_expr_s;
 int fh_elem_mesh_flag(fh_elem_mesh_t mesh, struct fh_expr_s* expr /* an fh_expr_t (run-time expressions, below) */, unsigned char* flags /* host [nel] or NULL */);
 int fh_elem_mesh_refine_flagged(fh_elem_mesh_t coarse, const unsigned char* flags /* host [nel], or NULL: the flags fh_elem_mesh_flag left on the device */,
                                 fh_elem_mesh_t* fine);
+/* Flags from the solution: Solution::FlagAMRRegionBasedOnErroNormAdaptive (Solution.cpp:843-1101) for one variable of family fe (0 linear, 1 serendipity,
+ * 2 biquadratic) whose vectors sol and eps (the last correction, _AMREps) run over the mesh's own[fe] dofs; norm 0 = L2, 1 = H1.  With w, phi, grad phi of the
+ * family's own Jacobian at every Gauss point and v(u) = (sum phi_i u_i)^2 [+ sum_j (sum_i u_i grad phi_ij)^2]: solNorm2 = sum v(sol) w and volume = sum w over
+ * all elements, volumeRefined over the refinable ones (level == the mesh's level); for a refinable element err_i = sum scale2[fe][norm] v(eps) w, vol_i = sum w;
+ * eps2 = threshold^2 solNorm2 / volume; flag_i = (err_i > eps2 vol_i) or (err_i > neighbor_threshold eps2 vol_i and a refinable element that shares a vertex
+ * with i has err_j > eps2 vol_j) -- what the reference's ascending walk with its 0 / 1 / 2 marks leaves, whatever the order.  volumeTestFalse = sum of vol_i
+ * over the flagged, errTestTrue2 = sum of err_i over the refinable unflagged; new_threshold = sqrt(threshold^2 volumeRefined / volumeTestFalse - errTestTrue2 /
+ * solNorm2 volume / volumeTestFalse), 1 when nothing is flagged; converged = (nflagged 2^dim <= 1).
+ *   fh_elem_mesh_error_flag        on the resident mesh; the flags stay on the device where fh_elem_mesh_refine_flagged(mesh, NULL, ...) finds them.  The five sums
+ *                                  have a fixed shape (no floating-point atomics): a repeated call gives the same bits.
+ *   fh_elem_mesh_error_indicators  err_i and vol_i alone (zero for an element that is not refinable)
+ *   fh_elem_error_flag_host        the same statement on plain arrays, no context and no device: the element body is one text compiled for both sides, so err_i,
+ *                                  vol_i, the sums and the flags are the device's bit for bit.  flags, err2, vol may be NULL.
+ * Refused before anything is allocated: fe outside 0 .. 2, norm outside 0 .. 1, an unsupported Gauss rule, vectors of another size than own[fe] or of another
+ * context, a negative or non-finite threshold.  No refinable element: no flags, converged. */
+int fh_elem_mesh_error_flag(fh_elem_mesh_t mesh, int fe, int gauss_order, fh_vec_t sol, fh_vec_t eps, int norm, double threshold, double neighbor_threshold,
+                            unsigned char* flags /* host [nel] or NULL */, double sums[5] /* solNorm2, volume, volumeRefined, volumeTestFalse, errTestTrue2 */,
+                            double* new_threshold, long long* nflagged, int* converged);
+int fh_elem_mesh_error_indicators(fh_elem_mesh_t mesh, int fe, int gauss_order, fh_vec_t eps, int norm, double* err2 /* host [nel] */, double* vol /* host [nel] */);
+int fh_elem_error_flag_host(int dim, int nel, const int* elem_geom, const int* elem_dof /* [nel*27] */, const int* lev, int level, int nnode, const double* coords, int fe, int gauss_order,
+                            const double* sol, const double* eps, int norm, double threshold, double neighbor_threshold,
+                            unsigned char* flags, double* err2, double* vol, double sums[5], double* new_threshold, long long* nflagged, int* converged);
 int fh_elem_mesh_elem_levels(fh_elem_mesh_t mesh, int* lev, int* father, int* child, int* homogeneous);
 int fh_elem_mesh_info(fh_elem_mesh_t mesh, int* dim, int* nel, int* nnode, int own[3], int* level);
 int fh_elem_mesh_get(fh_elem_mesh_t mesh, int* elem_geom /* [nel] */, int* elem_dof /* [nel*27] */, double* coords /* [nnode*dim] */, int* face_flag /* [nel*6] */);
