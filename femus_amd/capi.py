@@ -1277,6 +1277,12 @@ class Assembler:
         return {"active": bool(a.value), "clusters": n.value, "partial_entries": pe.value, "second_pass_rows": r.value,
                 "clusters_per_super": cs.value, "carried_entries": ce.value}
 
+    def plan_info(self):
+        """plan words of the fused cluster assembly: device memory they take (clusters * 512 * 16; 0 without a fused plan) and bytes per cluster"""
+        mb, pc = ctypes.c_int64(), ctypes.c_int()
+        _chk(self.L.fh_assembler_plan_info(self.h, ctypes.byref(mb), ctypes.byref(pc)))
+        return {"map_bytes": mb.value, "bytes_per_cluster": pc.value}
+
     def assemble_expr(self, A, res, sol, expr, scale=1.0):
         """source term f = scale * expr(x, y, z, t), evaluated on the device at the Gauss points"""
         _chk(self.L.fh_assemble_poisson_expr(self.h, None if sol is None else sol.h, expr.h, float(scale), A.h, res.h))

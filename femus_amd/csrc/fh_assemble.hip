@@ -73,7 +73,6 @@ struct fh_assembler_s {
   unsigned long long* d_cl_vdst64 = nullptr;           // ... as addresses, for the value array cl_val_base
   double* cl_val_base = nullptr;
   unsigned char *d_cl_map = nullptr, *d_cl_pmap = nullptr;
-  unsigned char* d_cl_mapb = nullptr;       // carried plans: destination positions of the slots (k_cluster_maps)
   unsigned short* d_cl_gtab = nullptr;      // [8][27 * 27] template entry that child j OWNS at (local row, local column), 0xffff = another child's (fh_assembler_galerkin from the macro rows)
   bool cl_all_rows = false;                 // every row of every cluster lies in the matrix (no ghost rows, no sink): the macro rows can be read back
   bool macro_valid = false;                 // the matrix cl_val_base and the partial-row buffer hold the macro rows of the last assembly
@@ -1900,8 +1899,9 @@ struct ClParams {
   const unsigned* sinfo;       // [CL_SPT][CL_T]: r | p << 7 | off[r] << 14 of slot tid + CL_T * i
   const unsigned long long* vdst;   // [ncl][128] address of the row's first entry (CSR array or partial-row buffer)
   const int* fdst;             // [ncl][128] >= 0: row of the residual vector (bit 30: carried row an earlier cluster stored to -- add), bit 31: offset into the partial-row buffer
-  const uint4* map;            // [ncl][CL_T]: byte i = template entry of slot tid + CL_T * i inside its row; bits 16 + i of word 2: carried entry to add to (k_cluster_maps)
-  const uint4* mapb;           // CARRY kernels: [ncl][CL_T] byte i = position of the slot in its destination row
+  const uint4* map;            // [ncl][CL_T] the plan word of the thread (k_cluster_maps): byte i = the one informative byte m of slot tid + CL_T * i -- the template entry
+                               //      inside its row (the slot goes to position p), or, where bit 10 + i of word 3 is set (carried row), the position in the destination row
+                               //      (the entry is p); bits 16 + i of word 2: carried entry to add to; bits i of word 3: a later cluster still adds (Galerkin product)
   double* Pbuf;
   double* res;
   const double* geo;           // GEO kernels: the assembler's geometry cache [nel][7][64] (k_geom_cache)
@@ -2066,12 +2066,13 @@ __global__ __launch_bounds__(CL_T) void k_cluster_q2hex_sf(AsmParams P, SfTab ta
     sf_stamp<INS>(st, 6);
     // this cluster's destinations and maps, and the thread's slot table (the same for every cluster: an L1 / L2 hit): issued only now, behind the stages
     // that need every register, and consumed after the workgroup barrier -- the staging, the residual and the wait at the barrier hide the round trip
+    // (measured and dropped: the slot table loaded once ahead of the loop and kept in registers in the GEO instantiation -- 228 registers, no scratch; the
+    // kernel 851 -> 838 us in a trace, the step not separable from run-to-run noise: profiles/plan_word_probe.json)
     const int tm = tid & (CL_NM_MAX - 1);
     const unsigned long long vd_cur = C.vdst[(size_t)cl * CL_NM_MAX + tm];
     const int fd_cur = C.fdst[(size_t)cl * CL_NM_MAX + tm];
     const uint4 mp_cur = C.map[(size_t)cl * CL_T + tid];
-    // CARRY: positions of the slots in their rows; residual destination of the row this lane sums in the output phase (wave * 16 + lane % 16)
-    const uint4 mq_cur = CARRY ? C.mapb[(size_t)cl * CL_T + tid] : make_uint4(0u, 0u, 0u, 0u);
+    // CARRY: residual destination of the row this lane sums in the output phase (wave * 16 + lane % 16)
     const int fv_own = CARRY ? C.fdst[(size_t)cl * CL_NM_MAX + wave * 16 + (lane & 15)] : 0;
     unsigned sinfo[CL_SPT];
 #pragma unroll
@@ -2133,7 +2134,6 @@ __global__ __launch_bounds__(CL_T) void k_cluster_q2hex_sf(AsmParams P, SfTab ta
     sf_stamp<INS>(st, 9);
     if (!(P.debug & 2)) {
       const unsigned mw[4] = {mp_cur.x, mp_cur.y, mp_cur.z, mp_cur.w};
-      const unsigned mq[4] = {mq_cur.x, mq_cur.y, mq_cur.z, mq_cur.w};
       // CARRY: the residual entry of a carried row that an earlier cluster of the super-cluster stored (same workgroup, a barrier ago); consumed behind the stores
       double fold = 0.0;
       if (CARRY && lane < 16 && fv_own >= 0 && (fv_own & 0x40000000))
@@ -2147,9 +2147,12 @@ __global__ __launch_bounds__(CL_T) void k_cluster_q2hex_sf(AsmParams P, SfTab ta
 #pragma unroll
       for (int i = 0; i < CL_SPT; i++) {
         const unsigned si = sinfo[i];
-        const int j = (mw[i >> 2] >> (8 * (i & 3))) & 255;
+        const int mb = (mw[i >> 2] >> (8 * (i & 3))) & 255;
         const int p = (si >> 7) & 127;
-        const int pos = CARRY ? (int)((mq[i >> 2] >> (8 * (i & 3))) & 255) : p;
+        // the slot's class comes with the word (not from rb[]: j feeds the descriptor address, a look-up would put an LDS round trip in front of it)
+        const bool crow = CARRY && ((mw[3] >> (10 + i)) & 1u);
+        const int j = crow ? p : mb;
+        const int pos = crow ? mb : p;
         dd[i] = dtab[(si >> 14) + j];
         vb[i] = rb[si & 127] + (unsigned long long)(pos * 8);
       }
@@ -2299,15 +2302,18 @@ __global__ __launch_bounds__(256) void k_rows_partial(int nprow, const int* __re
 //   complete row: e = the entry whose macro column carries the global column at CSR position p, q = p (the row is written in CSR order)
 //   carried row:  e = p, q = the CSR position of that entry's column (stored, or added to what the earlier clusters of the super-cluster left there)
 //   partial row:  e = q = p (packed row in the partial-row buffer; pmap gets the CSR position for the second pass)
-//   map  (always):        bytes 0 .. 9 = e of slot i; bits 16 + i of word 2: carried entry that an EARLIER cluster has stored already (load, add, store)
-//   mapb (carried plans): bytes 0 .. 9 = q of slot i; bits 16 + i of word 2: carried entry to which a LATER cluster still adds (the Galerkin product reads an
-//                         entry in the cluster that made the last contribution)
+// Of e and q at most one differs from p, which the readers have from the slot table, so ONE word carries the slot: its informative byte m and a class bit
+//   bytes 0 .. 9 (words 0, 1, low half of word 2) = m of slot i: e (complete row), q (carried row), p (partial row)
+//   word 2, bits 16 + i: carried entry that an EARLIER cluster has stored already (load, add, store)
+//   word 3, bits i:      carried entry to which a LATER cluster still adds (the Galerkin product reads an entry in the cluster that made the last contribution)
+//   word 3, bits 10 + i: class -- 1: carried row, m is the destination position and the entry is p; 0: m is the entry and the position is p
+// so the readers decode e = class ? p : m, q = class ? m : p; a plan without carried rows has no bit of word 3 set.
 // An entry that cannot be placed raises err (the assembler then keeps the two-pass path).  first_cnt[g] counts the first contributions to carried row g: the
 // caller checks that they cover the whole CSR row (a position nobody stores to would keep stale values).
 __global__ __launch_bounds__(256) void k_cluster_maps(int ncl, int ns, int nm, const int* __restrict__ cdof, const unsigned* __restrict__ sinfo, const unsigned short* __restrict__ roff,
                                                       const unsigned char* __restrict__ tcol, const int* __restrict__ vdst, int m, const int* __restrict__ rowptr, const int* __restrict__ col,
                                                       const unsigned char* __restrict__ rowcls, const int* __restrict__ aptr, const int* __restrict__ aei,
-                                                      const int* __restrict__ elem_dof, int nloc, uint4* __restrict__ map, uint4* __restrict__ mapb, unsigned char* __restrict__ pmap,
+                                                      const int* __restrict__ elem_dof, int nloc, uint4* __restrict__ map, unsigned char* __restrict__ pmap,
                                                       unsigned* __restrict__ first_cnt, int* __restrict__ err) {
   __shared__ int cd[CL_NM_MAX];
   const int c = blockIdx.x;
@@ -2325,11 +2331,11 @@ __global__ __launch_bounds__(256) void k_cluster_maps(int ncl, int ns, int nm, c
     return -1;
   };
   for (int tid = threadIdx.x; tid < CL_T; tid += 256) {
-    unsigned w[4] = {0u, 0u, 0u, 0u}, wb[4] = {0u, 0u, 0u, 0u};
+    unsigned w[4] = {0u, 0u, 0u, 0u};
     for (int i = 0; i < CL_SPT; i++) {
       const unsigned si = sinfo[i * CL_T + tid];
       const int r = si & 127, p = (si >> 7) & 127, o = si >> 14;
-      unsigned byte = (unsigned)p, pos_b = (unsigned)p, cls = 0, acc = 0, last = 1;
+      unsigned byte = (unsigned)p, carried = 0, cls = 0, acc = 0, last = 1;
       if (r < nm) {
         const int len = roff[r + 1] - o;
         const int vb = vdst[(size_t)c * CL_NM_MAX + r];
@@ -2348,7 +2354,8 @@ __global__ __launch_bounds__(256) void k_cluster_maps(int ncl, int ns, int nm, c
             const int target = cd[tcol[o + p]];
             int pos = find_pos(g, target);
             if (pos < 0 || pos > 127) { atomicExch(err, 1); pos = 0; }
-            pos_b = (unsigned)pos;
+            byte = (unsigned)pos;
+            carried = 1;
             bool later = false;
             if (target < m) {        // the elements that hold BOTH nodes: the two element lists are sorted, a merge finds the common ones (<= 8 + 8 steps)
               int a = aptr[g], b = aptr[target];
@@ -2387,12 +2394,10 @@ __global__ __launch_bounds__(256) void k_cluster_maps(int ncl, int ns, int nm, c
         }
       }
       w[i >> 2] |= byte << (8 * (i & 3));
-      wb[i >> 2] |= pos_b << (8 * (i & 3));
       w[2] |= acc << (16 + i);
-      wb[2] |= (last ? 0u : 1u) << (16 + i);
+      w[3] |= ((last ? 0u : 1u) << i) | (carried << (10 + i));
     }
     map[(size_t)c * CL_T + tid] = make_uint4(w[0], w[1], w[2], w[3]);
-    if (mapb) mapb[(size_t)c * CL_T + tid] = make_uint4(wb[0], wb[1], wb[2], wb[3]);
   }
 }
 // every position of a carried CSR row must receive exactly one first contribution
@@ -2718,7 +2723,6 @@ static int cluster_plan_build(fh_assembler_t as, fh_mat_t A, const int* elem_dof
   FH_TRY(up((void**)&as->d_cl_prow, prow.data(), prow.size() * 4));
   FH_TRY(up((void**)&as->d_cl_pstart, pstart.data(), pstart.size() * 4));
   FH_CHECK_HIP(hipMalloc(&as->d_cl_map, (size_t)ncl * CL_T * 16));
-  if (sup_shift > 0 || ctx->assemble_carry >= 200) FH_CHECK_HIP(hipMalloc(&as->d_cl_mapb, (size_t)ncl * CL_T * 16));
   FH_CHECK_HIP(hipMalloc(&as->d_cl_pmap, npart + 128));
   FH_CHECK_HIP(hipMemset(as->d_cl_pmap, 0xFF, npart + 128));      // 255 = residual entry (the map kernel fills in the matrix entries)
   FH_CHECK_HIP(hipMalloc(&as->d_Pbuf, (npart + 128) * sizeof(double)));
@@ -2739,7 +2743,7 @@ static int cluster_plan_build(fh_assembler_t as, fh_mat_t A, const int* elem_dof
     FH_CHECK_HIP(hipMemsetAsync(d_first, 0, (size_t)m * sizeof(unsigned), ctx->stream));
     FH_CHECK_HIP(hipMemsetAsync(d_ncar, 0, sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(k_cluster_maps, dim3(ncl), dim3(256), 0, ctx->stream, ncl, ns, nm, d_cdof, as->d_cl_sinfo, d_roff, d_tcol, as->d_cl_vdst, m, A->d_rowptr, A->d_col, d_complete,
-                       as->d_adj_ptr, as->d_adj_ei, as->d_elem_dof, nloc, reinterpret_cast<uint4*>(as->d_cl_map), reinterpret_cast<uint4*>(as->d_cl_mapb), as->d_cl_pmap, d_first, d_err);
+                       as->d_adj_ptr, as->d_adj_ei, as->d_elem_dof, nloc, reinterpret_cast<uint4*>(as->d_cl_map), as->d_cl_pmap, d_first, d_err);
     if (sup_shift > 0 && m > 0)
       hipLaunchKernelGGL(k_cl_cover, dim3(fh_div_up(m, 256)), dim3(256), 0, ctx->stream, m, A->d_rowptr, d_complete, d_first, d_err, d_ncar);
     FH_CHECK_HIP(hipGetLastError());
@@ -2754,7 +2758,7 @@ static int cluster_plan_build(fh_assembler_t as, fh_mat_t A, const int* elem_dof
       // (a pattern with positions no element contributes to: a carried row would keep stale values there) -- the plan without carried rows
       FH_TRACE("fh_assembler_create: carried rows do not cover their CSR rows -- cluster plan without them");
       for (void** q : {(void**)&as->d_cl_dtab, (void**)&as->d_cl_fblk, (void**)&as->d_cl_sinfo, (void**)&as->d_cl_oblk, (void**)&as->d_cl_gtab, (void**)&as->d_cl_vdst, (void**)&as->d_cl_vdst64,
-                       (void**)&as->d_cl_fdst, (void**)&as->d_cl_map, (void**)&as->d_cl_mapb, (void**)&as->d_cl_pmap, (void**)&as->d_Pbuf, (void**)&as->d_cl_prow, (void**)&as->d_cl_pstart}) {
+                       (void**)&as->d_cl_fdst, (void**)&as->d_cl_map, (void**)&as->d_cl_pmap, (void**)&as->d_Pbuf, (void**)&as->d_cl_prow, (void**)&as->d_cl_pstart}) {
         if (*q) FH_CHECK_HIP(hipFree(*q));
         *q = nullptr;
       }
@@ -2912,7 +2916,7 @@ static int launch_cluster(fh_assembler_t as, const AsmParams& P, fh_mat_t A, dou
   C.ncl = as->cl_ncl; C.ns = as->cl_ns; C.nm = as->cl_nm;
   C.dtab = reinterpret_cast<const uint2*>(as->d_cl_dtab); C.fblk = reinterpret_cast<const uint4*>(as->d_cl_fblk); C.oblk = reinterpret_cast<const uint4*>(as->d_cl_oblk);
   C.sinfo = as->d_cl_sinfo;
-  C.vdst = as->d_cl_vdst64; C.fdst = as->d_cl_fdst; C.map = reinterpret_cast<const uint4*>(as->d_cl_map); C.mapb = reinterpret_cast<const uint4*>(as->d_cl_mapb);
+  C.vdst = as->d_cl_vdst64; C.fdst = as->d_cl_fdst; C.map = reinterpret_cast<const uint4*>(as->d_cl_map);
   C.Pbuf = as->d_Pbuf; C.res = res;
   C.stamps = nullptr;
   C.sup_shift = as->cl_walk_shift;
@@ -2922,7 +2926,7 @@ static int launch_cluster(fh_assembler_t as, const AsmParams& P, fh_mat_t A, dou
     FH_TRY(ensure_geom_cache(as));
     if (as->geo_state == 1) C.geo = as->d_geo;
   }
-  if (as->cl_sup_shift > 0 || (as->ctx->assemble_carry >= 200 && as->d_cl_mapb)) {      // (>= 200: measurement aid, the CARRY kernel on a plan without carried rows)
+  if (as->cl_sup_shift > 0 || as->ctx->assemble_carry >= 200) {      // (>= 200: measurement aid, the CARRY kernel on a plan without carried rows: no class bit is set, it decodes what the plain kernel decodes)
     if (C.geo) FH_TRY((launch_cluster_one<0, true, true>(as, P, C)));
     else if (P.source_kind == 4) FH_TRY((launch_cluster_one<2, true>(as, P, C)));
     else if (P.source_kind != 0) FH_TRY((launch_cluster_one<1, true>(as, P, C)));
@@ -3603,7 +3607,7 @@ extern "C" int fh_assembler_destroy(fh_assembler_t as) {
   if (as->d_prog) hipFree(as->d_prog);
   if (as->d_prog_consts) hipFree(as->d_prog_consts);
   hipFree(as->d_iota);
-  for (void* q : {(void*)as->d_cl_dtab, (void*)as->d_cl_fblk, (void*)as->d_cl_sinfo, (void*)as->d_cl_oblk, (void*)as->d_cl_gtab, (void*)as->d_cl_vdst, (void*)as->d_cl_vdst64, (void*)as->d_cl_fdst, (void*)as->d_cl_map, (void*)as->d_cl_mapb, (void*)as->d_cl_pmap,
+  for (void* q : {(void*)as->d_cl_dtab, (void*)as->d_cl_fblk, (void*)as->d_cl_sinfo, (void*)as->d_cl_oblk, (void*)as->d_cl_gtab, (void*)as->d_cl_vdst, (void*)as->d_cl_vdst64, (void*)as->d_cl_fdst, (void*)as->d_cl_map, (void*)as->d_cl_pmap,
                   (void*)as->d_Pbuf, (void*)as->d_geo, (void*)as->d_cl_prow, (void*)as->d_cl_pstart})
     if (q) hipFree(q);
   for (void* q : {(void*)as->d_adj_ptr, (void*)as->d_adj_ei, (void*)as->d_rowmap, (void*)as->d_Kbuf, (void*)as->d_Fbuf, (void*)as->d_slot, (void*)as->d_gal_child,
@@ -3816,6 +3820,14 @@ extern "C" int fh_assembler_carry_info(fh_assembler_t as, int* clusters_per_supe
   const bool on = as->fused && as->ctx->assemble_fused && as->ctx->assemble_sf;
   if (clusters_per_super) *clusters_per_super = on ? 1 << as->cl_sup_shift : 0;
   if (carried_entries) *carried_entries = on ? (int64_t)as->cl_ncarried : 0;
+  return 0;
+}
+
+extern "C" int fh_assembler_plan_info(fh_assembler_t as, int64_t* map_bytes, int* bytes_per_cluster) {
+  FH_REQUIRE(as, "fh_assembler_plan_info: null argument");
+  const bool have = as->fused && as->d_cl_map;
+  if (map_bytes) *map_bytes = have ? (int64_t)as->cl_ncl * CL_T * 16 : 0;
+  if (bytes_per_cluster) *bytes_per_cluster = have ? CL_T * 16 : 0;
   return 0;
 }
 
@@ -4119,7 +4131,7 @@ __global__ __launch_bounds__(256) void k_gal_masks(int nelc, const int* __restri
 
 template <bool INS>
 __global__ __launch_bounds__(GMAC_T) void k_galerkin_macro(int nelc, const int* __restrict__ child, int nm, const unsigned* __restrict__ sinfo, const uint4* __restrict__ map,
-                                                           const uint4* __restrict__ mapb /* carried plans, else null */, const unsigned long long* __restrict__ vdst, const unsigned short* __restrict__ gtab,
+                                                           const unsigned long long* __restrict__ vdst, const unsigned short* __restrict__ gtab,
                                                            const unsigned* __restrict__ fmask, const unsigned* __restrict__ cmask,
                                                            const int* __restrict__ slot_c, double* __restrict__ Kc, int ks_c, const double* __restrict__ Cdense /* [8][27][27] */,
                                                            unsigned long long* __restrict__ stamps) {
@@ -4162,27 +4174,25 @@ __global__ __launch_bounds__(GMAC_T) void k_galerkin_macro(int nelc, const int* 
   __syncthreads();
   double tv[CL_SPT];
   // where slot i of a cluster's macro matrix is read: position p of the row (complete / partial rows), or -- a row carried in the CSR array across the clusters of a
-  // super-cluster -- the CSR position the map byte names, and only in the cluster that made the LAST contribution (the entry holds the sum of all of them there;
-  // the pseudo child matrices still add up to the assembled matrix, which is all the coarse operator depends on); -1: nothing to read
+  // super-cluster (class bit 10 + i of word 3) -- the CSR position the map byte names, and only in the cluster that made the LAST contribution (bit i of word 3
+  // clear; the entry holds the sum of all of them there; the pseudo child matrices still add up to the assembled matrix, which is all the coarse operator depends
+  // on); -1: nothing to read
   auto slot_pos = [&](const uint4& q4, int i) {
     const unsigned mq[4] = {q4.x, q4.y, q4.z, q4.w};
     const int r = si[i] & 127, p = (si[i] >> 7) & 127;
     if (r >= nm) return -1;
-    if (!mapb) return p;
-    return ((mq[2] >> (16 + i)) & 1u) ? -1 : (int)((mq[i >> 2] >> (8 * (i & 3))) & 255);
+    if ((mq[3] >> i) & 1u) return -1;
+    return ((mq[3] >> (10 + i)) & 1u) ? (int)((mq[i >> 2] >> (8 * (i & 3))) & 255) : p;
   };
-  const uint4 qzero = make_uint4(0u, 0u, 0u, 0u);
-  uint4 mq = mapb ? mapb[(size_t)cl * CL_T + tid] : qzero;
 #pragma unroll
   for (int i = 0; i < CL_SPT; i++) {
-    const int r = si[i] & 127, pos = slot_pos(mq, i);
+    const int r = si[i] & 127, pos = slot_pos(mp, i);
     tv[i] = pos >= 0 ? reinterpret_cast<const double*>(rbl[r])[pos] : 0.0;
   }
   int En = min(E + stride, nelc - 1);
   int cln = child[(size_t)En * NCH] >> 3;
   unsigned long long vdn = vdst[(size_t)cln * CL_NM_MAX + tm];
   uint4 mpn = map[(size_t)cln * CL_T + tid];
-  uint4 mqn = mapb ? mapb[(size_t)cln * CL_T + tid] : qzero;
   const int ln = min(lane, NC - 1);
   unsigned dmask = fmask[(size_t)E * NCH + wave], cdm = cmask[E];      // Dirichlet nodes of this wave's child / of the coarse element (k_gal_masks)
   int slc = slot_c[(size_t)E * NC + ln];
@@ -4196,7 +4206,8 @@ __global__ __launch_bounds__(GMAC_T) void k_galerkin_macro(int nelc, const int* 
       const unsigned mw[4] = {mp.x, mp.y, mp.z, mp.w};
 #pragma unroll
       for (int i = 0; i < CL_SPT; i++) {
-        const int r = si[i] & 127, j = (mw[i >> 2] >> (8 * (i & 3))) & 255;
+        const int r = si[i] & 127, mb = (mw[i >> 2] >> (8 * (i & 3))) & 255;
+        const int j = ((mw[3] >> (10 + i)) & 1u) ? (int)((si[i] >> 7) & 127) : mb;      // carried row: the entry is p
         if (r < nm) Tm[(si[i] >> 14) + j] = tv[i];
       }
     }
@@ -4207,10 +4218,9 @@ __global__ __launch_bounds__(GMAC_T) void k_galerkin_macro(int nelc, const int* 
     sf_stamp<INS>(st, 2);
     // the NEXT cluster's values: in flight during the products below
     mp = mpn;
-    mq = mqn;
 #pragma unroll
     for (int i = 0; i < CL_SPT; i++) {
-      const int r = si[i] & 127, pos = slot_pos(mq, i);
+      const int r = si[i] & 127, pos = slot_pos(mp, i);
       tv[i] = pos >= 0 ? reinterpret_cast<const double*>(rbl[r])[pos] : 0.0;
     }
     {
@@ -4218,7 +4228,6 @@ __global__ __launch_bounds__(GMAC_T) void k_galerkin_macro(int nelc, const int* 
       const int clnn = child[(size_t)Enn * NCH] >> 3;
       vdn = vdst[(size_t)clnn * CL_NM_MAX + tm];
       mpn = map[(size_t)clnn * CL_T + tid];
-      if (mapb) mqn = mapb[(size_t)clnn * CL_T + tid];
     }
     const unsigned long long cdead = cdm, dead = dmask;
     {   // the next element's masks and slots (consumed one iteration later)
@@ -4437,7 +4446,7 @@ extern "C" int fh_assembler_galerkin(fh_assembler_t fas, fh_assembler_t cas, con
       FH_CHECK_HIP(hipMalloc(&d_st, nst * sizeof(unsigned long long)));
       FH_CHECK_HIP(hipMemsetAsync(d_st, 0, nst * sizeof(unsigned long long), c->stream));
       hipLaunchKernelGGL(k_galerkin_macro<true>, dim3(gm_grid), dim3(GMAC_T), gmac_lds_bytes(), c->stream, cas->nel, cas->d_gal_child, fas->cl_nm, fas->d_cl_sinfo,
-                         reinterpret_cast<const uint4*>(fas->d_cl_map), reinterpret_cast<const uint4*>(fas->d_cl_mapb), fas->d_cl_vdst64, fas->d_cl_gtab, cas->d_gal_fmask, cas->d_gal_fmask + (size_t)cas->nel * 8, cas->d_slot, cas->d_Kbuf,
+                         reinterpret_cast<const uint4*>(fas->d_cl_map), fas->d_cl_vdst64, fas->d_cl_gtab, cas->d_gal_fmask, cas->d_gal_fmask + (size_t)cas->nel * 8, cas->d_slot, cas->d_Kbuf,
                          cas->kstride, cas->d_gal_dense, d_st);
       std::vector<unsigned long long> h(nst);
       FH_CHECK_HIP(hipMemcpyAsync(h.data(), d_st, nst * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -4455,7 +4464,7 @@ extern "C" int fh_assembler_galerkin(fh_assembler_t fas, fh_assembler_t cas, con
       for (int k = 0; k < 10; k++) fprintf(stderr, "  %2d %-62s %9.1f  %5.1f %%\n", k, name[k], sum[k] / std::max(ncl, 1.0), 100.0 * sum[k] / std::max(tot, 1.0));
     } else
       hipLaunchKernelGGL(k_galerkin_macro<false>, dim3(gm_grid), dim3(GMAC_T), gmac_lds_bytes(), c->stream, cas->nel, cas->d_gal_child, fas->cl_nm, fas->d_cl_sinfo,
-                         reinterpret_cast<const uint4*>(fas->d_cl_map), reinterpret_cast<const uint4*>(fas->d_cl_mapb), fas->d_cl_vdst64, fas->d_cl_gtab, cas->d_gal_fmask, cas->d_gal_fmask + (size_t)cas->nel * 8, cas->d_slot, cas->d_Kbuf,
+                         reinterpret_cast<const uint4*>(fas->d_cl_map), fas->d_cl_vdst64, fas->d_cl_gtab, cas->d_gal_fmask, cas->d_gal_fmask + (size_t)cas->nel * 8, cas->d_slot, cas->d_Kbuf,
                          cas->kstride, cas->d_gal_dense, (unsigned long long*)nullptr);
   } else if (c->galerkin_mfma) {
     const size_t lds = nc == 27 ? galerkin_mfma_lds<27, 8>() : galerkin_mfma_lds<9, 4>();

@@ -479,6 +479,11 @@ int fh_assembler_fused_info(fh_assembler_t as, int* active, int* nclusters, int6
  * leaves every workgroup at least two super-clusters, else 0.  The classes are read from the element lists; nothing about the mesh is assumed beyond the
  * cluster structure itself.  clusters_per_super = 1: nothing is carried; carried_entries = CSR entries of the carried rows. */
 int fh_assembler_carry_info(fh_assembler_t as, int* clusters_per_super, int64_t* carried_entries);
+/* Size of the fused plan's per-cluster words: every thread of the cluster kernel (512 per cluster) reads ONE 16-byte word per cluster -- the template entry
+ * or the destination position of each of its ten slots (at most one of the two differs from the slot's own position), a class bit per slot and the flags
+ * of the carried entries -- and the element-wise Galerkin product reads the same word.  *map_bytes = device memory of the words (clusters * 512 * 16, with
+ * or without carried rows; 0 when the assembler has no fused plan), *bytes_per_cluster = 8192.  Either pointer may be null. */
+int fh_assembler_plan_info(fh_assembler_t as, int64_t* map_bytes, int* bytes_per_cluster);
 /* "assemble_fused" = 1 chooses per assembly: the fused path, unless fh_assembler_galerkin asked for the element rows of the PREVIOUS assembly (a solve that
  * re-prepares its hierarchy after every assembly: the two-pass path leaves the rows in place); 2 = always fused (the rows are re-created when asked for),
  * 0 = never.  path: what the last assembly ran, 1 = fused, 2 = two-pass, 0 = none yet / another path.
