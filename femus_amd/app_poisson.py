@@ -377,7 +377,7 @@ class Poisson001:
         return out
 
     def run_elements_adaptive(self, max_amr_levels, threshold, norm="H1", neighbor_threshold=0.0, amr_mode="reference", log=None, smoother=capi.SMOOTH_GS_COLOR,
-                              omega=1.0, keep_steps=False):
+                              omega=1.0, keep_steps=False, exact=None, exact_gradient=None):
         """MGsolve with _AMRtest (LinearImplicitSystem.cpp:309-404, 529-558; SetAMRSetOptions(AMR, AMRlevels = max_amr_levels, AMRnorm = norm, AMRthreshold =
         threshold)): the nlevels uniform levels are built on the device and solved on the top one as run_elements(mesh_data="device") does; then, until the flags
         say converged or max_amr_levels levels have been added: AMREps = what the solve added to the top level's solution (the final solution minus the start
@@ -388,7 +388,11 @@ class Poisson001:
         live until the method returns; none is downloaded but the final coordinates (keep_steps=True also brings down, for every step, "sol", "eps" and the
         level's (kind, ed, xs, ff, lev, level): result["steps"], for tests).
         The result is run_elements(mesh_data="device")'s of the last solve, with "amr_history" (per step: nflagged, nel, threshold_in, threshold_out, sums,
-        converged), "elem_levels" and "hanging" of the final level and "nlevels"."""
+        converged), "elem_levels" and "hanging" of the final level and "nlevels".
+        With exact -- an expression over "x,y,z,t" (text or capi.Expr) -- every "amr_history" entry also carries "l2_error" and "h1_error" of that step's
+        solution (capi.ElementMesh.error_norms on the resident top level while the solution is uploaded for the flags): against the exact values at the Gauss
+        points when exact_gradient (dim expressions) is given, else against the exact function's nodal interpolant.  max_amr_levels = 0 at consecutive nlevels
+        gives the uniform convergence table of ex02."""
         from . import mixed_mesh
         ctx = self.ctx
         max_amr_levels = int(max_amr_levels)
@@ -397,6 +401,8 @@ class Poisson001:
         if amr_mode not in ("reference", "coarsest"):
             raise ValueError("amr_mode must be \"reference\" or \"coarsest\", not %r" % (amr_mode,))
         norm_code = capi.amr_norm("run_elements_adaptive", norm)
+        if exact is None and exact_gradient is not None:
+            raise ValueError("exact_gradient without exact")
         fam = {"linear": 0, "serendipity": 1, "biquadratic": 2}[self.fe]
         level0 = mixed_mesh.tri_box(self.box[0], self.box[1], self.lo[:2], self.hi[:2]) if self.box is not None else mixed_mesh.read_gambit(self.mesh_file)
         all_flags = sorted({int(f) for f in np.unique(level0[3]) if f < -1})
@@ -458,11 +464,14 @@ class Poisson001:
                 SOLv, EPSv = ctx.vector_from(sol), ctx.vector_from(eps)
                 try:
                     r = m.flag_by_error(fam, SOLv, EPSv, thr, norm_code, neighbor_threshold)
+                    en = m.error_norms(fam, SOLv, exact=exact, gradient=exact_gradient) if exact is not None else None
                 finally:
                     SOLv.destroy()
                     EPSv.destroy()
                 amr_history.append({"nflagged": r["nflagged"], "nel": m.nel, "threshold_in": thr, "threshold_out": r["threshold"], "sums": r["sums"],
                                     "converged": r["converged"]})
+                if en is not None:
+                    amr_history[-1]["l2_error"], amr_history[-1]["h1_error"] = en["l2"], en["h1"]
                 if log:
                     log("AMR step %d: %d of %d elements flagged, threshold %.6e -> %.6e%s" % (len(amr_history) - 1, r["nflagged"], m.nel, thr, r["threshold"],
                                                                                            ", converged" if r["converged"] else ""))

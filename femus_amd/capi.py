@@ -820,6 +820,29 @@ class ElementMesh:
                                                   _p(err2) if self.nel else None, _p(vol) if self.nel else None))
         return err2, vol
 
+    def error_norms(self, fe, sol, exact=None, gradient=None, against=None, order="seventh", per_element=False):
+        """the L2 norm and the H1 semi-norm of sol minus a known solution on the device (fh_elem_mesh_error_norms; GetErrorNorm_L2_H1_with_analytical_sol and its
+        variants): sol a Vec over own[fe] dofs.  What it is compared with follows from what is given: exact and gradient (dim of them) -> the exact values at
+        the Gauss points ("qp"); exact alone -> the exact function's nodal interpolant ("dofs"); against, a second Vec over own[fe] dofs -> that discrete
+        function ("vector").  exact and gradient[j] are Exprs over "x,y,z,t" or their texts.  Returns {"l2", "h1"}, with per_element also "elem_l2" and
+        "elem_h1" (the squared contributions of every element)"""
+        who = "ElementMesh.error_norms"
+        k = FE[fe] if isinstance(fe, str) else int(fe)
+        mode, ex, grad, made = _norm_arguments(who, self.dim, exact, gradient, against)
+        norms = np.zeros(2)
+        l2, h1 = (np.zeros(self.nel), np.zeros(self.nel)) if per_element else (None, None)
+        try:
+            _chk(self.L.fh_elem_mesh_error_norms(self.h, k, _gauss_order(who, order), sol.h if sol is not None else None, mode, ex, grad,
+                                                 against.h if against is not None else None, _p(norms), _p(l2) if per_element and self.nel else None,
+                                                 _p(h1) if per_element and self.nel else None))
+        finally:
+            for e in made:
+                e.destroy()
+        out = {"l2": float(norms[0]), "h1": float(norms[1])}
+        if per_element:
+            out["elem_l2"], out["elem_h1"] = l2, h1
+        return out
+
     def set_levels(self, lev):
         """the level of every element of a mesh uploaded non-homogeneous (fh_elem_mesh_set_levels); the mesh's level becomes their maximum"""
         lev = _i32(lev)
@@ -980,6 +1003,66 @@ def error_flag_host(kind, ed, xs, lev, level, fe, sol, eps, threshold, norm="H1"
                                                 _p(sol), _p(eps), amr_norm(who, norm), float(threshold), float(neighbor_threshold), _p(flags), _p(err2), _p(vol),
                                                 _p(sums), ctypes.byref(thr), ctypes.byref(n), ctypes.byref(conv)))
     return {"flags": flags, "err2": err2, "vol": vol, "sums": sums, "threshold": thr.value, "nflagged": int(n.value), "converged": bool(conv.value)}
+
+
+def _norm_arguments(who, dim, exact, gradient, against):
+    """(mode, exact handle, gradient handles, the Exprs compiled here) of error_norms: against -> 2 (vector), a gradient -> 0 (qp), exact alone -> 1 (dofs); what
+    a mode lacks or must not have is the library's refusal"""
+    if exact is None and gradient is None and against is None:
+        raise FemusHipError("%s: give exact and gradient, exact alone, or against" % who)
+    mode = 2 if against is not None else 0 if gradient is not None else 1
+    made = []
+
+    def handle(e):
+        if isinstance(e, str):
+            made.append(Expr(e, "x,y,z,t"))
+            return made[-1].h
+        return e.h
+    try:
+        ex = handle(exact) if exact is not None else None
+        grad = None
+        if gradient is not None:
+            gradient = [gradient] if isinstance(gradient, (str, Expr)) else list(gradient)
+            if len(gradient) != dim:
+                raise FemusHipError("%s: gradient has %d components, the mesh has dimension %d" % (who, len(gradient), dim))
+            grad = (ctypes.c_void_p * dim)(*[handle(g) if g is not None else None for g in gradient])
+    except BaseException:
+        for e in made:
+            e.destroy()
+        raise
+    return mode, ex, grad, made
+
+
+def error_norms_host(kind, ed, xs, fe, sol, exact=None, gradient=None, against=None, order="seventh"):
+    """ElementMesh.error_norms on the arrays of mixed_mesh, in the library without a device (fh_elem_error_norms_host): the same element body, so the same bits
+    wherever the expressions are made of + - * /, sqrt and the exact operations, and always against a vector.  Returns {"l2", "h1", "elem_l2", "elem_h1"}"""
+    who = "error_norms_host"
+    kind, xs = np.asarray(kind), _f64(xs)
+    code = np.zeros(kind.shape[0], dtype=np.int32)
+    for name, c in GEOM.items():
+        code[kind == name] = c
+    ed = _i32(ed)
+    nel = kind.shape[0]
+    if ed.shape != (nel, 27) or xs.ndim != 2:
+        raise FemusHipError("%s: ed must be [%d, 27] and xs [nnode, dim]" % (who, nel))
+    k = FE[fe] if isinstance(fe, str) else int(fe)
+    sol = _f64(sol) if sol is not None else None
+    against = _f64(against) if against is not None else None
+    if 0 <= k <= 2 and nel:
+        ndof = 1 + max(int(ed[kind == s][:, :_NDOFS[s][k]].max()) for s in set(kind.tolist()) if s in _NDOFS)
+        for name, v in (("sol", sol), ("against", against)):
+            if v is not None and v.shape != (ndof,):
+                raise FemusHipError("%s: %s has %d entries, the family has %d dofs on this mesh" % (who, name, v.size, ndof))
+    mode, ex, grad, made = _norm_arguments(who, int(xs.shape[1]), exact, gradient, against)
+    norms, l2, h1 = np.zeros(2), np.zeros(nel), np.zeros(nel)
+    try:
+        _chk(load_library().fh_elem_error_norms_host(int(xs.shape[1]), nel, _p(code), _p(ed), int(xs.shape[0]), _p(xs), k, _gauss_order(who, order),
+                                                     _p(sol) if sol is not None else None, mode, ex, grad, _p(against) if against is not None else None,
+                                                     _p(norms), _p(l2), _p(h1)))
+    finally:
+        for e in made:
+            e.destroy()
+    return {"l2": float(norms[0]), "h1": float(norms[1]), "elem_l2": l2, "elem_h1": h1}
 
 
 def fe_elem_prolongator(geom, fe):

@@ -21,24 +21,15 @@
 //                      d_flags of the mesh, the terms of volumeTestFalse and errTestTrue2 to the work arrays, the count by one integer atomic per wave
 //   5. k_ee_reduce     the last two sums
 // The new threshold and the convergence test are evaluated on the host in double.
-#include "fh_elemmesh.h"
-#include "fh_elemerror_body.h"
+#include "fh_elemerror.h"
 #include <cmath>
 
 using namespace fherr;
 
-namespace {
-struct EeTabs {                   // per shape code: dofs of the family, Gauss points, where w / phi / dphi start in the table buffer (doubles)
-  int nc[EM_G], ng[EM_G], ow[EM_G], ophi[EM_G], odphi[EM_G];
-};
-struct EeHostTabs {
-  EeTabs t;
-  std::vector<double> buf;
-  int ncmax = 0, ngmax = 0;
-};
+// ---- shared with fh_elemnorm.hip (fh_elemerror.h) ----
+namespace fherr {
 bool ee_shape(int g) { return g == fhfe::GEOM_HEX || g == fhfe::GEOM_QUAD || g == fhfe::GEOM_TRI || g == fhfe::GEOM_TET || g == fhfe::GEOM_WEDGE; }
 
-// the tables of every shape with present[g] != 0: the ones the generic assembler uploads (fhfe::shape_tables)
 int ee_tables(const char* who, int dim, int fe, int order, const bool present[EM_G], EeHostTabs& H) {
   memset(&H.t, 0, sizeof(H.t));
   FH_REQUIRE(order >= 0 && order <= 4, "%s: unsupported Gauss rule %d", who, order);
@@ -63,16 +54,6 @@ int ee_tables(const char* who, int dim, int fe, int order, const bool present[EM
   return 0;
 }
 
-int ee_check_options(const char* who, int fe, int norm, double threshold, double neighbor_threshold) {
-  FH_REQUIRE(fe >= 0 && fe <= 2, "%s: fe must be 0 (linear), 1 (serendipity) or 2 (biquadratic), not %d", who, fe);
-  FH_REQUIRE(norm == 0 || norm == 1, "%s: norm must be 0 (L2) or 1 (H1), not %d", who, norm);
-  FH_REQUIRE(std::isfinite(threshold) && threshold >= 0.0, "%s: the threshold must be finite and not negative, not %g", who, threshold);
-  FH_REQUIRE(std::isfinite(neighbor_threshold) && neighbor_threshold >= 0.0, "%s: the neighbour threshold must be finite and not negative, not %g", who,
-             neighbor_threshold);
-  return 0;
-}
-
-// the shape of k_ee_reduce on the host
 double ee_fixed_sum(std::vector<double> a) {
 #pragma clang fp contract(off)
   if (a.empty()) return 0.0;
@@ -94,6 +75,17 @@ double ee_fixed_sum(std::vector<double> a) {
     a.swap(out);
   } while (a.size() > 1);
   return a[0];
+}
+}  // namespace fherr
+
+namespace {
+int ee_check_options(const char* who, int fe, int norm, double threshold, double neighbor_threshold) {
+  FH_REQUIRE(fe >= 0 && fe <= 2, "%s: fe must be 0 (linear), 1 (serendipity) or 2 (biquadratic), not %d", who, fe);
+  FH_REQUIRE(norm == 0 || norm == 1, "%s: norm must be 0 (L2) or 1 (H1), not %d", who, norm);
+  FH_REQUIRE(std::isfinite(threshold) && threshold >= 0.0, "%s: the threshold must be finite and not negative, not %g", who, threshold);
+  FH_REQUIRE(std::isfinite(neighbor_threshold) && neighbor_threshold >= 0.0, "%s: the neighbour threshold must be finite and not negative, not %g", who,
+             neighbor_threshold);
+  return 0;
 }
 
 // what follows the sums, on the host in double: the new threshold in the reference's expression (Solution.cpp:1083), 1 when nothing is flagged
@@ -204,8 +196,10 @@ __global__ __launch_bounds__(256) void k_ee_flags(int nel, int level, double thr
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
 }
 
+}  // namespace
+
 // nk arrays of n entries at d_in (stride n) -> d_out[0 .. nk); p0 / p1 hold nk * ceil(n / EE_RC) doubles each
-void ee_reduce(hipStream_t st, size_t n, int nk, const double* d_in, double* p0, double* p1, double* d_out) {
+void fherr::ee_reduce(hipStream_t st, size_t n, int nk, const double* d_in, double* p0, double* p1, double* d_out) {
   const double* in = d_in;
   size_t stride = n;
   double* p[2] = {p0, p1};
@@ -222,6 +216,7 @@ void ee_reduce(hipStream_t st, size_t n, int nk, const double* d_in, double* p0,
   } while (n > 1);
 }
 
+namespace {
 struct EeWork {
   double *d_tab = nullptr, *d_T = nullptr, *d_err = nullptr, *d_p0 = nullptr, *d_p1 = nullptr, *d_sums = nullptr;
   unsigned char* d_vmark = nullptr;

@@ -18,15 +18,13 @@ FH_HD inline double ee_scale2(int fe, int norm) {
 }
 FH_HD inline int ee_nterms(int dim, int norm) { return norm ? 1 + dim : 1; }
 
-// One Gauss point: elem_type::Jacobian over the family's first nc nodes (Jac[a][b] += dphi_n/dxi_a x_n[b], nodes ascending; the inverse and the determinant in
-// the reference's terms; grad phi_n [a] = sum_b dphi_n/dxi_b JacI[a][b] from the left), then solig / solGradig and errig / errGradig (nodes ascending) and the
-// terms as the reference writes them: v v w, g_j g_j w and scale v v w, scale g_j g_j w.  X[n * 3 + b], phi[n], dphi[n * dim + a] of this point.
-// out[0] = weight, out[1 .. nt] the solution's terms (S null: zeros), out[1 + nt .. 2 nt] the error's.
+// elem_type::Jacobian over the family's first nc nodes (Jac[a][b] += dphi_n/dxi_a x_n[b], nodes ascending; the inverse and the determinant in the reference's
+// terms): fills JacI and returns the point's weight.  X[n * 3 + b], dphi[n * dim + a] of this point.  Shared by the flags' body below and the norms' body
+// (fh_elemnorm_body.h).
 template <int dim>
-FH_HD inline void ee_point_t(int nc, double wg, const double* phi, const double* dphi, const double* X, const double* S, const double* E, int norm, double sc,
-                           double* out) {
+FH_HD inline double ee_jacobian_t(int nc, double wg, const double* dphi, const double* X, double Ji[3][3]) {
 #pragma clang fp contract(off)
-  double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, Ji[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, det;
+  double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, det;
   for (int n = 0; n < nc; n++)
     for (int a = 0; a < dim; a++)
       for (int b = 0; b < dim; b++) J[a][b] += dphi[n * dim + a] * X[n * 3 + b];
@@ -48,15 +46,34 @@ FH_HD inline void ee_point_t(int nc, double wg, const double* phi, const double*
     Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
     Ji[2][2] = (-J[0][1] * J[1][0] + J[0][0] * J[1][1]) / det;
   }
-  const double weight = det * wg;
+  return det * wg;
+}
+
+// grad phi_n [a] = sum_b dphi_n/dxi_b JacI[a][b], from the left; dphi_n = the node's dim reference derivatives
+template <int dim>
+FH_HD inline double ee_gradphi_t(const double* dphi_n, const double Ji[3][3], int a) {
+#pragma clang fp contract(off)
+  double g = dphi_n[0] * Ji[a][0];
+  for (int b = 1; b < dim; b++) g = g + dphi_n[b] * Ji[a][b];
+  return g;
+}
+
+// One Gauss point: weight and gradients as above, then solig / solGradig and errig / errGradig (nodes ascending) and the terms as the reference writes them:
+// v v w, g_j g_j w and scale v v w, scale g_j g_j w.  X[n * 3 + b], phi[n], dphi[n * dim + a] of this point.
+// out[0] = weight, out[1 .. nt] the solution's terms (S null: zeros), out[1 + nt .. 2 nt] the error's.
+template <int dim>
+FH_HD inline void ee_point_t(int nc, double wg, const double* phi, const double* dphi, const double* X, const double* S, const double* E, int norm, double sc,
+                           double* out) {
+#pragma clang fp contract(off)
+  double Ji[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  const double weight = ee_jacobian_t<dim>(nc, wg, dphi, X, Ji);
   double sv = 0., ev = 0., sg[3] = {0., 0., 0.}, eg[3] = {0., 0., 0.};
   for (int n = 0; n < nc; n++) {
     if (S) sv += phi[n] * S[n];
     ev += phi[n] * E[n];
     if (norm)
       for (int a = 0; a < dim; a++) {
-        double g = dphi[n * dim] * Ji[a][0];
-        for (int b = 1; b < dim; b++) g = g + dphi[n * dim + b] * Ji[a][b];
+        const double g = ee_gradphi_t<dim>(dphi + n * dim, Ji, a);
         if (S) sg[a] += S[n] * g;
         eg[a] += E[n] * g;
       }

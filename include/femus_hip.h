@@ -530,6 +530,30 @@ int fh_assemble_poisson_expr(fh_assembler_t as, fh_vec_t sol, fh_expr_t source, 
 int fh_assemble_neumann_faces_expr(fh_ctx_t ctx, int geom, int fe, int gauss_order, int nfaces, const int* face_nodes, const int* face_expr,
                                    int nexpr, const fh_expr_t* exprs, int nnode, const double* coords, fh_vec_t res);
 
+/* ---- error norms of a resident element mesh's solution (fh_elemnorm.hip): GetErrorNorm_L2_H1_with_analytical_sol (FE_convergence.hpp:1279-1415) and its
+ * variants (:1457-, :480-935) for one variable of family fe whose vector sol runs over the mesh's own[fe] dofs, any mix of shapes, homogeneous or not (every
+ * element counts: the copies and children of a flagged level cover the domain once).  At every Gauss point, with weight, phi, phi_x of the family's own Jacobian
+ * over the family's first nc nodes: u_h = sum_i phi_i sol_i, g_h[j] = sum_i phi_x[i,j] sol_i (i ascending), and the comparison values by mode
+ *   0 "qp"      x_g[j] = sum_i x_i[j] phi_i; u = exact(x_g), g[j] = gradient[j](x_g), programs over at most x, y, z, t at the point (x_g, 0 ..., t = 0);
+ *               exact and all dim gradients are required, other must be NULL
+ *   1 "dofs"    U_i = exact(x_i) at the element's nc dofs; u = sum phi_i U_i, g[j] = sum phi_x[i,j] U_i; gradient and other must be NULL
+ *   2 "vector"  U_i = other_i, a second vector over own[fe] dofs (e.g. a coarser solution prolonged); exact and gradient must be NULL
+ * l2_i = sum over the points (ascending) of (u_h - u)(u_h - u) weight, h1_i of (g_h[j] - g[j])(g_h[j] - g[j]) weight for j ascending, each term added on its
+ * own; norms = {sqrt(sum l2_i), sqrt(sum h1_i)}: the L2 norm and the H1 semi-norm, the sums in the fixed shape of fh_elem_mesh_error_flag's (no floating-point
+ * atomics: a repeated call gives the same bits), the square roots on the host.  The boundary integrals of :780-870 are not part of this.
+ *   fh_elem_mesh_error_norms   on the resident mesh; two launches, nothing per element on the host
+ *   fh_elem_error_norms_host   the same statement on plain arrays, no context and no device: the element body is one text compiled for both sides, so l2_i, h1_i
+ *                              and the norms are the device's bit for bit in mode 2 always, and in modes 0 and 1 for programs of + - * /, sqrt and the exact
+ *                              operations (sin, cos, exp and their like differ by the ulps of the two math libraries)
+ * Refused before anything is allocated, with a message that names the argument: fe outside 0 .. 2, mode outside 0 .. 2, an unsupported Gauss rule, an expression
+ * missing for its mode or present where it is not allowed, a program over more than four variables, a vector of another size than own[fe] or of another context
+ * than the mesh's, sol NULL. */
+int fh_elem_mesh_error_norms(fh_elem_mesh_t mesh, int fe, int gauss_order, fh_vec_t sol, int mode, fh_expr_t exact, const fh_expr_t* gradient /* [dim] or NULL */,
+                             fh_vec_t other, double norms[2], double* elem_l2 /* host [nel] or NULL */, double* elem_h1 /* host [nel] or NULL */);
+int fh_elem_error_norms_host(int dim, int nel, const int* elem_geom, const int* elem_dof /* [nel*27] */, int nnode, const double* coords, int fe, int gauss_order,
+                             const double* sol, int mode, fh_expr_t exact, const fh_expr_t* gradient /* [dim] or NULL */, const double* other,
+                             double norms[2], double* elem_l2 /* [nel] or NULL */, double* elem_h1 /* [nel] or NULL */);
+
 /* The callback of applications/001_Poisson on a ONE-DIMENSIONAL mesh (main.cpp:355-480 with dim == 1; the shipped input/input1D.json: an EDGE3 box with
  * V = 1, nu = 0.01, main.cpp:392-395): advection-diffusion with the streamline-upwind terms of that loop.  elem_dof[nel*3]: the nodes of every element in
  * EDGE3 order (the two ends, then the middle: MeshGeneration.cpp:231-233), vertices numbered first so that a node id is its dof id in both families;
