@@ -1,6 +1,18 @@
 // Batched Poisson assembly on gfx950 (K1-K4 of SURVEY 2.1; a4, a7, a12 of SURVEY 8): fh_assembler_* and nothing else.  The public elem_type::Jacobian and the
 // face integrals are in fh_faces.hip, the one-dimensional callback in fh_line.hip, the generic (dim, nc, ng) path of simplex / prism / mixed meshes in fh_generic.hip.
-// Restates, as ONE device pass per element colour, the per-element callback of
+// The element-wise Galerkin product, which consumes what an assembly leaves behind, is in fh_galerkin.hip; fh_assembler.h holds what the two share.
+// The paths, in the order in which this file holds them:
+//   1. coloured scatter (k_assemble_poisson; every geometry and order): one device pass per element colour, described below
+//   2. the row pass of the two-pass assembly (k_row_assemble, k_row_assemble2_t): element matrices go to the element-row buffer, then every CSR row
+//      sums its element rows in element order
+//   3. the HEX27 / Q2 element-matrix kernels that fill that buffer: symmetric tiles (k_elem_q2hex_sym), matrix cores (k_elem_q2hex_mfma),
+//      sum-factorised (k_elem_q2hex_sf, whose phases the cluster kernel shares)
+//   4. the fused cluster assembly (k_cluster_q2hex_sf + k_rows_partial), its plan builder (k_cluster_maps, k_cl_*, cluster_plan_build), its
+//      instrumented launch and its geometry cache
+//   5. the reference-matrix kernel of affine elements (k_elem_q2hex_affine), the dispatch of the element kernels
+//   6. host side: fh_assembler_create / destroy, assemble_poisson_core, which chooses the path and records what it left behind, the functions
+//      through which the Galerkin product asks for that, the queries
+// The coloured scatter restates the per-element callback of
 //   src/08_equations/assemble/00_poisson_eqn_with_all_dirichlet_bc_AD_or_nonAD_separate.hpp:106-228
 // with elem_type::Jacobian from src/02_reference_geom_elements/03_fe_evaluations_at_quadrature/ElemType.hpp:1183-1248
 // (2-D) and :1438-1537 (3-D):
@@ -16,99 +28,10 @@
 //            every (i,j) comes from a precomputed element->CSR map (emap, built once per pattern) or, if disabled,
 //            from a binary search in the sorted row.
 // The small dense K is FP64-VALU work, not an MFMA target (north_star); the scatter side is HBM-bound.
-#include "fh_internal.h"
+#include "fh_assembler.h"
 #include "fh_fe.h"
 #include "fh_expr_device.h"
 #include <algorithm>
-
-struct SfTab { double L[3][4], D[3][4]; };   // l_a(x_k), l'_a(x_k): 1-D quadratic Lagrange basis (nodes -1, 0, +1) at the four abscissae
-
-struct fh_assembler_s {
-  fh_ctx_t ctx = nullptr;
-  int geom = 0, fe = 0, order = 0, dim = 3, nc = 27, ng = 64, nloc = 27;
-  int nel = 0, nnode = 0, ndof = 0;
-  int ncolors = 0;
-  std::vector<int> color_ptr;    // host
-  int* d_color_elems = nullptr;  // elements grouped by colour
-  int* d_elem_dof = nullptr;     // [nel*nloc]
-  double* d_coords = nullptr;    // [nnode*dim]
-  double* d_w = nullptr;         // [ng]
-  double* d_phi = nullptr;       // [ng*nc]
-  double* d_dphi = nullptr;      // [ng*nc*dim]
-  int* d_emap = nullptr;         // [nel*nc*ncp] CSR slot of (i,j), ncp = nc rounded up to 4
-  int* d_iota = nullptr;         // identity element list (for the uncoloured element-matrix entry point)
-  int ncp = 28;
-  // two-pass ("row gather") assembly: element matrices -> Kbuf, then every CSR row sums its <= 8 element rows in element order
-  int* d_adj_ptr = nullptr;      // [m+1]
-  int* d_adj_ei = nullptr;       // (element << 5) | local row, ascending element order
-  unsigned char* d_rowmap = nullptr;   // [nadj*nc] slot of (element row, j) inside the CSR row
-  int* d_slot = nullptr;         // [nel*nc] adjacency slot of (element, local row), -1 when the row is not in the matrix
-  double* d_Kbuf = nullptr;      // [nadj*kstride] element rows in row-gather order
-  size_t kbuf_bytes = 0;
-  int nadj = 0;                  // element rows in d_Kbuf; row nadj is the spare one
-  // element-wise Galerkin product from the next finer level (fh_assembler_galerkin): children, child interpolation tables, Dirichlet masks
-  int* d_gal_child = nullptr;
-  uint64_t gal_key = 0;          // hash of (children, fine / coarse Dirichlet nodes) the tables below were made from
-  bool gal_children_in_order = false;      // child j of coarse element E is fine element 8 * (its cluster) + j
-  unsigned char *d_gal_cnt = nullptr, *d_gal_row = nullptr, *d_gal_fb = nullptr, *d_gal_cb = nullptr;
-  unsigned* d_gal_fmask = nullptr;     // [nel * 8] Dirichlet bits of the children's nodes, then [nel] of the coarse element's (k_galerkin_macro)
-  double *d_gal_val = nullptr, *d_gal_res = nullptr, *d_gal_dense = nullptr;
-  int kstride = 27;              // doubles per element row in d_Kbuf (nc, or 32 for HEX27/Q2: whole 64-byte lines per row)
-  double* d_Fbuf = nullptr;      // [nadj]
-  bool two_pass = false;
-  // fused cluster assembly (k_cluster_q2hex_sf + k_rows_partial): groups of 8 consecutive elements with one common local topology
-  // (the children of one coarse element: 125 macro nodes).  Plan = tables of the template + per-cluster destinations and maps.
-  bool fused = false;            // plan built and verified
-  bool kbuf_valid = false;       // the element-row buffer holds the matrices of the last assembly (the fused path does not write it)
-  bool rows_used_since = false;  // the element-wise Galerkin product asked for the element rows since the last assembly: the next assembly keeps them (two-pass)
-  int last_path = 0;             // 1: the last assembly ran the fused path, 2: two-pass
-  int cl_ncl = 0, cl_nm = 0, cl_ns = 0, cl_nprow = 0;
-  int cl_sup_shift = 0;          // log2 of the clusters per super-cluster whose inner rows are carried in the CSR array (0: none)
-  int cl_walk_shift = 0;         // log2 of the consecutive clusters a workgroup of the cluster kernel serves one after the other (= cl_sup_shift; measurements: assemble_carry 100 + k walks 2^k clusters with nothing carried)
-  size_t cl_ncarried = 0;        // CSR entries of carried rows
-  size_t cl_npart = 0;           // entries of the partial-row buffer (without the sink)
-  unsigned* d_cl_sinfo = nullptr;
-  void *d_cl_dtab = nullptr, *d_cl_fblk = nullptr, *d_cl_oblk = nullptr;      // descriptor tables of the template (see ClParams)
-  int *d_cl_vdst = nullptr, *d_cl_fdst = nullptr;      // [ncl][128]: >= 0 CSR offset / row of a complete row, bit 31: offset into the partial-row buffer
-  unsigned long long* d_cl_vdst64 = nullptr;           // ... as addresses, for the value array cl_val_base
-  double* cl_val_base = nullptr;
-  unsigned char *d_cl_map = nullptr, *d_cl_pmap = nullptr;
-  unsigned short* d_cl_gtab = nullptr;      // [8][27 * 27] template entry that child j OWNS at (local row, local column), 0xffff = another child's (fh_assembler_galerkin from the macro rows)
-  bool cl_all_rows = false;                 // every row of every cluster lies in the matrix (no ghost rows, no sink): the macro rows can be read back
-  bool macro_valid = false;                 // the matrix cl_val_base and the partial-row buffer hold the macro rows of the last assembly
-  uint64_t macro_uid = 0;                   // the matrix of that assembly (fh_mat_s::uid, not its address: it may be destroyed, and a later one may get the address)
-  uint64_t macro_val_gen = 0;               // ... as long as nobody but SetPenalty has written the matrix since (fh_mat_s::val_gen)
-  double* d_Pbuf = nullptr;
-  // geometry cache of the fused assembly (option assemble_geom_cache): what phase A computes from this assembler's node coordinates alone, [nel][7][64]:
-  // rows 0 .. 5 D_q, row 6 det * w, lane = Gauss point in the cluster kernel's order.  Made at the first fused assembly with a constant source.
-  double* d_geo = nullptr;
-  int geo_state = 0;                        // 0: not made yet, 1: made, -1: the allocation failed (phase A stays in the kernel)
-  int* d_cl_prow = nullptr;                 // rows of the second pass
-  unsigned* d_cl_pstart = nullptr;          // [nprow + 1] their segments of the partial-row buffer
-  // arguments of the last assembly (the element-wise Galerkin product re-creates the element rows from them when the fused path ran)
-  int last_source_kind = 0;
-  double last_params[2] = {1.0, 0.0};
-  // optional fast path for AFFINE HEX27/Q2 elements (option assemble_affine): K_e = sum_ab det*B_ab * M_ab with the nine reference
-  // matrices M_ab = sum_g w_g d_a phi_i d_b phi_j, B = J^-1 J^-T; curved elements keep the quadrature kernel
-  int *d_aff_elems = nullptr, *d_gen_elems = nullptr;
-  int n_aff = 0, n_gen = 0;
-  double *d_Mab = nullptr, *d_mphi = nullptr;
-  // matrix-core element kernel (k_elem_q2hex_mfma): reference gradients T[q][c][n] (q-stride 85, c-stride 28, zero padded) and
-  // shape values Phi[q][n] (stride 33)
-  double *d_mfT = nullptr, *d_mfPhi = nullptr;
-  double* d_mfSFc = nullptr;     // sum-factorised map Jacobian: per-lane 1-D shape values [18][64] (null: tables are not tensor products)
-  int* d_mfSFi = nullptr;        // ... and per-lane LDS offsets [7][64]
-  // sum-factorised element kernel (k_elem_q2hex_sf): 1-D basis values (uniform operands) and the per-lane tables
-  SfTab sf_tab;
-  double* d_sfLc = nullptr;      // [SF_NLC][64]
-  int* d_sfLi = nullptr;         // [SF_NLI][64]
-  // source term given as a compiled expression (fh_expr): device copy of the program of the expression last used
-  int* d_prog = nullptr;
-  double* d_prog_consts = nullptr;
-  int nprog = 0;
-  std::vector<int> h_prog;
-  std::vector<double> h_prog_consts;
-};
 
 struct AsmParams {
   const int* elems;        // element ids of this launch
@@ -643,12 +566,6 @@ static int dispatch_rows(fh_assembler_t as, fh_mat_t A, double* res, bool build)
 //   phase 2  lane < 28 of each half: one upper tile, 16 FMA per 8 LDS doubles (2+2 ds_read_b128)
 // Waves are independent (own LDS slab, wave-level barriers only); one wave per workgroup.
 // ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 template <int SRC>
 __global__ __launch_bounds__(64) void k_elem_q2hex_sym(AsmParams P) {
   constexpr int NC = 27, NCP = 28, DIM = 3, GC = 8, NPP = 7;
@@ -1281,19 +1198,6 @@ __device__ __forceinline__ void sf_ld4(const double* p, double v[4]) {
 
 // Phases A and stages 1-3 of the sum-factorised element matrix (shared by k_elem_q2hex_sf and the cluster kernel k_cluster_q2hex_sf): from the
 // element's nodes in xt (tensor order) to this lane's 3 x 3 block Kb over (a, a') and its source entry fsrc.  R is the wave's scratch region.
-// phase stamps of the instrumented build of the cluster kernel (asm_debug bit 7): shader clock at the phase boundaries, summed per wave in scalar registers
-struct SfStamps {
-  unsigned long long prev, acc[16];
-};
-template <bool INS>
-__device__ __forceinline__ void sf_stamp(SfStamps& st, const int k) {
-  if (INS) {
-    const unsigned long long t = __builtin_amdgcn_s_memtime();
-    st.acc[k] += t - st.prev;
-    st.prev = t;
-  }
-}
-
 // lane l of tabv holds entry l of the 1-D table {L[3][4], D[3][4]} (sf_tab_lanes); a uniform entry is fetched with two v_readlane.  Keeping the 24 doubles
 // in scalar registers instead (the kernel argument) left the unrolled stages 2-3 with scalar spills.
 __device__ __forceinline__ double sf_tab_lanes(const SfTab& tab, const int lane) {
@@ -1859,11 +1763,7 @@ static int launch_sf(fh_assembler_t as, const AsmParams& P, int nw) {
 // Addresses inside the workgroup's LDS are 14-bit double indices; a descriptor holds the first address, the second (or the index of a
 // zero cell) and, for the 49 entries with four or eight contributions, the start of an overflow list.
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int CL_NE = 8;                         // elements per cluster = waves per workgroup
-constexpr int CL_T = CL_NE * 64;                 // threads
-constexpr int CL_SPT = 10;                       // slots (macro entries) per thread
 constexpr int CL_NS_MAX = CL_T * CL_SPT;         // 5120 >= 4913
-constexpr int CL_NM_MAX = 128;                   // macro nodes (125), padded
 constexpr int CL_NBLK = 128;                     // address blocks of the entries with more than two contributions (49 used; one per lane 16 .. 31 of the eight waves)
 // LDS of the cluster kernel (doubles): the per-lane tables it reads from LDS -- rows CL_LC0 .. SF_NLC - 1 of the constants (the others live in registers) and
 // the integer rows --, the eight wave regions (xt + R), a zero cell (operand of absent contributions)
@@ -3610,10 +3510,9 @@ extern "C" int fh_assembler_destroy(fh_assembler_t as) {
   for (void* q : {(void*)as->d_cl_dtab, (void*)as->d_cl_fblk, (void*)as->d_cl_sinfo, (void*)as->d_cl_oblk, (void*)as->d_cl_gtab, (void*)as->d_cl_vdst, (void*)as->d_cl_vdst64, (void*)as->d_cl_fdst, (void*)as->d_cl_map, (void*)as->d_cl_pmap,
                   (void*)as->d_Pbuf, (void*)as->d_geo, (void*)as->d_cl_prow, (void*)as->d_cl_pstart})
     if (q) hipFree(q);
-  for (void* q : {(void*)as->d_adj_ptr, (void*)as->d_adj_ei, (void*)as->d_rowmap, (void*)as->d_Kbuf, (void*)as->d_Fbuf, (void*)as->d_slot, (void*)as->d_gal_child,
-                  (void*)as->d_gal_cnt, (void*)as->d_gal_row, (void*)as->d_gal_fb, (void*)as->d_gal_cb, (void*)as->d_gal_val, (void*)as->d_gal_res, (void*)as->d_gal_dense,
-                  (void*)as->d_gal_fmask})
+  for (void* q : {(void*)as->d_adj_ptr, (void*)as->d_adj_ei, (void*)as->d_rowmap, (void*)as->d_Kbuf, (void*)as->d_Fbuf, (void*)as->d_slot})
     if (q) hipFree(q);
+  as->gal.release();
   delete as;
   return 0;
 }
@@ -3767,6 +3666,50 @@ static int assemble_poisson_core(fh_assembler_t as, fh_vec_t sol, int source_kin
   return 0;
 }
 
+// element rows of the last assembly into the element-row buffer (pass 1 of the two-pass path alone)
+static int element_rows_again(fh_assembler_t as) {
+  FH_REQUIRE(as->two_pass && as->d_Kbuf, "fh_assembler_galerkin: the fine assembler holds no element rows");
+  AsmParams P = base_params(as);
+  P.sol = nullptr;          // only K_e is needed (the Poisson element matrix does not depend on the solution); the vector of that assembly may be gone by now
+  P.source_kind = as->last_source_kind;
+  P.p0 = as->last_params[0];
+  P.p1 = as->last_params[1];
+  P.elems = as->d_iota;
+  P.nelems = as->nel;
+  P.Kout = as->d_Kbuf;
+  P.kstride = as->kstride;
+  P.Fout = as->d_Fbuf;
+  P.slot = as->d_slot;
+  P.nsink = as->nadj;
+  FH_TRY(dispatch_assemble(as, P));
+  as->kbuf_valid = true;
+  return 0;
+}
+
+// ---- what the element-wise Galerkin product (fh_galerkin.hip) sees of the state assemble_poisson_core leaves behind (declared in fh_assembler.h) ----
+int fh_assembler_row_pass(fh_assembler_t as, fh_mat_t A, double* res) { return dispatch_rows(as, A, res, false); }
+
+int fh_assembler_need_element_rows(fh_assembler_t as) {
+  as->rows_used_since = true;                              // (the next assembly of this level keeps its element rows)
+  if (!as->kbuf_valid) FH_TRY(element_rows_again(as));      // the fused assembly kept no element rows: pass 1 of the two-pass path with the last arguments
+  return 0;
+}
+
+void fh_assembler_rows_replaced(fh_assembler_t as) {
+  as->kbuf_valid = true;      // the element rows a product wrote (the next coarser product reads them)
+  as->macro_valid = false;    // ... and not the macro rows an earlier fused assembly of this level may have left in its matrix: the product has overwritten it
+}
+
+// The macro rows live in the user-visible matrix of the assembly: any writer of its values since the assembly other than the Dirichlet-row replacement -- a
+// scaling, an in-place product, staged adds -- ends their validity (val_gen), and so does the destruction of that matrix: they are read through addresses,
+// which must still be the ones of a live matrix with the assembly's values.
+MacroRows fh_assembler_macro_rows(fh_assembler_t as) {
+  if (!(as->fused && as->last_path == 1 && as->macro_valid && as->cl_all_rows && as->d_cl_gtab)) return {};
+  const fh_mat_t mat = fh_mat_alive(as->macro_uid);
+  if (!mat || mat->d_val != as->cl_val_base || mat->val_gen != as->macro_val_gen) return {};
+  return {true, as->cl_nm, as->cl_ncl, as->d_cl_sinfo, reinterpret_cast<const uint4*>(as->d_cl_map), as->d_cl_vdst64, as->d_cl_gtab};
+}
+
 extern "C" int fh_element_matrices_poisson(fh_assembler_t as, fh_vec_t sol, int source_kind, const double* params, double* K, double* F) {
   FH_REQUIRE(as && K && F, "fh_element_matrices_poisson: null argument");
   const size_t nk = (size_t)as->nel * as->nc * as->nc, nf = (size_t)as->nel * as->nc;
@@ -3850,651 +3793,4 @@ extern "C" int fh_assembler_info(fh_assembler_t as, int* ncolors, int64_t* algor
   if (flops)
     *flops = (double)as->nel * ng * (nc * dim * dim * 2.0 + 60.0 + nc * dim * dim * 2.0 + (double)nc * nc * (dim * 2.0 + 2.0) + nc * 10.0);
   return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Galerkin coarse operator ELEMENT BY ELEMENT (uniform refinement): A = sum_e K_e and every fine element lies in one coarse element, whose
-// 27 (9) nodes interpolate its nodes by the fixed child matrix C_j (the rows of the element prolongator, ElemType.cpp:439-532), so
-//   PP^T KK PP = sum_E sum_{children j of E} C_j^T K_{child j} C_j          (LinearImplicitSystem.cpp:347-370, PetscMatrix.cpp:733-751)
-// -- coarse ELEMENT matrices from the fine ones the assembler still holds, then the same row pass as the assembly.  The general sparse triple
-// product streams ~10 elementary products per non-zero (8 ms on the 64^3 level); this reads the element-row buffer once (1.8 GB) and does
-// 7 k multiply-adds per child with the 125 non-zeros of C_j.  Rows of the interpolation at fine Dirichlet nodes and its columns at coarse
-// Dirichlet nodes are zero (ZeroInterpolatorDirichletNodes, :1032-1120): masks on K_j and on the result.  Same value as the product up to
-// the order of the sums.  One wave per coarse element.
-// ------------------------------------------------------------------------------------------------------------------
-template <int NC, int NCH>
-__global__ __launch_bounds__(256) void k_galerkin_elem(int nelc, const int* __restrict__ child, const int* __restrict__ slot_f, const double* __restrict__ Kf, int ks_f,
-                                                       const int* __restrict__ edof_f, int nloc_f, const unsigned char* __restrict__ fb,
-                                                       const int* __restrict__ slot_c, double* __restrict__ Kc, int ks_c, const int* __restrict__ edof_c, int nloc_c,
-                                                       const unsigned char* __restrict__ cb, const unsigned char* __restrict__ tab_cnt,
-                                                       const unsigned char* __restrict__ tab_row, const double* __restrict__ tab_val) {
-  constexpr int NE = NC * NC, NT = (NE + 63) / 64, LD = NC + 1;
-  __shared__ double cval[NCH * NC * 8];
-  __shared__ unsigned char crow[NCH * NC * 8], ccnt[NCH * NC];
-  __shared__ double slab[4][2][NC * LD];
-  for (int k = threadIdx.x; k < NCH * NC * 8; k += 256) { cval[k] = tab_val[k]; crow[k] = tab_row[k]; }
-  for (int k = threadIdx.x; k < NCH * NC; k += 256) ccnt[k] = tab_cnt[k];
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double* Ks = slab[wave][0];
-  double* Ts = slab[wave][1];
-  for (int E = blockIdx.x * 4 + wave; E < nelc; E += gridDim.x * 4) {
-    double acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; t++) acc[t] = 0.0;
-    for (int j = 0; j < NCH; j++) {
-      const int ej = child[(size_t)E * NCH + j];
-      // all gathers of the child first (independent chains in flight), then the LDS writes
-      double kin[NT];
-#pragma unroll
-      for (int t = 0; t < NT; t++) {
-        const int idx = min(lane + 64 * t, NE - 1);
-        const int i = idx / NC, c = idx - i * NC;
-        const int s = slot_f[(size_t)ej * NC + i];
-        const bool dead = s < 0 || fb[edof_f[(size_t)ej * nloc_f + i]] || fb[edof_f[(size_t)ej * nloc_f + c]];
-        kin[t] = dead ? 0.0 : Kf[(size_t)max(s, 0) * ks_f + c];
-      }
-#pragma unroll
-      for (int t = 0; t < NT; t++) {
-        const int idx = lane + 64 * t;
-        if (idx < NE) Ks[(idx / NC) * LD + idx % NC] = kin[t];
-      }
-      wave_lds_sync();
-      // T = K_j C_j and K_E += C_j^T T: the (at most 8) non-zeros of a column of C_j, padded with zero weights -- a fixed trip count and
-      // NT independent chains per lane instead of one serial chain of dependent LDS reads per entry
-      {
-        double tv[NT];
-        int rbase[NT], cbase[NT];
-#pragma unroll
-        for (int t = 0; t < NT; t++) {
-          const int idx = min(lane + 64 * t, NE - 1);
-          rbase[t] = (idx / NC) * LD;
-          cbase[t] = (j * NC + idx % NC) * 8;
-          tv[t] = 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; q++)
-#pragma unroll
-          for (int t = 0; t < NT; t++) tv[t] += Ks[rbase[t] + crow[cbase[t] + q]] * cval[cbase[t] + q];
-#pragma unroll
-        for (int t = 0; t < NT; t++) {
-          const int idx = lane + 64 * t;
-          if (idx < NE) Ts[(idx / NC) * LD + idx % NC] = tv[t];
-        }
-      }
-      wave_lds_sync();
-      {
-        int kcol[NT], abase[NT];
-#pragma unroll
-        for (int t = 0; t < NT; t++) {
-          const int idx = min(lane + 64 * t, NE - 1);
-          kcol[t] = idx % NC;
-          abase[t] = (j * NC + idx / NC) * 8;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; q++)
-#pragma unroll
-          for (int t = 0; t < NT; t++) acc[t] += cval[abase[t] + q] * Ts[crow[abase[t] + q] * LD + kcol[t]];
-      }
-      wave_lds_sync();
-    }
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-      const int idx = lane + 64 * t;
-      if (idx < NE) {
-        const int a = idx / NC, k = idx - a * NC;
-        const int s = slot_c[(size_t)E * NC + a];
-        if (s >= 0) {
-          const bool dead = cb[edof_c[(size_t)E * nloc_c + a]] || cb[edof_c[(size_t)E * nloc_c + k]];
-          Kc[(size_t)s * ks_c + k] = dead ? 0.0 : acc[t];
-        }
-      }
-    }
-  }
-}
-
-// The same on the FP64 matrix cores (default): per child two small dense products T = K_j C_j and K_E += C_j^T T as v_mfma_f64_16x16x4 tiles
-// (27 -> 32 x 32 x 28 padded: 2 x 28 instructions of 64 cycles), operands from LDS (the eight C_j, the gathered K_j, T), the element rows of
-// the NEXT child gathered into registers while the current one is multiplied.  One wave per coarse element, one workgroup of four per CU.
-// waves per workgroup: they share the child matrices C_j in LDS; the per-wave scratch holds K_j first and T = K_j C_j afterwards (one region), so that
-// eight waves -- two per SIMD, one's LDS round trips behind the other's matrix instructions -- fit beside the 57 KB of C
-constexpr int GAL_NW = 8;
-template <int NC, int NCH>
-__global__ __launch_bounds__(GAL_NW * 64) void k_galerkin_mfma(int nelc, const int* __restrict__ child, const int* __restrict__ slot_f, const double* __restrict__ Kf, int ks_f,
-                                                       const int* __restrict__ edof_f, int nloc_f, const unsigned char* __restrict__ fb,
-                                                       const int* __restrict__ slot_c, double* __restrict__ Kc, int ks_c, const int* __restrict__ edof_c, int nloc_c,
-                                                       const unsigned char* __restrict__ cb, const double* __restrict__ Cdense /* [NCH][NC][NC] */) {
-  constexpr int NE = NC * NC, NT = (NE + 63) / 64, MT = (NC + 15) / 16, KP = (NC + 3) / 4 * 4, CLD = MT * 16, KLD = KP + 1, TLD = MT * 16;
-  extern __shared__ __attribute__((aligned(16))) double gm_smem[];
-  double* Cs = gm_smem;                                   // [NCH][KP][CLD], zero padded
-  for (int k = threadIdx.x; k < NCH * KP * CLD; k += GAL_NW * 64) {
-    const int j = k / (KP * CLD), r = (k / CLD) % KP, c = k % CLD;
-    Cs[k] = (r < NC && c < NC) ? Cdense[(j * NC + r) * NC + c] : 0.0;
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  constexpr int WS = (MT * 16 * KLD > KP * TLD) ? MT * 16 * KLD : KP * TLD;    // doubles of scratch per wave
-  double* Ks = Cs + NCH * KP * CLD + wave * WS;      // [MT*16][KLD]
-  double* Ts = Ks;                                    // [KP][TLD]: the same region, after K_j has been consumed
-  __syncthreads();
-  const int kk = lane >> 4, li = lane & 15;
-  typedef double d4 __attribute__((ext_vector_type(4)));
-  for (int E = blockIdx.x * GAL_NW + wave; E < nelc; E += gridDim.x * GAL_NW) {
-    d4 KE[MT][MT];
-#pragma unroll
-    for (int a = 0; a < MT; a++)
-#pragma unroll
-      for (int b = 0; b < MT; b++) KE[a][b] = d4{0.0, 0.0, 0.0, 0.0};
-    double kin[NT];
-    auto gather = [&](int j) {      // K_j with the rows / columns of Dirichlet nodes zeroed (kept in registers until the LDS is free)
-      const int ej = child[(size_t)E * NCH + j];
-      const int ln = min(lane, NC - 1);
-      const int sl = slot_f[(size_t)ej * NC + ln];
-      const bool dn = sl < 0 || fb[edof_f[(size_t)ej * nloc_f + ln]];
-      const unsigned long long dead = __ballot(dn && lane < NC);
-#pragma unroll
-      for (int t = 0; t < NT; t++) {
-        const int idx = min(lane + 64 * t, NE - 1);
-        const int i = idx / NC, c = idx - i * NC;
-        const int s = __shfl(sl, i, 64);
-        const bool d = ((dead >> i) | (dead >> c)) & 1ull;
-        kin[t] = d ? 0.0 : Kf[(size_t)max(s, 0) * ks_f + c];
-      }
-    };
-    gather(0);
-    for (int j = 0; j < NCH; j++) {
-#pragma unroll
-      for (int t = 0; t < NT; t++) {
-        const int idx = lane + 64 * t;
-        if (idx < NE) Ks[(idx / NC) * KLD + idx % NC] = kin[t];
-      }
-      // the padding of K_j (rows and columns NC .. of the operand tile) is zero: T of the previous child lived here
-      for (int q = lane; q < (MT * 16 - NC) * KLD; q += 64) Ks[NC * KLD + q] = 0.0;
-      for (int q = lane; q < NC * (KLD - NC); q += 64) Ks[(q / (KLD - NC)) * KLD + NC + q % (KLD - NC)] = 0.0;
-      wave_lds_sync();
-      if (j + 1 < NCH) gather(j + 1);
-      const double* Cj = Cs + j * KP * CLD;
-      d4 T[MT][MT];
-#pragma unroll
-      for (int a = 0; a < MT; a++)
-#pragma unroll
-        for (int b = 0; b < MT; b++) T[a][b] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int k0 = 0; k0 < KP; k0 += 4) {
-        double av[MT], bv[MT];
-#pragma unroll
-        for (int x = 0; x < MT; x++) {
-          av[x] = Ks[(x * 16 + li) * KLD + k0 + kk];
-          bv[x] = Cj[(k0 + kk) * CLD + x * 16 + li];
-        }
-#pragma unroll
-        for (int a = 0; a < MT; a++)
-#pragma unroll
-          for (int b = 0; b < MT; b++) T[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a], bv[b], T[a][b], 0, 0, 0);
-      }
-      wave_lds_sync();                       // every lane has read its operands of K_j: T may take the region
-#pragma unroll
-      for (int a = 0; a < MT; a++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const int i = a * 16 + kk + 4 * r;
-          if (i < KP) {
-#pragma unroll
-            for (int b = 0; b < MT; b++) Ts[i * TLD + b * 16 + li] = T[a][b][r];
-          }
-        }
-      wave_lds_sync();
-#pragma unroll
-      for (int k0 = 0; k0 < KP; k0 += 4) {
-        double av[MT], bv[MT];
-#pragma unroll
-        for (int x = 0; x < MT; x++) {
-          av[x] = Cj[(k0 + kk) * CLD + x * 16 + li];        // A[row a][k i] = C_j[i][a]
-          bv[x] = Ts[(k0 + kk) * TLD + x * 16 + li];
-        }
-#pragma unroll
-        for (int a = 0; a < MT; a++)
-#pragma unroll
-          for (int b = 0; b < MT; b++) KE[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a], bv[b], KE[a][b], 0, 0, 0);
-      }
-      wave_lds_sync();
-    }
-    // rows / columns of coarse Dirichlet nodes are zero; rows without a slot are not stored
-    const int ln = min(lane, NC - 1);
-    const int slc = slot_c[(size_t)E * NC + ln];
-    const unsigned long long cdead = __ballot(lane < NC && cb[edof_c[(size_t)E * nloc_c + ln]]);
-#pragma unroll
-    for (int a = 0; a < MT; a++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int ra = a * 16 + kk + 4 * r;
-        const int s = __shfl(slc, min(ra, NC - 1), 64);
-#pragma unroll
-        for (int b = 0; b < MT; b++) {
-          const int k = b * 16 + li;
-          if (ra < NC && k < NC && s >= 0) {
-            const bool d = ((cdead >> ra) | (cdead >> k)) & 1ull;
-            Kc[(size_t)s * ks_c + k] = d ? 0.0 : KE[a][b][r];
-          }
-        }
-      }
-  }
-}
-
-template <int NC, int NCH>
-static size_t galerkin_mfma_lds() {
-  constexpr int MT = (NC + 15) / 16, KP = (NC + 3) / 4 * 4;
-  const size_t ws = std::max((size_t)MT * 16 * (KP + 1), (size_t)KP * MT * 16);
-  return ((size_t)NCH * KP * MT * 16 + GAL_NW * ws) * sizeof(double);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Element-wise Galerkin product FROM THE MACRO ROWS of a fused assembly (round 5).  The fused path keeps no element rows; what it leaves behind per cluster
-// (= per coarse element) is the 125 x 125 macro matrix K_m = sum_j S_j^T K_j S_j: complete rows in the CSR array, the others as packed rows in the
-// partial-row buffer, 4913 entries at the addresses the cluster kernel stored them to.  With C (125 x 27) the interpolation from the coarse element,
-// K_E = C^T K_m C = sum_j C_j^T K~_j C_j for ANY split of the macro entries over the children (K~_j = the entries child j owns: an entry met by several
-// children belongs to the first, table gtab).  One workgroup of eight waves per coarse element: all threads read the 4913 entries back (the loads of the
-// NEXT cluster fly during the products) into a template-ordered LDS array, wave j forms K~_j from it and runs the two 32 x 32 x 28 products of
-// k_galerkin_mfma on the matrix cores, the eight results are added in child order and leave as coarse element rows.  39 kB read per coarse element instead
-// of 55 kB, and the fused assembly stays the path of every assembly of a solve (LinearImplicitSystem.cpp:288-411: assemble -> Galerkin -> solve, every time).
-// Between the assembly and this product only Dirichlet ROWS of the fine matrix may have been replaced (SetPenalty): they are masked here anyway.
-// ------------------------------------------------------------------------------------------------------------------
-constexpr int GMAC_NW = 8, GMAC_T = GMAC_NW * 64;
-constexpr int GMAC_KP = 28;                                             // K of the two products, padded to the matrix instruction's 4
-constexpr int GMAC_TN = 4928;                                           // template entries (4913), padded
-constexpr int GMAC_RS = 27 * 28;                                        // one wave's result [27][28]
-constexpr int GMAC_BUF = GMAC_NW * GMAC_RS > GMAC_TN ? GMAC_NW * GMAC_RS : GMAC_TN;      // the macro matrix, then the eight results (same region)
-constexpr size_t gmac_lds_bytes() { return (size_t)GMAC_BUF * sizeof(double) + CL_NM_MAX * sizeof(unsigned long long) + 32 * sizeof(int); }
-static_assert(gmac_lds_bytes() <= 160 * 1024, "k_galerkin_macro: LDS budget");
-
-// Operands in registers (second form of the round; the first staged K~_j, C_j and T through LDS like k_galerkin_mfma and took 1.0 ms against that kernel's
-// 0.86): wave j always serves child j, so its fragments of C_j -- B operand of T = K~_j C_j AND A operand of R = C_j^T T, the same values -- and the
-// template indices of its K~_j fragments are loop invariant (14 doubles + 14 indices per lane); T leaves the first product in exactly the lanes the second
-// product wants it as B operand (row 4 m + kk of T = accumulator m / 4, register m % 4 of lane (kk, li)): no LDS round trip between the two products.
-// Dirichlet masks of the children's and of the coarse element's 27 nodes (bit = local node), once per hierarchy: the product kernel then needs no chain
-// of dependent look-ups (children -> element dofs -> flags) per cluster
-__global__ __launch_bounds__(256) void k_gal_masks(int nelc, const int* __restrict__ child, const int* __restrict__ edof_f, int nloc_f, const unsigned char* __restrict__ fb,
-                                                    const int* __restrict__ edof_c, int nloc_c, const unsigned char* __restrict__ cb, unsigned* __restrict__ fmask,
-                                                    unsigned* __restrict__ cmask) {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= nelc * 9) return;
-  const int E = k / 9, j = k % 9;
-  unsigned m = 0;
-  if (j < 8) {
-    const int ej = child[(size_t)E * 8 + j];
-    for (int n = 0; n < 27; n++) m |= (fb[edof_f[(size_t)ej * nloc_f + n]] ? 1u : 0u) << n;
-    fmask[(size_t)E * 8 + j] = m;
-  } else {
-    for (int n = 0; n < 27; n++) m |= (cb[edof_c[(size_t)E * nloc_c + n]] ? 1u : 0u) << n;
-    cmask[E] = m;
-  }
-}
-
-template <bool INS>
-__global__ __launch_bounds__(GMAC_T) void k_galerkin_macro(int nelc, const int* __restrict__ child, int nm, const unsigned* __restrict__ sinfo, const uint4* __restrict__ map,
-                                                           const unsigned long long* __restrict__ vdst, const unsigned short* __restrict__ gtab,
-                                                           const unsigned* __restrict__ fmask, const unsigned* __restrict__ cmask,
-                                                           const int* __restrict__ slot_c, double* __restrict__ Kc, int ks_c, const double* __restrict__ Cdense /* [8][27][27] */,
-                                                           unsigned long long* __restrict__ stamps) {
-  constexpr int NC = 27, NCH = 8, NE = NC * NC, MT = 2, NK = GMAC_KP / 4;
-  SfStamps st;
-  if (INS) {
-#pragma unroll
-    for (int k = 0; k < 16; k++) st.acc[k] = 0;
-  }
-  extern __shared__ __attribute__((aligned(16))) double gmac_smem[];
-  double* Tm = gmac_smem;                                 // the macro matrix in template order; behind the products: the eight results
-  unsigned long long* rbl = reinterpret_cast<unsigned long long*>(gmac_smem + GMAC_BUF);
-  int* slds = reinterpret_cast<int*>(rbl + CL_NM_MAX);    // slots of the coarse element's 27 rows
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int kk = lane >> 4, li = lane & 15;
-  unsigned si[CL_SPT];
-#pragma unroll
-  for (int i = 0; i < CL_SPT; i++) si[i] = sinfo[i * CL_T + tid];
-  // loop-invariant fragments of child `wave`: C_j[4 m + kk][16 x + li] and the template index of K~_j[16 x + li][4 m + kk]
-  double creg[NK][MT];
-  int gidx[NK][MT];
-#pragma unroll
-  for (int m = 0; m < NK; m++)
-#pragma unroll
-    for (int x = 0; x < MT; x++) {
-      const int r = 4 * m + kk, c = x * 16 + li;
-      creg[m][x] = (r < NC && c < NC) ? Cdense[((size_t)wave * NC + r) * NC + c] : 0.0;
-      const unsigned short g = (c < NC && r < NC) ? gtab[(size_t)wave * NE + c * NC + r] : (unsigned short)0xffff;
-      gidx[m][x] = g == 0xffff ? -1 : (int)g;
-    }
-  typedef double d4 __attribute__((ext_vector_type(4)));
-  const int stride = gridDim.x;
-  int E = blockIdx.x;
-  if (E >= nelc) return;
-  // pipeline: values of cluster n in registers (tv), map / destinations of cluster n + 1 in registers (mp, vd)
-  const int tm = tid & (CL_NM_MAX - 1);
-  int cl = child[(size_t)E * NCH] >> 3;
-  if (tid < CL_NM_MAX) rbl[tid] = vdst[(size_t)cl * CL_NM_MAX + tm];
-  uint4 mp = map[(size_t)cl * CL_T + tid];
-  __syncthreads();
-  double tv[CL_SPT];
-  // where slot i of a cluster's macro matrix is read: position p of the row (complete / partial rows), or -- a row carried in the CSR array across the clusters of a
-  // super-cluster (class bit 10 + i of word 3) -- the CSR position the map byte names, and only in the cluster that made the LAST contribution (bit i of word 3
-  // clear; the entry holds the sum of all of them there; the pseudo child matrices still add up to the assembled matrix, which is all the coarse operator depends
-  // on); -1: nothing to read
-  auto slot_pos = [&](const uint4& q4, int i) {
-    const unsigned mq[4] = {q4.x, q4.y, q4.z, q4.w};
-    const int r = si[i] & 127, p = (si[i] >> 7) & 127;
-    if (r >= nm) return -1;
-    if ((mq[3] >> i) & 1u) return -1;
-    return ((mq[3] >> (10 + i)) & 1u) ? (int)((mq[i >> 2] >> (8 * (i & 3))) & 255) : p;
-  };
-#pragma unroll
-  for (int i = 0; i < CL_SPT; i++) {
-    const int r = si[i] & 127, pos = slot_pos(mp, i);
-    tv[i] = pos >= 0 ? reinterpret_cast<const double*>(rbl[r])[pos] : 0.0;
-  }
-  int En = min(E + stride, nelc - 1);
-  int cln = child[(size_t)En * NCH] >> 3;
-  unsigned long long vdn = vdst[(size_t)cln * CL_NM_MAX + tm];
-  uint4 mpn = map[(size_t)cln * CL_T + tid];
-  const int ln = min(lane, NC - 1);
-  unsigned dmask = fmask[(size_t)E * NCH + wave], cdm = cmask[E];      // Dirichlet nodes of this wave's child / of the coarse element (k_gal_masks)
-  int slc = slot_c[(size_t)E * NC + ln];
-  if (INS) st.prev = __builtin_amdgcn_s_memtime();
-  int ndone = 0;
-#pragma unroll 1
-  for (; E < nelc; E += stride) {
-    sf_stamp<INS>(st, 0);
-    // ---- the macro matrix of this cluster into LDS (template order); destinations of the next cluster into rbl ----
-    {
-      const unsigned mw[4] = {mp.x, mp.y, mp.z, mp.w};
-#pragma unroll
-      for (int i = 0; i < CL_SPT; i++) {
-        const int r = si[i] & 127, mb = (mw[i >> 2] >> (8 * (i & 3))) & 255;
-        const int j = ((mw[3] >> (10 + i)) & 1u) ? (int)((si[i] >> 7) & 127) : mb;      // carried row: the entry is p
-        if (r < nm) Tm[(si[i] >> 14) + j] = tv[i];
-      }
-    }
-    if (tid < CL_NM_MAX) rbl[tid] = vdn;      // (the loads through the previous content were issued one iteration ago and have landed in tv)
-    if (tid < NC) slds[tid] = slc;
-    sf_stamp<INS>(st, 1);
-    __syncthreads();
-    sf_stamp<INS>(st, 2);
-    // the NEXT cluster's values: in flight during the products below
-    mp = mpn;
-#pragma unroll
-    for (int i = 0; i < CL_SPT; i++) {
-      const int r = si[i] & 127, pos = slot_pos(mp, i);
-      tv[i] = pos >= 0 ? reinterpret_cast<const double*>(rbl[r])[pos] : 0.0;
-    }
-    {
-      const int Enn = min(E + 2 * stride, nelc - 1);
-      const int clnn = child[(size_t)Enn * NCH] >> 3;
-      vdn = vdst[(size_t)clnn * CL_NM_MAX + tm];
-      mpn = map[(size_t)clnn * CL_T + tid];
-    }
-    const unsigned long long cdead = cdm, dead = dmask;
-    {   // the next element's masks and slots (consumed one iteration later)
-      const int En1 = min(E + stride, nelc - 1);
-      dmask = fmask[(size_t)En1 * NCH + wave];
-      cdm = cmask[En1];
-      slc = slot_c[(size_t)En1 * NC + ln];
-    }
-    sf_stamp<INS>(st, 3);
-    // ---- wave j: T = K~_j C_j (A operand gathered from the macro matrix, rows / columns of Dirichlet nodes zeroed), R_j = C_j^T T ----
-    d4 T[MT][MT], KE[MT][MT];
-#pragma unroll
-    for (int a = 0; a < MT; a++)
-#pragma unroll
-      for (int b = 0; b < MT; b++) { T[a][b] = d4{0.0, 0.0, 0.0, 0.0}; KE[a][b] = d4{0.0, 0.0, 0.0, 0.0}; }
-    {
-      double av[2][MT];                      // fragments of K~_j, one k-step ahead of the products
-      auto gather = [&](int m, double (&o)[MT]) {
-#pragma unroll
-        for (int x = 0; x < MT; x++) {
-          const int row = x * 16 + li, col = 4 * m + kk;
-          const bool d = gidx[m][x] < 0 || (((dead >> min(row, 63)) | (dead >> min(col, 63))) & 1ull);
-          const double v = Tm[max(gidx[m][x], 0)];
-          o[x] = d ? 0.0 : v;
-        }
-      };
-      gather(0, av[0]);
-#pragma unroll
-      for (int m = 0; m < NK; m++) {
-        if (m + 1 < NK) gather(m + 1, av[(m + 1) & 1]);
-#pragma unroll
-        for (int a = 0; a < MT; a++)
-#pragma unroll
-          for (int b = 0; b < MT; b++) T[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[m & 1][a], creg[m][b], T[a][b], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < NK; m++)
-#pragma unroll
-      for (int a = 0; a < MT; a++)
-#pragma unroll
-        for (int b = 0; b < MT; b++) KE[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(creg[m][a], T[m / 4][b][m % 4], KE[a][b], 0, 0, 0);
-    if (INS) {
-      asm volatile("" ::"v"(KE[0][0][0]), "v"(KE[1][1][3]));
-      sf_stamp<INS>(st, 4);
-    }
-    __syncthreads();                       // every wave is done with the macro matrix: the results take the region
-    sf_stamp<INS>(st, 5);
-    {
-      double* Rs = Tm + wave * GMAC_RS;
-#pragma unroll
-      for (int a = 0; a < MT; a++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const int ra = a * 16 + kk + 4 * r;
-#pragma unroll
-          for (int b = 0; b < MT; b++) {
-            const int k = b * 16 + li;
-            if (ra < NC && k < NC) Rs[ra * 28 + k] = KE[a][b][r];
-          }
-        }
-    }
-    sf_stamp<INS>(st, 6);
-    __syncthreads();
-    sf_stamp<INS>(st, 7);
-    // ---- the eight results added in child order; rows / columns of coarse Dirichlet nodes are zero; rows without a slot are not stored ----
-    for (int idx = tid; idx < NE; idx += GMAC_T) {
-      const int i = idx / NC, k = idx - i * NC;
-      double v = Tm[i * 28 + k];
-#pragma unroll
-      for (int w = 1; w < GMAC_NW; w++) v += Tm[w * GMAC_RS + i * 28 + k];
-      const int s2 = slds[i];
-      const bool d = ((cdead >> i) | (cdead >> k)) & 1ull;
-      if (s2 >= 0) Kc[(size_t)s2 * ks_c + k] = d ? 0.0 : v;
-    }
-    sf_stamp<INS>(st, 8);
-    __syncthreads();                       // the region is the next cluster's macro matrix
-    sf_stamp<INS>(st, 9);
-    ndone++;
-  }
-  if (INS && stamps && lane == 0) {
-    unsigned long long* o = stamps + ((size_t)blockIdx.x * GMAC_NW + wave) * 20;
-#pragma unroll
-    for (int k = 0; k < 16; k++) o[k] = st.acc[k];
-    o[16] = (unsigned long long)ndone;
-  }
-}
-
-// element rows of the last assembly into the element-row buffer (pass 1 of the two-pass path alone)
-static int element_rows_again(fh_assembler_t as) {
-  FH_REQUIRE(as->two_pass && as->d_Kbuf, "fh_assembler_galerkin: the fine assembler holds no element rows");
-  AsmParams P = base_params(as);
-  P.sol = nullptr;          // only K_e is needed (the Poisson element matrix does not depend on the solution); the vector of that assembly may be gone by now
-  P.source_kind = as->last_source_kind;
-  P.p0 = as->last_params[0];
-  P.p1 = as->last_params[1];
-  P.elems = as->d_iota;
-  P.nelems = as->nel;
-  P.Kout = as->d_Kbuf;
-  P.kstride = as->kstride;
-  P.Fout = as->d_Fbuf;
-  P.slot = as->d_slot;
-  P.nsink = as->nadj;
-  FH_TRY(dispatch_assemble(as, P));
-  as->kbuf_valid = true;
-  return 0;
-}
-
-extern "C" int fh_assembler_galerkin(fh_assembler_t fas, fh_assembler_t cas, const int* child, int nfb, const int* fbdc, int ncb, const int* cbdc, fh_mat_t Ac) {
-  FH_GUARD_BEGIN
-  FH_REQUIRE(fas && cas && child && Ac && (nfb == 0 || fbdc) && (ncb == 0 || cbdc), "fh_assembler_galerkin: null argument");
-  FH_REQUIRE(fas->two_pass && cas->two_pass && fas->nc == cas->nc && fas->geom == cas->geom && (fas->nc == 27 || fas->nc == 9),
-             "fh_assembler_galerkin: both levels need the two-pass biquadratic assembler");
-  const int nch = fhfe::nvert_of(cas->geom), nc = cas->nc;
-  FH_REQUIRE(fas->nel == cas->nel * nch, "fh_assembler_galerkin: %d fine elements are not the uniform refinement of %d coarse ones", fas->nel, cas->nel);
-  FH_REQUIRE(Ac->m == cas->ndof, "fh_assembler_galerkin: the coarse matrix does not belong to the coarse assembler");
-  fh_ctx_t c = cas->ctx;
-  auto up = [&](void** d, const void* h, size_t bytes) -> int {
-    if (*d) FH_CHECK_HIP(hipFree(*d));
-    FH_CHECK_HIP(hipMalloc(d, bytes ? bytes : 8));
-    if (bytes) FH_CHECK_HIP(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
-    return 0;
-  };
-  // integer / table set-up, once per hierarchy -- and again when the children or the Dirichlet sets differ from the ones the tables were made from
-  uint64_t key = 1469598103934665603ull;
-  {
-    auto mix = [&](const int* a, size_t n) {
-      key = (key ^ (uint64_t)n) * 1099511628211ull;
-      for (size_t k = 0; k < n; k++) key = (key ^ (uint64_t)(uint32_t)a[k]) * 1099511628211ull;
-    };
-    mix(child, (size_t)cas->nel * nch);
-    mix(fbdc, (size_t)nfb);
-    mix(cbdc, (size_t)ncb);
-  }
-  if (!cas->d_gal_child || cas->gal_key != key) {
-    cas->gal_key = key;
-    FH_TRY(up((void**)&cas->d_gal_child, child, (size_t)cas->nel * nch * sizeof(int)));
-    std::vector<unsigned char> cnt((size_t)nch * nc, 0), row((size_t)nch * nc * 8, 0);
-    std::vector<double> val((size_t)nch * nc * 8, 0.0), phi(nc), dphi((size_t)nc * 3);
-    for (int j = 0; j < nch; j++)
-      for (int i = 0; i < nc; i++) {                      // fine node i of child j: C_j[i][k] = phi_k at its reference point in the parent
-        double pt[3] = {0, 0, 0};
-        fhfe::child_node_ref(cas->geom, j, i, pt);
-        fhfe::eval_basis(cas->geom, fhfe::FE_BIQUADRATIC, pt, phi.data(), dphi.data());
-        for (int k = 0; k < nc; k++)
-          if (std::fabs(phi[k]) > 1e-14) {                // the threshold of ElemType.cpp:439-532
-            unsigned char& n = cnt[(size_t)j * nc + k];
-            FH_REQUIRE(n < 8, "fh_assembler_galerkin: more than 8 fine nodes of a child depend on one coarse node");
-            row[((size_t)j * nc + k) * 8 + n] = (unsigned char)i;
-            val[((size_t)j * nc + k) * 8 + n] = phi[k];
-            n++;
-          }
-      }
-    {
-      std::vector<double> dense((size_t)nch * nc * nc, 0.0);
-      for (int j = 0; j < nch; j++)
-        for (int k = 0; k < nc; k++)
-          for (int q = 0; q < cnt[(size_t)j * nc + k]; q++) dense[((size_t)j * nc + row[((size_t)j * nc + k) * 8 + q]) * nc + k] = val[((size_t)j * nc + k) * 8 + q];
-      FH_TRY(up((void**)&cas->d_gal_dense, dense.data(), dense.size() * sizeof(double)));
-    }
-    FH_TRY(up((void**)&cas->d_gal_cnt, cnt.data(), cnt.size()));
-    FH_TRY(up((void**)&cas->d_gal_row, row.data(), row.size()));
-    FH_TRY(up((void**)&cas->d_gal_val, val.data(), val.size() * sizeof(double)));
-    std::vector<unsigned char> fb(fas->nnode, 0), cb(cas->nnode, 0);
-    for (int k = 0; k < nfb; k++) {
-      FH_REQUIRE(fbdc[k] >= 0 && fbdc[k] < fas->nnode, "fh_assembler_galerkin: fine Dirichlet node %d out of range", fbdc[k]);
-      fb[fbdc[k]] = 1;
-    }
-    for (int k = 0; k < ncb; k++) {
-      FH_REQUIRE(cbdc[k] >= 0 && cbdc[k] < cas->nnode, "fh_assembler_galerkin: coarse Dirichlet node %d out of range", cbdc[k]);
-      cb[cbdc[k]] = 1;
-    }
-    FH_TRY(up((void**)&cas->d_gal_fb, fb.data(), fb.size()));
-    FH_TRY(up((void**)&cas->d_gal_cb, cb.data(), cb.size()));
-    if (!cas->d_gal_res) FH_CHECK_HIP(hipMalloc(&cas->d_gal_res, std::max<size_t>(cas->ndof, 1) * sizeof(double)));
-    if (nc == 27) {
-      if (cas->d_gal_fmask) FH_CHECK_HIP(hipFree(cas->d_gal_fmask));
-      cas->d_gal_fmask = nullptr;
-      FH_CHECK_HIP(hipMalloc(&cas->d_gal_fmask, ((size_t)cas->nel * 9 + 1) * sizeof(unsigned)));
-      hipLaunchKernelGGL(k_gal_masks, dim3(fh_div_up(cas->nel * 9, 256)), dim3(256), 0, c->stream, cas->nel, cas->d_gal_child, fas->d_elem_dof, fas->nloc, cas->d_gal_fb,
-                         cas->d_elem_dof, cas->nloc, cas->d_gal_cb, cas->d_gal_fmask, cas->d_gal_fmask + (size_t)cas->nel * 8);
-      FH_CHECK_HIP(hipGetLastError());
-    }
-    // the macro rows of a fused assembly can stand in for the element rows when child j of coarse element E is element j of ONE cluster (what the
-    // refinement's numbering gives: MeshRefinement.cpp:240-294)
-    cas->gal_children_in_order = nch == CL_NE;
-    for (int E = 0; E < cas->nel && cas->gal_children_in_order; E++)
-      for (int j = 0; j < nch; j++)
-        if (child[(size_t)E * nch + j] != (child[(size_t)E * nch] / nch) * nch + j || child[(size_t)E * nch] % nch) { cas->gal_children_in_order = false; break; }
-  }
-  // source of the fine element contributions: the macro rows the fused assembly left in the fine matrix and the partial-row buffer (nothing to re-create,
-  // the fused path stays the path of the next assembly), or the element-row buffer of the two-pass path
-  // (the macro rows live in the user-visible fine matrix: any writer of its values since the assembly other than the Dirichlet-row replacement -- a scaling, an
-  //  in-place product, staged adds -- sends the product back to the element rows, which are re-created from the arguments of the last assembly)
-  //  -- and so does the destruction of that matrix: the kernel reads it through addresses, which must still be the ones of a live matrix with the assembly's values)
-  const fh_mat_t fine_mat = fas->macro_valid ? fh_mat_alive(fas->macro_uid) : nullptr;
-  const bool from_macro = nc == 27 && c->galerkin_mfma && c->galerkin_macro && fas->fused && fas->last_path == 1 && fas->macro_valid && fas->cl_all_rows &&
-                          fas->d_cl_gtab && cas->gal_children_in_order && fas->cl_ncl == cas->nel && fine_mat != nullptr &&
-                          fine_mat->d_val == fas->cl_val_base && fine_mat->val_gen == fas->macro_val_gen;
-  if (!from_macro) {
-    fas->rows_used_since = true;                              // (the next assembly of this level keeps its element rows)
-    if (!fas->kbuf_valid) FH_TRY(element_rows_again(fas));     // the fused assembly kept no element rows: pass 1 of the two-pass path with the last arguments
-  }
-  const int grid = std::max(1, std::min(fh_div_up(cas->nel, 4), c->num_cu * 2));
-  if (from_macro) {
-    static bool attr_set_m[64] = {};
-    if (!attr_set_m[c->device & 63]) {
-      FH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_galerkin_macro<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gmac_lds_bytes()));
-      FH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_galerkin_macro<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gmac_lds_bytes()));
-      attr_set_m[c->device & 63] = true;
-    }
-    const int gm_grid = std::max(1, std::min(cas->nel, c->num_cu));          // (two workgroups per compute unit would need 128 registers per lane: 101 spilled)
-    if (c->asm_debug & 128) {             // dev aid: phase cycles of every wave on stderr (as for the cluster kernel)
-      unsigned long long* d_st = nullptr;
-      const size_t nst = (size_t)gm_grid * GMAC_NW * 20;
-      FH_CHECK_HIP(hipMalloc(&d_st, nst * sizeof(unsigned long long)));
-      FH_CHECK_HIP(hipMemsetAsync(d_st, 0, nst * sizeof(unsigned long long), c->stream));
-      hipLaunchKernelGGL(k_galerkin_macro<true>, dim3(gm_grid), dim3(GMAC_T), gmac_lds_bytes(), c->stream, cas->nel, cas->d_gal_child, fas->cl_nm, fas->d_cl_sinfo,
-                         reinterpret_cast<const uint4*>(fas->d_cl_map), fas->d_cl_vdst64, fas->d_cl_gtab, cas->d_gal_fmask, cas->d_gal_fmask + (size_t)cas->nel * 8, cas->d_slot, cas->d_Kbuf,
-                         cas->kstride, cas->d_gal_dense, d_st);
-      std::vector<unsigned long long> h(nst);
-      FH_CHECK_HIP(hipMemcpyAsync(h.data(), d_st, nst * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-      FH_CHECK_HIP(hipStreamSynchronize(c->stream));
-      FH_CHECK_HIP(hipFree(d_st));
-      static const char* name[10] = {"loop top", "macro matrix into LDS", "barrier", "next cluster's loads issued, look-ups", "K~ fragments gathered, two products (56 MFMA)",
-                                     "barrier (all waves done with the macro matrix)", "result into LDS", "barrier", "eight results added, coarse rows stored", "barrier"};
-      double sum[10] = {0}, ncl = 0, tot = 0;
-      for (size_t w = 0; w < (size_t)gm_grid * GMAC_NW; w++) {
-        for (int k = 0; k < 10; k++) sum[k] += (double)h[w * 20 + k];
-        ncl += (double)h[w * 20 + 16];
-      }
-      for (int k = 0; k < 10; k++) tot += sum[k];
-      fprintf(stderr, "k_galerkin_macro phase stamps: %.0f shader-clock ticks per cluster and wave\n", tot / std::max(ncl, 1.0));
-      for (int k = 0; k < 10; k++) fprintf(stderr, "  %2d %-62s %9.1f  %5.1f %%\n", k, name[k], sum[k] / std::max(ncl, 1.0), 100.0 * sum[k] / std::max(tot, 1.0));
-    } else
-      hipLaunchKernelGGL(k_galerkin_macro<false>, dim3(gm_grid), dim3(GMAC_T), gmac_lds_bytes(), c->stream, cas->nel, cas->d_gal_child, fas->cl_nm, fas->d_cl_sinfo,
-                         reinterpret_cast<const uint4*>(fas->d_cl_map), fas->d_cl_vdst64, fas->d_cl_gtab, cas->d_gal_fmask, cas->d_gal_fmask + (size_t)cas->nel * 8, cas->d_slot, cas->d_Kbuf,
-                         cas->kstride, cas->d_gal_dense, (unsigned long long*)nullptr);
-  } else if (c->galerkin_mfma) {
-    const size_t lds = nc == 27 ? galerkin_mfma_lds<27, 8>() : galerkin_mfma_lds<9, 4>();
-    static bool attr_set[64] = {};
-    if (!attr_set[c->device & 63]) {
-      FH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_galerkin_mfma<27, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)galerkin_mfma_lds<27, 8>()));
-      FH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_galerkin_mfma<9, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)galerkin_mfma_lds<9, 4>()));
-      attr_set[c->device & 63] = true;
-    }
-    const int g1 = std::max(1, std::min(fh_div_up(cas->nel, GAL_NW), c->num_cu));
-    if (nc == 27)
-      hipLaunchKernelGGL((k_galerkin_mfma<27, 8>), dim3(g1), dim3(GAL_NW * 64), lds, c->stream, cas->nel, cas->d_gal_child, fas->d_slot, fas->d_Kbuf, fas->kstride, fas->d_elem_dof,
-                         fas->nloc, cas->d_gal_fb, cas->d_slot, cas->d_Kbuf, cas->kstride, cas->d_elem_dof, cas->nloc, cas->d_gal_cb, cas->d_gal_dense);
-    else
-      hipLaunchKernelGGL((k_galerkin_mfma<9, 4>), dim3(g1), dim3(GAL_NW * 64), lds, c->stream, cas->nel, cas->d_gal_child, fas->d_slot, fas->d_Kbuf, fas->kstride, fas->d_elem_dof,
-                         fas->nloc, cas->d_gal_fb, cas->d_slot, cas->d_Kbuf, cas->kstride, cas->d_elem_dof, cas->nloc, cas->d_gal_cb, cas->d_gal_dense);
-  } else if (nc == 27)
-    hipLaunchKernelGGL((k_galerkin_elem<27, 8>), dim3(grid), dim3(256), 0, c->stream, cas->nel, cas->d_gal_child, fas->d_slot, fas->d_Kbuf, fas->kstride,
-                       fas->d_elem_dof, fas->nloc, cas->d_gal_fb, cas->d_slot, cas->d_Kbuf, cas->kstride, cas->d_elem_dof, cas->nloc, cas->d_gal_cb, cas->d_gal_cnt,
-                       cas->d_gal_row, cas->d_gal_val);
-  else
-    hipLaunchKernelGGL((k_galerkin_elem<9, 4>), dim3(grid), dim3(256), 0, c->stream, cas->nel, cas->d_gal_child, fas->d_slot, fas->d_Kbuf, fas->kstride,
-                       fas->d_elem_dof, fas->nloc, cas->d_gal_fb, cas->d_slot, cas->d_Kbuf, cas->kstride, cas->d_elem_dof, cas->nloc, cas->d_gal_cb, cas->d_gal_cnt,
-                       cas->d_gal_row, cas->d_gal_val);
-  FH_CHECK_HIP(hipGetLastError());
-  FH_CHECK_HIP(hipMemsetAsync(cas->d_Fbuf, 0, std::max<size_t>(cas->nadj, 1) * sizeof(double), c->stream));
-  FH_TRY(dispatch_rows(cas, Ac, cas->d_gal_res, false));
-  cas->kbuf_valid = true;     // the coarse element rows this product wrote (the next coarser product reads them)
-  cas->macro_valid = false;   // ... and not the macro rows an earlier fused assembly of the coarse level may have left in Ac: this product has overwritten Ac
-  fh_mat_values_written(Ac);
-  return 0;
-  FH_GUARD_END("fh_assembler_galerkin")
 }
