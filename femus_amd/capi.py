@@ -1167,6 +1167,18 @@ class GenericAssembler:
         _chk(self.L.fh_generic_assembler_assemble(self.h, sol.h if sol is not None else None, source.h if source is not None else None, float(scale),
                                                   K.h if K is not None else None, res.h))
 
+    def assemble_form(self, K, res, sol, form):
+        """K and res are overwritten with the Jacobian and residual of the QuasilinearForm at sol (None: 0): fh_generic_assembler_assemble_form, under
+        assemble()'s contract.  K is unsymmetric as soon as the form has c_g or a_u"""
+        _chk(self.L.fh_generic_assembler_assemble_form(self.h, sol.h if sol is not None else None, form.pointer() if form is not None else None,
+                                                       K.h if K is not None else None, res.h))
+
+    def form_chunks(self):
+        """Gauss points per LDS chunk of assemble_form's element pass by shape (0 before the first assemble_form)"""
+        gc = (ctypes.c_int * 3)()
+        _chk(self.L.fh_generic_assembler_form_chunks(self.h, gc))
+        return {s: gc[k] for k, s in enumerate(self.shapes[:3])}
+
     def info(self):
         """elements per 256-thread workgroup of the element pass by shape, bytes held on the device, bytes one assembly cannot avoid moving, device
         allocations made so far"""
@@ -1513,6 +1525,47 @@ class Expr:
         if self.h:
             self.L.fh_expr_destroy(self.h)
             self.h = None
+
+
+class QuasilinearForm:
+    """fh_quasilinear_form_t: the coefficient programs of -div(a grad u) + c = f for GenericAssembler.assemble_form, each a text over QuasilinearForm.VARIABLES
+    (compiled here and owned by this object) or an Expr of the caller's (left alone by destroy()), or None: a = 1, every other term 0.  a_u = da/du,
+    c_u = dc/du, c_g[d] = dc/du_d are the caller's derivatives; c_g has at most dim entries.
+    ex03 (Poisson plus nonlinear advection):  c="u*(ux+uy)", c_u="ux+uy", c_g=("u", "u");   ex03b (nonlinear diffusivity):  a="1+u*u", a_u="2*u" """
+
+    VARIABLES = "x,y,z,u,ux,uy,uz"
+
+    class _Struct(ctypes.Structure):
+        _fields_ = [(n, ctypes.c_void_p) for n in ("f", "a", "a_u", "c", "c_u")] + [("c_g", ctypes.c_void_p * 3)]
+
+    def __init__(self, f=None, a=None, a_u=None, c=None, c_u=None, c_g=None):
+        c_g = list(c_g) if c_g is not None else []
+        if len(c_g) > 3:
+            raise ValueError("c_g has one entry per space dimension, at most 3, not %d" % len(c_g))
+        self._owned, self.exprs = [], {}
+        try:
+            for name, e in [("f", f), ("a", a), ("a_u", a_u), ("c", c), ("c_u", c_u)] + [("c_g[%d]" % d, e) for d, e in enumerate(c_g)]:
+                if e is not None and not isinstance(e, Expr):
+                    e = Expr(str(e), self.VARIABLES)
+                    self._owned.append(e)
+                self.exprs[name] = e
+        except BaseException:
+            self.destroy()
+            raise
+        self._refresh()
+
+    def _refresh(self):
+        h = lambda name: self.exprs[name].h.value if self.exprs.get(name) is not None and self.exprs[name].h is not None else None
+        self._s = self._Struct(h("f"), h("a"), h("a_u"), h("c"), h("c_u"), (ctypes.c_void_p * 3)(*[h("c_g[%d]" % d) for d in range(3)]))
+
+    def pointer(self):
+        return ctypes.cast(ctypes.pointer(self._s), ctypes.c_void_p)
+
+    def destroy(self):
+        for e in self._owned:
+            e.destroy()
+        self._owned, self.exprs = [], {}
+        self._refresh()
 
 
 def system_elem_dofs(mesh, fes):

@@ -43,7 +43,8 @@ struct fh_generic_assembler_s {
   int lpr = 1, maxrow = 1;
   size_t row_lds = 0;
   int64_t nadj = 0, nrows = 0, nent = 0;      // entries of adj, element rows, entries of Kb / Pos
-  // the source program: consts (doubles) then code (ints) in one buffer, staged through pinned memory; uploaded only when it differs from the last one
+  // the source program (assemble_form: all its programs back to back): consts (doubles) then code (ints) in one buffer, staged through pinned memory; uploaded
+  // only when it differs from the last one
   char* d_prog = nullptr;
   char* h_prog = nullptr;
   size_t prog_cap = 0;
@@ -52,6 +53,11 @@ struct fh_generic_assembler_s {
   std::vector<int> code;
   std::vector<double> consts;
   bool have_prog = false;
+  // the quasilinear element body (fh_quasilinear.hip): its Gauss chunk, table staging and LDS per shape, chosen at the first assemble_form
+  bool form_ready = false;
+  int form_gcm[3] = {0, 0, 0};
+  bool form_tl[3] = {false, false, false};
+  size_t form_lds[3] = {0, 0, 0};
   int64_t device_bytes = 0, algorithmic_bytes = 0, device_allocations = 0;
   std::vector<void*> dv;         // every device allocation but d_prog
 };
@@ -66,5 +72,12 @@ int gp_plan_host(const char* who, fh_ctx_t ctx, const GenMesh& m, int nel, int n
 // buffer, and the CSR position of every element entry.  *miss = ~0: done; otherwise the smallest entry the pattern does not hold, (shape index << 56) | index
 // into the shape's positions, and the object is still alive for the caller's message.  On a failure the object is freed.
 int gp_plan_work(const char* who, fh_generic_assembler_t as, const GenMesh& m, fh_mat_t KK, unsigned long long* miss);
+// consts then code into the object's program buffer, when they are not what is already there (`who`: the entry point, for the refusals).  A set of several
+// programs goes through here laid back to back in both arrays, its directory with the caller: the buffer of a single program is the set of one
+int gp_upload_program(const char* who, fh_generic_assembler_t as, std::vector<int>& code, std::vector<double>& consts);
+// the checks assemble and assemble_form make of their matrix and vectors
+int gp_check_call(const char* who, fh_generic_assembler_t as, fh_vec_t sol, fh_mat_t KK, fh_vec_t RES);
+// the row pass: Kb / Fb into KK's values and RES
+void gp_launch_rows(fh_generic_assembler_t as, fh_mat_t KK, fh_vec_t RES);
 void* gp_alloc(fh_generic_assembler_t as, size_t bytes);
 void gp_free(fh_generic_assembler_t as);

@@ -26,6 +26,9 @@
 // Row pass of the plan: lpr lanes per row (a group never leaves its wave), the row's sums in LDS: element rows in ascending element order, the lanes of the group
 // split one element row's entries (distinct positions), LDS operations of one wave complete in order -- so every entry sees its additions in ascending element
 // order, starting from 0.0 as the one-shot row thread does.  No search, no atomics, no read-modify-write of global memory.
+//
+// fh_quasilinear.hip puts a second element body on the same plan (fh_generic_assembler_assemble_form: an unsymmetric Jacobian from run-time coefficient
+// programs); it shares the row pass, the program buffer and the call checks below (gp_launch_rows, gp_upload_program, gp_check_call) and nothing of this body.
 #include "fh_generic.h"
 #include "fh_fe.h"
 #include "fh_expr_device.h"
@@ -575,11 +578,7 @@ extern "C" int fh_generic_assembler_set_coords(fh_generic_assembler_t as, int nn
   return 0;
 }
 
-// the source program into the object's buffer, when it is not the one already there
-static int gp_stage_program(fh_generic_assembler_t as, fh_expr_t source) {
-  std::vector<int> code;
-  std::vector<double> consts;
-  FH_TRY(fh_expr_fetch(source, "fh_generic_assembler_assemble: the source expression", 4, code, consts));
+int gp_upload_program(const char* who, fh_generic_assembler_t as, std::vector<int>& code, std::vector<double>& consts) {
   if (consts.empty()) consts.resize(1, 0.0);
   if (as->have_prog && code == as->code && consts == as->consts) return 0;
   const size_t bytes = consts.size() * sizeof(double) + code.size() * sizeof(int);
@@ -591,7 +590,7 @@ static int gp_stage_program(fh_generic_assembler_t as, fh_expr_t source) {
     FH_CHECK_HIP(hipMalloc((void**)&d, cap));
     if (hipHostMalloc((void**)&h, cap) != hipSuccess) {
       hipFree(d);
-      fh_set_error("fh_generic_assembler_assemble: out of pinned host memory");
+      fh_set_error("%s: out of pinned host memory", who);
       return 2;
     }
     hipFree(as->d_prog);
@@ -614,14 +613,32 @@ static int gp_stage_program(fh_generic_assembler_t as, fh_expr_t source) {
   return 0;
 }
 
+// the source program into the object's buffer, when it is not the one already there
+static int gp_stage_program(fh_generic_assembler_t as, fh_expr_t source) {
+  std::vector<int> code;
+  std::vector<double> consts;
+  FH_TRY(fh_expr_fetch(source, "fh_generic_assembler_assemble: the source expression", 4, code, consts));
+  return gp_upload_program("fh_generic_assembler_assemble", as, code, consts);
+}
+
+int gp_check_call(const char* who, fh_generic_assembler_t as, fh_vec_t sol, fh_mat_t KK, fh_vec_t RES) {
+  FH_REQUIRE(as && RES, "%s: null argument", who);
+  FH_REQUIRE(fh_mat_alive(as->mat_uid) != nullptr, "%s: the matrix this object was created on has been destroyed", who);
+  FH_REQUIRE(KK != nullptr, "%s: null matrix", who);
+  FH_REQUIRE(KK->uid == as->mat_uid && KK->nnz == as->mat_nnz, "%s: not the matrix this object was created on (uid %llu, %d non-zeros; created on uid %llu, %d)", who,
+             (unsigned long long)KK->uid, KK->nnz, (unsigned long long)as->mat_uid, as->mat_nnz);
+  FH_REQUIRE(RES->n_local >= as->ndof && (!sol || sol->n_local >= as->ndof), "%s: size mismatch", who);
+  return 0;
+}
+
+void gp_launch_rows(fh_generic_assembler_t as, fh_mat_t KK, fh_vec_t RES) {
+  hipLaunchKernelGGL(k_gen_rows, dim3(fh_div_up(as->ndof, GP_THREADS / as->lpr)), dim3(GP_THREADS), as->row_lds, as->ctx->stream, as->ndof, as->lpr, as->maxrow, as->rows,
+                     as->d_adj_ptr, as->d_adj, as->d_Kb, as->d_Pos, as->d_Fb, KK->d_rowptr, KK->d_val, RES->d);
+}
+
 extern "C" int fh_generic_assembler_assemble(fh_generic_assembler_t as, fh_vec_t sol, fh_expr_t source, double scale, fh_mat_t KK, fh_vec_t RES) {
   FH_GUARD_BEGIN
-  FH_REQUIRE(as && RES, "fh_generic_assembler_assemble: null argument");
-  FH_REQUIRE(fh_mat_alive(as->mat_uid) != nullptr, "fh_generic_assembler_assemble: the matrix this object was created on has been destroyed");
-  FH_REQUIRE(KK != nullptr, "fh_generic_assembler_assemble: null matrix");
-  FH_REQUIRE(KK->uid == as->mat_uid && KK->nnz == as->mat_nnz, "fh_generic_assembler_assemble: not the matrix this object was created on (uid %llu, %d non-zeros; created on uid %llu, %d)",
-             (unsigned long long)KK->uid, KK->nnz, (unsigned long long)as->mat_uid, as->mat_nnz);
-  FH_REQUIRE(RES->n_local >= as->ndof && (!sol || sol->n_local >= as->ndof), "fh_generic_assembler_assemble: size mismatch");
+  FH_TRY(gp_check_call("fh_generic_assembler_assemble", as, sol, KK, RES));
   const int* d_code = nullptr;
   const double* d_k = nullptr;
   int ncode = 0;
@@ -633,8 +650,7 @@ extern "C" int fh_generic_assembler_assemble(fh_generic_assembler_t as, fh_vec_t
   }
   for (int k = 0; k < as->ns; k++)
     if (as->nslot[k]) gp_launch_pairs(as, k, sol ? sol->d : nullptr, scale, d_code, ncode, d_k);
-  hipLaunchKernelGGL(k_gen_rows, dim3(fh_div_up(as->ndof, GP_THREADS / as->lpr)), dim3(GP_THREADS), as->row_lds, as->ctx->stream, as->ndof, as->lpr, as->maxrow, as->rows,
-                     as->d_adj_ptr, as->d_adj, as->d_Kb, as->d_Pos, as->d_Fb, KK->d_rowptr, KK->d_val, RES->d);
+  gp_launch_rows(as, KK, RES);
   const bool ok = hipGetLastError() == hipSuccess;
   fh_mat_values_written(KK);
   FH_REQUIRE(ok, "fh_generic_assembler_assemble: launch failed");

@@ -1,0 +1,181 @@
+"""Newton's method for a quasilinear scalar equation  -div(a(x, u) grad u) + c(x, u, grad u) = f  on resident element meshes of any shape: the driver of
+NonLinearImplicitSystem::MGsolve (src/08_equations/00_stationary/NonLinearImplicitSystem.cpp:157-361) for the problems of
+applications/000_tutorial/ex03_poisson_plus_nonlin_advection and ex03b_div_grad_nonlinear_diffusivity, on triangles, tetrahedra, prisms and mixed meshes.
+
+The levels, transfers, pattern, plan and boundary data are made where the levels live, as app_poisson.Poisson001.run_elements(mesh_data="device") makes them
+(capi.ElementMesh.refine / prolongator / boundary_dofs / matrix / boundary_owners / boundary_faces, capi.GenericAssembler.from_mesh); Jacobian and residual of
+every Newton step come from capi.GenericAssembler.assemble_form (femus_amd/csrc/fh_quasilinear.hip) at the current state."""
+import numpy as np
+
+from . import capi
+
+FAMILY = {"linear": 0, "serendipity": 1, "biquadratic": 2}
+
+
+class QuasilinearElements:
+    def __init__(self, ctx, level0, fe, nlevels, form, dirichlet=None, flux=None, order="seventh", npre=1, npost=1):
+        """level0: (kind, ed, xs, ff, own), the arrays of mixed_mesh.read_gambit / tri_box; fe: "linear", "serendipity" or "biquadratic"; nlevels: levels of
+        the hierarchy, level0 included; form: a capi.QuasilinearForm (the caller's: it is not destroyed here).
+        dirichlet: {face flag: Expr over "x,y,z,t" or None (= 0)}, the boundary values; flux: {face flag: Expr over "x,y,z,t"}, the flux a du/dn on faces that
+        are not Dirichlet (a boundary face in neither carries the natural condition, flux 0).  A Dirichlet dof shared by two flags takes the value of the last
+        (element, face) that holds it, as GenerateBdc does."""
+        if fe not in FAMILY:
+            raise ValueError("fe must be one of %s, not %r" % (sorted(FAMILY), fe))
+        if int(nlevels) < 1:
+            raise ValueError("nlevels must be at least 1, not %r" % (nlevels,))
+        self.ctx, self.level0, self.fe, self.nlevels, self.form, self.order = ctx, level0, fe, int(nlevels), form, order
+        self.dirichlet, self.flux = dict(dirichlet or {}), dict(flux or {})
+        both = set(self.dirichlet) & set(self.flux)
+        if both:
+            raise ValueError("face flags %s are both Dirichlet and flux faces" % sorted(both))
+        self.npre, self.npost = int(npre), int(npost)
+
+    def solve(self, tol=1e-6, max_newton=15, lin_maxit=4, smoother=capi.SMOOTH_GS_COLOR, omega=1.0, selective_levels=0, flag=None, amr_mode="reference", exact=None,
+              exact_gradient=None, log=None):
+        """Every nonlinear iteration: assemble_form at SOL; the flux faces; on a flagged top level RES <- P_amr^T RES and the operator P_amr^T KK P_amr; the
+        boundary rows; the Galerkin chain PP^T KK PP; at most lin_maxit GMRES steps preconditioned by one V-cycle (one level: the exact solve, ex03b's PREONLY);
+        EPS <- P_amr EPS; SOL += EPS.  It stops as HasNonLinearConverged does (NonLinearImplicitSystem.cpp:113-153): ||EPS||_2 / (||SOL||_2 + 1e-50) < tol, or
+        ||EPS||_2 < 1e-12, or ||SOL||_2 < 1e-12 -- or after max_newton iterations, not converged.
+        selective_levels > 0: the last so many levels come from the flagged refinement `flag` (an expression over x, y, z, level), wired as
+        Poisson001.run_elements wires them (hanging dofs into the boundary rows, PP[l + 1] <- PP[l + 1] P_amr[l], a conforming start).
+        Returns {"solution", "coords", "newton_history": [(Krylov steps, ||RES||_2 before the step, ||EPS||_2 / ||SOL||_2 after it)], "converged", "dofs"};
+        with exact (an expression over "x,y,z,t"; exact_gradient: dim of them, else the nodal interpolant is the yardstick) also "l2_error" and "h1_error" from
+        capi.ElementMesh.error_norms; with selective_levels also "hanging", "constraints" (capi.ElementMesh.amr_constraints of the top level), "elem_levels"."""
+        ctx, nl, fam = self.ctx, self.nlevels, FAMILY[self.fe]
+        selective_levels = int(selective_levels)
+        if selective_levels and (not 0 < selective_levels < nl or flag is None):
+            raise ValueError("selective_levels must be 0 .. nlevels - 1 = %d and come with a flag expression over x, y, z, level" % (nl - 1))
+        if amr_mode not in ("reference", "coarsest"):
+            raise ValueError("amr_mode must be \"reference\" or \"coarsest\", not %r" % (amr_mode,))
+        if exact is None and exact_gradient is not None:
+            raise ValueError("exact_gradient without exact")
+        top, n_uniform = nl - 1, nl - selective_levels
+        d_flags = sorted(int(f) for f in self.dirichlet)
+        f_flags = sorted(int(f) for f in self.flux)
+        owned, resident = [], [capi.ElementMesh.from_arrays(ctx, *self.level0)]       # owned: every device object made here, destroyed at the end
+        try:
+            for l in range(1, nl):
+                if l < n_uniform:
+                    resident.append(resident[-1].refine())
+                else:
+                    resident[-1].flag(flag)
+                    resident.append(resident[-1].refine("resident"))
+            m = resident[top]
+            hanging, P_amr, constraints = [np.zeros(0, np.int32)] * nl, [None] * nl, None
+            for l, lv in enumerate(resident):
+                if not lv.homogeneous:
+                    c = lv.amr_constraints(fam, amr_mode)
+                    hanging[l], P_amr[l] = c[0], lv.amr_prolongator(fam, amr_mode)
+                    owned.append(P_amr[l])
+                    if l == top:
+                        constraints = c
+            bdc, P = [], [None]
+            for l, lv in enumerate(resident):
+                bdc.append(np.union1d(lv.boundary_dofs(fam, d_flags), hanging[l]).astype(np.int32))
+                if l:
+                    P.append(resident[l - 1].prolongator(lv, fam))
+                    owned.append(P[l])
+            K = m.matrix(fam)
+            owned.append(K)
+            gen = capi.GenericAssembler.from_mesh(m, fam, K, order=self.order)
+            owned.append(gen)
+            b_dofs, b_flag, b_xy = m.boundary_owners(fam, d_flags)
+            faces = {f: m.boundary_faces(fam, [f]) for f in f_flags}
+            xs, ndof, dim = m.coords(), m.own[fam], m.dim
+            # the start vector: 0 with the boundary values
+            sol0 = np.zeros(ndof)
+            for f in np.unique(b_flag):
+                fn = self.dirichlet[int(f)]
+                if fn is not None:
+                    sel = b_flag == f
+                    x4 = np.zeros((int(sel.sum()), 4))
+                    x4[:, :dim] = b_xy[sel]
+                    sol0[b_dofs[sel]] = fn(x4)
+            # the flux faces by kind of face (a prism has quadrilaterals and triangles), each flag's in (element, face) order
+            exprs, flux_calls = [self.flux[f] for f in f_flags], []
+            widths = sorted({int(n) for f in f_flags for n in faces[f][3]})
+            for nn in widths:
+                nodes = np.concatenate([faces[f][2][faces[f][3] == nn][:, :nn] for f in f_flags])
+                which = np.concatenate([np.full(int((faces[f][3] == nn).sum()), k) for k, f in enumerate(f_flags)])
+                flux_calls.append(("lineface" if dim == 2 else "triface" if nn in (3, 6, 7) else "quadface", nodes, which))
+            for l in range(1, nl):                                    # PP[l] <- PP[l] PPamr[l - 1], before the Dirichlet zeroing; then ZeroInterpolatorDirichletNodes
+                if P_amr[l - 1] is not None:
+                    P[l] = P[l].matmul(P_amr[l - 1])
+                    owned.append(P[l])
+                if bdc[l].size:
+                    P[l].mat_zero_rows(bdc[l], 0.0)
+                if bdc[l - 1].size:
+                    P[l].zero_cols(bdc[l - 1])
+            SOL, RES, EPS = ctx.vector(ndof), ctx.vector(ndof), ctx.vector(ndof)
+            owned += [SOL, RES, EPS]
+            SOL.upload(sol0)
+            PA = P_amr[top]
+            if PA is not None:                                        # a conforming start
+                RES.matrix_mult(SOL, PA)
+                SOL.assign(RES)
+            mg = capi.Multigrid(ctx, nl)
+            owned.append(mg)
+            A = [None] * nl
+            if PA is None:
+                A[top] = K
+            history, converged = [], False
+            for it in range(int(max_newton)):
+                gen.assemble_form(K, RES, SOL, self.form)
+                for fgeom, nodes, which in flux_calls:
+                    if dim == 2:
+                        capi.assemble_neumann_edges(ctx, self.fe, nodes, which, exprs, xs, RES, order=self.order)
+                    else:
+                        capi.assemble_neumann_faces_expr(ctx, fgeom, self.fe, nodes, which, exprs, xs, RES, order=self.order)
+                if PA is not None:
+                    EPS.matrix_mult_transpose(RES, PA)
+                    RES.assign(EPS)
+                    if A[top] is None:
+                        A[top] = capi.Mat.ptap(PA, K)
+                        owned.append(A[top])
+                    else:
+                        A[top].ptap_numeric(PA, K)
+                if bdc[top].size:
+                    A[top].mat_zero_rows(bdc[top], 1.0)
+                    RES.set(bdc[top], np.zeros(bdc[top].size))
+                rn = RES.l2_norm()
+                for l in range(top, 0, -1):
+                    if A[l - 1] is None:
+                        A[l - 1] = capi.Mat.ptap(P[l], A[l])
+                        owned.append(A[l - 1])
+                    else:
+                        A[l - 1].ptap_numeric(P[l], A[l])
+                for l in range(top):
+                    if bdc[l].size:
+                        A[l].mat_zero_rows(bdc[l], 1.0)
+                for l in range(nl):
+                    mg.set_level(l, A[l], P[l], None, smoother, omega, self.npre if l > 0 else 1, self.npost if l > 0 else 0)
+                mg.setup()
+                EPS.zero()
+                its, _ = mg.solve(RES, EPS, outer="gmres" if nl > 1 else "preonly", rtol=1e-12, atol=1e-20, maxit=int(lin_maxit))
+                if PA is not None:
+                    RES.matrix_mult(EPS, PA)
+                    EPS.assign(RES)
+                SOL.add(1.0, EPS)
+                en, sn = EPS.l2_norm(), SOL.l2_norm()
+                rel = en / (sn + 1e-50)
+                history.append((its, rn, rel))
+                if log:
+                    log("Nonlinear iteration %d: %d Krylov steps, Res_l2norm = %.6e, Eps_l2norm/Sol_l2norm = %.6e, Eps_l2norm = %.6e" % (it + 1, its, rn, rel, en))
+                if rel < tol or en < 1e-12 or sn < 1e-12:
+                    converged = True
+                    break
+            out = {"solution": SOL.to_numpy(), "coords": xs[:ndof], "newton_history": history, "converged": converged, "dofs": ndof}
+            if exact is not None:
+                en = m.error_norms(fam, SOL, exact=exact, gradient=exact_gradient, order=self.order)
+                out["l2_error"], out["h1_error"] = en["l2"], en["h1"]
+            if selective_levels:
+                out["hanging"], out["constraints"], out["elem_levels"] = hanging[top], constraints, m.elem_levels()[0]
+            return out
+        finally:
+            seen = set()
+            for q in sorted(reversed(owned), key=lambda q: not isinstance(q, capi.Multigrid)):       # the cycle before the operators it holds
+                if id(q) not in seen:
+                    seen.add(id(q))
+                    q.destroy()
+            for lv in resident:
+                lv.destroy()

@@ -609,6 +609,24 @@ int fh_generic_assembler_shapes(fh_generic_assembler_t as, int shapes[3]);
 int fh_generic_assembler_create_from_mesh(fh_elem_mesh_t mesh, int fe, int gauss_order, fh_mat_t KK, fh_generic_assembler_t* out);
 int fh_generic_assembler_plan_sizes(fh_generic_assembler_t as, int* ndof, int64_t* nadj, int64_t* nent);
 int fh_generic_assembler_get_plan(fh_generic_assembler_t as, int* adj_ptr, int* adj, int* pos);
+/* A QUASILINEAR scalar equation on the same object (fh_quasilinear.hip): the Jacobian and residual of one Newton step of NonLinearImplicitSystem, as the
+ * callbacks of applications/000_tutorial/ex03_poisson_plus_nonlin_advection (main.cpp:419-446) and ex03b_div_grad_nonlinear_diffusivity (:423-455) form them,
+ * with the coefficients as run-time programs over the SEVEN variables (x, y, z, u, ux, uy, uz) of a Gauss point (coordinates and derivatives beyond dim are 0):
+ *   RES_i = sum_g [ f phi_i - a (grad phi_i . grad u) - c phi_i ] w
+ *   KK_ij = sum_g [ a (grad phi_i . grad phi_j) + a_u phi_j (grad phi_i . grad u) + phi_i ( c_u phi_j + c_g . grad phi_j ) ] w
+ * -grad.(a grad u) + c = f with a = a(x, u), c = c(x, u, grad u); a_u = da/du, c_u = dc/du, c_g[d] = dc/du_d are the CALLER's derivative programs (the reference
+ * gets them from adept).  Any member may be NULL: a = 1, every other term 0, so that a form with f alone is the Poisson callback (scale 1).  Signs as there:
+ * KK EPS = RES, SOL += EPS.  KK is unsymmetric as soon as c_g or a_u is given: all nc x nc entries of an element are formed, none mirrored.
+ * Works on an object of either builder and obeys assemble's contract: only enqueues on the context's stream, no host loop over the mesh, no allocation (the
+ * program buffer may grow as it does there; the programs go up only when the set differs from the last one), OVERWRITES KK and RES, KK must be the matrix of
+ * create, sol NULL = 0.  No floating-point atomics, every sum in a fixed order (nodes ascending inside a Gauss point, Gauss points ascending, a row's elements
+ * ascending): a repeated call gives the same bits.  Refused before anything is enqueued, the object still usable: a program compiled over more than 7
+ * variables, c_g[d] given for d >= dim, a foreign matrix, and -- at the first call, when the Gauss chunk of this larger element body is chosen -- a shape whose
+ * element does not fit the LDS of a workgroup.  fh_generic_assembler_info keeps its meaning. */
+typedef struct { fh_expr_t f, a, a_u, c, c_u, c_g[3]; } fh_quasilinear_form_t;   /* any member may be NULL */
+int fh_generic_assembler_assemble_form(fh_generic_assembler_t as, fh_vec_t sol, const fh_quasilinear_form_t* form, fh_mat_t KK, fh_vec_t RES);
+/* the Gauss points one chunk of assemble_form's element pass takes per shape (0 beyond the last shape, and for every shape before the first assemble_form) */
+int fh_generic_assembler_form_chunks(fh_generic_assembler_t as, int gauss_chunk[3]);
 /* Open-boundary pressure term of the steady Navier-Stokes residual (src/08_equations/assemble/03_navier_stokes.hpp:185-290): on every listed boundary
  * face  aResV[k][node_i] += phi_i * tau * normal[k] * weight  for the dim velocity components (Q2 face nodes), tau = the prescribed pressure -- one
  * number per face (tau) or expression face_expr[f] of the nexpr expressions evaluated at the face Gauss point, as the bdc callback is (:280) -- and
