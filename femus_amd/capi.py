@@ -1179,6 +1179,20 @@ class GenericAssembler:
         _chk(self.L.fh_generic_assembler_form_chunks(self.h, gc))
         return {s: gc[k] for k, s in enumerate(self.shapes[:3])}
 
+    def assemble_transient(self, K, res, sol, sol_old, form, time, dt, theta=1.0):
+        """K and res are overwritten with the Jacobian and residual of one Newton iteration of one theta-step of u_t - div(a grad u) + c = f, scaled by dt
+        (fh_generic_assembler_assemble_transient): sol the iterate, sol_old the state at time - dt, time the time at the END of the step; form a TransientForm
+        (or a QuasilinearForm: no t in it)"""
+        _chk(self.L.fh_generic_assembler_assemble_transient(self.h, sol.h if sol is not None else None, sol_old.h if sol_old is not None else None,
+                                                            form.pointer() if form is not None else None, float(time), float(dt), float(theta),
+                                                            K.h if K is not None else None, res.h))
+
+    def transient_chunks(self):
+        """Gauss points per LDS chunk of assemble_transient's element pass by shape (0 before the first assemble_transient)"""
+        gc = (ctypes.c_int * 3)()
+        _chk(self.L.fh_generic_assembler_transient_chunks(self.h, gc))
+        return {s: gc[k] for k, s in enumerate(self.shapes[:3])}
+
     def info(self):
         """elements per 256-thread workgroup of the element pass by shape, bytes held on the device, bytes one assembly cannot avoid moving, device
         allocations made so far"""
@@ -1566,6 +1580,12 @@ class QuasilinearForm:
             e.destroy()
         self._owned, self.exprs = [], {}
         self._refresh()
+
+
+class TransientForm(QuasilinearForm):
+    """the same programs for GenericAssembler.assemble_transient (u_t - div(a grad u) + c = f): texts over eight variables, the last the time"""
+
+    VARIABLES = "x,y,z,u,ux,uy,uz,t"
 
 
 def system_elem_dofs(mesh, fes):

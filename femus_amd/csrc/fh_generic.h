@@ -58,6 +58,11 @@ struct fh_generic_assembler_s {
   int form_gcm[3] = {0, 0, 0};
   bool form_tl[3] = {false, false, false};
   size_t form_lds[3] = {0, 0, 0};
+  // the transient element body (fh_transient.hip): the same three of its own, chosen at the first assemble_transient
+  bool tr_ready = false;
+  int tr_gcm[3] = {0, 0, 0};
+  bool tr_tl[3] = {false, false, false};
+  size_t tr_lds[3] = {0, 0, 0};
   int64_t device_bytes = 0, algorithmic_bytes = 0, device_allocations = 0;
   std::vector<void*> dv;         // every device allocation but d_prog
 };

@@ -24,21 +24,13 @@
 // The programs sit back to back in the object's program buffer -- all constants, then all code, the layout of the Poisson path's single program, so the two
 // paths share the buffer and its cache: it is uploaded only when its content differs from the last call's, whichever path made that.  The directory (where
 // each program starts, how long it is) is 96 bytes of kernel argument.
-#include "fh_generic.h"
+#include "fh_quasilinear.h"
 #include "fh_expr_device.h"
 #include <algorithm>
 
 namespace {
-enum { QF_F = 0, QF_A, QF_AU, QF_C, QF_CU, QF_CG, QF_NPROG = QF_CG + 3 };
 constexpr int QF_VARS = 7;                   // x, y, z, u, ux, uy, uz
-constexpr int QF_PT = 7;                     // a, a_u, c, c_u, c_g[3] of a Gauss point
-
-struct GenFormDir {
-  int code[QF_NPROG], ncode[QF_NPROG], kons[QF_NPROG];     // first word, words (-1: no such program), first constant
-};
-
 constexpr size_t qf_elem_doubles(int ns, int gc) { return (size_t)ns * 4 + (size_t)gc * (14 + QF_PT) + (size_t)gc * ns * 5; }
-constexpr int qf_entries_per_lane(int L) { return L == 64 ? (GEN_NC * GEN_NC + 63) / 64 : 4; }
 }  // namespace
 
 // The element body.  Every thread of the workgroup calls this with the same ng and gcm (workgroup barriers); a sub-group without an element passes
@@ -265,32 +257,40 @@ static int qf_plan(fh_generic_assembler_t as) {
   return 0;
 }
 
-extern "C" int fh_generic_assembler_assemble_form(fh_generic_assembler_t as, fh_vec_t sol, const fh_quasilinear_form_t* form, fh_mat_t KK, fh_vec_t RES) {
-  FH_GUARD_BEGIN
-  const char* who = "fh_generic_assembler_assemble_form";
-  FH_TRY(gp_check_call(who, as, sol, KK, RES));
-  FH_REQUIRE(form, "fh_generic_assembler_assemble_form: null form");
-  // ---- every refusal first: nothing is enqueued before the last of them ----
+int qf_gather_programs(const char* who, fh_generic_assembler_t as, const fh_quasilinear_form_t* form, int max_vars, const char* vars, GenFormDir& dir,
+                       std::vector<int>& code, std::vector<double>& consts) {
   static const char* const names[QF_NPROG] = {"f", "a", "a_u", "c", "c_u", "c_g[0]", "c_g[1]", "c_g[2]"};
   const fh_expr_t progs[QF_NPROG] = {form->f, form->a, form->a_u, form->c, form->c_u, form->c_g[0], form->c_g[1], form->c_g[2]};
-  for (int d = as->dim; d < 3; d++)
-    FH_REQUIRE(!progs[QF_CG + d], "fh_generic_assembler_assemble_form: c_g[%d] given on a mesh of dimension %d", d, as->dim);
-  GenFormDir dir;
-  std::vector<int> code, c1;
-  std::vector<double> consts, k1;
+  for (int d = as->dim; d < 3; d++) FH_REQUIRE(!progs[QF_CG + d], "%s: c_g[%d] given on a mesh of dimension %d", who, d, as->dim);
+  std::vector<int> c1;
+  std::vector<double> k1;
+  code.clear();
+  consts.clear();
   for (int p = 0; p < QF_NPROG; p++) {
     dir.code[p] = dir.kons[p] = 0;
     dir.ncode[p] = -1;
     if (!progs[p]) continue;
     int nv = 0;
     FH_TRY(fh_expr_nvars(progs[p], &nv));
-    FH_REQUIRE(nv <= QF_VARS, "fh_generic_assembler_assemble_form: the program %s has %d variables, at most %d (x, y, z, u, ux, uy, uz) are served", names[p], nv,
-               QF_VARS);
-    FH_TRY(fh_expr_fetch(progs[p], names[p], QF_VARS, c1, k1));
+    FH_REQUIRE(nv <= max_vars, "%s: the program %s has %d variables, at most %d (%s) are served", who, names[p], nv, max_vars, vars);
+    FH_TRY(fh_expr_fetch(progs[p], names[p], max_vars, c1, k1));
     dir.code[p] = (int)code.size(), dir.ncode[p] = (int)c1.size(), dir.kons[p] = (int)consts.size();
     code.insert(code.end(), c1.begin(), c1.end());
     consts.insert(consts.end(), k1.begin(), k1.end());
   }
+  return 0;
+}
+
+extern "C" int fh_generic_assembler_assemble_form(fh_generic_assembler_t as, fh_vec_t sol, const fh_quasilinear_form_t* form, fh_mat_t KK, fh_vec_t RES) {
+  FH_GUARD_BEGIN
+  const char* who = "fh_generic_assembler_assemble_form";
+  FH_TRY(gp_check_call(who, as, sol, KK, RES));
+  FH_REQUIRE(form, "fh_generic_assembler_assemble_form: null form");
+  // ---- every refusal first: nothing is enqueued before the last of them ----
+  GenFormDir dir;
+  std::vector<int> code;
+  std::vector<double> consts;
+  FH_TRY(qf_gather_programs(who, as, form, QF_VARS, "x, y, z, u, ux, uy, uz", dir, code, consts));
   if (!as->form_ready) FH_TRY(qf_plan(as));
   FH_TRY(gp_upload_program(who, as, code, consts));
   const double* d_k = (const double*)as->d_prog;

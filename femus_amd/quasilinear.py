@@ -12,6 +12,165 @@ from . import capi
 FAMILY = {"linear": 0, "serendipity": 1, "biquadratic": 2}
 
 
+class ResidentHierarchy:
+    """What the Newton drivers on resident element meshes share (QuasilinearElements here, transient.TransientQuasilinearElements): the levels, transfers,
+    boundary lists, P_amr wiring of flagged levels, pattern, plan, flux faces, work vectors and the Multigrid object, made once and kept until destroy(); and one
+    nonlinear iteration on them.  dirichlet: {face flag: Expr over "x,y,z,t" or None (= 0)}; flux: {face flag: Expr}."""
+
+    def __init__(self, ctx, level0, fe, nlevels, dirichlet, flux, order, selective_levels=0, flag=None, amr_mode="reference"):
+        nl, fam = int(nlevels), FAMILY[fe]
+        selective_levels = int(selective_levels)
+        if selective_levels and (not 0 < selective_levels < nl or flag is None):
+            raise ValueError("selective_levels must be 0 .. nlevels - 1 = %d and come with a flag expression over x, y, z, level" % (nl - 1))
+        if amr_mode not in ("reference", "coarsest"):
+            raise ValueError("amr_mode must be \"reference\" or \"coarsest\", not %r" % (amr_mode,))
+        self.ctx, self.fe, self.fam, self.nl, self.order, self.selective_levels = ctx, fe, fam, nl, order, selective_levels
+        self.dirichlet, self.flux = dirichlet, flux
+        top, n_uniform = nl - 1, nl - selective_levels
+        d_flags = sorted(int(f) for f in dirichlet)
+        f_flags = sorted(int(f) for f in flux)
+        owned = self.owned = []                                       # every device object made here but the levels
+        resident = self.resident = [capi.ElementMesh.from_arrays(ctx, *level0)]
+        try:
+            for l in range(1, nl):
+                if l < n_uniform:
+                    resident.append(resident[-1].refine())
+                else:
+                    resident[-1].flag(flag)
+                    resident.append(resident[-1].refine("resident"))
+            m = self.top = resident[top]
+            hanging, P_amr, self.constraints = [np.zeros(0, np.int32)] * nl, [None] * nl, None
+            for l, lv in enumerate(resident):
+                if not lv.homogeneous:
+                    c = lv.amr_constraints(fam, amr_mode)
+                    hanging[l], P_amr[l] = c[0], lv.amr_prolongator(fam, amr_mode)
+                    owned.append(P_amr[l])
+                    if l == top:
+                        self.constraints = c
+            self.hanging = hanging
+            bdc, P = self.bdc, self.P = [], [None]
+            for l, lv in enumerate(resident):
+                bdc.append(np.union1d(lv.boundary_dofs(fam, d_flags), hanging[l]).astype(np.int32))
+                if l:
+                    P.append(resident[l - 1].prolongator(lv, fam))
+                    owned.append(P[l])
+            self.K = m.matrix(fam)
+            owned.append(self.K)
+            self.gen = capi.GenericAssembler.from_mesh(m, fam, self.K, order=order)
+            owned.append(self.gen)
+            self.b_dofs, self.b_flag, self.b_xy = m.boundary_owners(fam, d_flags)
+            faces = {f: m.boundary_faces(fam, [f]) for f in f_flags}
+            self.xs, self.ndof, self.dim = m.coords(), m.own[fam], m.dim
+            # the flux faces by kind of face (a prism has quadrilaterals and triangles), each flag's in (element, face) order
+            self.flux_exprs, self.flux_calls = [flux[f] for f in f_flags], []
+            widths = sorted({int(n) for f in f_flags for n in faces[f][3]})
+            for nn in widths:
+                nodes = np.concatenate([faces[f][2][faces[f][3] == nn][:, :nn] for f in f_flags])
+                which = np.concatenate([np.full(int((faces[f][3] == nn).sum()), k) for k, f in enumerate(f_flags)])
+                self.flux_calls.append(("lineface" if self.dim == 2 else "triface" if nn in (3, 6, 7) else "quadface", nodes, which))
+            for l in range(1, nl):                                    # PP[l] <- PP[l] PPamr[l - 1], before the Dirichlet zeroing; then ZeroInterpolatorDirichletNodes
+                if P_amr[l - 1] is not None:
+                    P[l] = P[l].matmul(P_amr[l - 1])
+                    owned.append(P[l])
+                if bdc[l].size:
+                    P[l].mat_zero_rows(bdc[l], 0.0)
+                if bdc[l - 1].size:
+                    P[l].zero_cols(bdc[l - 1])
+            self.SOL, self.RES, self.EPS = ctx.vector(self.ndof), ctx.vector(self.ndof), ctx.vector(self.ndof)
+            owned += [self.SOL, self.RES, self.EPS]
+            self.PA = P_amr[top]
+            self.mg = capi.Multigrid(ctx, nl)
+            owned.append(self.mg)
+            self.A = [None] * nl
+            if self.PA is None:
+                self.A[top] = self.K
+        except BaseException:
+            self.destroy()
+            raise
+
+    def boundary_values(self, time=0.0, zeros=False):
+        """(dofs, values): the Dirichlet dofs whose flag has an expression, and that expression at their coordinates and `time`; with zeros also the dofs of
+        the flags given as None, with the value 0 they stand for (a start vector of zeros has them already, a state that was set from outside has not)"""
+        dofs, values = [], []
+        for f in np.unique(self.b_flag):
+            fn = self.dirichlet[int(f)]
+            sel = self.b_flag == f
+            if fn is not None:
+                x4 = np.zeros((int(sel.sum()), 4))
+                x4[:, :self.dim], x4[:, 3] = self.b_xy[sel], time
+                dofs.append(self.b_dofs[sel])
+                values.append(fn(x4))
+            elif zeros:
+                dofs.append(self.b_dofs[sel])
+                values.append(np.zeros(int(sel.sum())))
+        return (np.concatenate(dofs), np.concatenate(values)) if dofs else (np.zeros(0, np.int32), np.zeros(0))
+
+    def make_conforming(self, v):
+        """v <- P_amr v on a flagged top level: every hanging dof on its constraint row (RES is the scratch)"""
+        if self.PA is not None:
+            self.RES.matrix_mult(v, self.PA)
+            v.assign(self.RES)
+
+    def add_flux(self, res):
+        """res += the integrals of the flux faces"""
+        for fgeom, nodes, which in self.flux_calls:
+            if self.dim == 2:
+                capi.assemble_neumann_edges(self.ctx, self.fe, nodes, which, self.flux_exprs, self.xs, res, order=self.order)
+            else:
+                capi.assemble_neumann_faces_expr(self.ctx, fgeom, self.fe, nodes, which, self.flux_exprs, self.xs, res, order=self.order)
+
+    def newton_iteration(self, assemble, lin_maxit, smoother, omega, npre, npost):
+        """assemble() has to leave Jacobian and residual at SOL in K and RES; then, on a flagged top level, RES <- P_amr^T RES and the operator P_amr^T KK P_amr;
+        the boundary rows; the Galerkin chain PP^T KK PP; at most lin_maxit GMRES steps preconditioned by one V-cycle (one level: the exact solve); EPS <- P_amr EPS;
+        SOL += EPS.  Returns (Krylov steps, ||RES||_2 before the step, ||EPS||_2, ||SOL||_2 after it)"""
+        nl, top = self.nl, self.nl - 1
+        A, P, PA, K, bdc = self.A, self.P, self.PA, self.K, self.bdc
+        SOL, RES, EPS = self.SOL, self.RES, self.EPS
+        mg, owned = self.mg, self.owned
+        assemble()
+        if PA is not None:
+            EPS.matrix_mult_transpose(RES, PA)
+            RES.assign(EPS)
+            if A[top] is None:
+                A[top] = capi.Mat.ptap(PA, K)
+                owned.append(A[top])
+            else:
+                A[top].ptap_numeric(PA, K)
+        if bdc[top].size:
+            A[top].mat_zero_rows(bdc[top], 1.0)
+            RES.set(bdc[top], np.zeros(bdc[top].size))
+        rn = RES.l2_norm()
+        for l in range(top, 0, -1):
+            if A[l - 1] is None:
+                A[l - 1] = capi.Mat.ptap(P[l], A[l])
+                owned.append(A[l - 1])
+            else:
+                A[l - 1].ptap_numeric(P[l], A[l])
+        for l in range(top):
+            if bdc[l].size:
+                A[l].mat_zero_rows(bdc[l], 1.0)
+        for l in range(nl):
+            mg.set_level(l, A[l], P[l], None, smoother, omega, npre if l > 0 else 1, npost if l > 0 else 0)
+        mg.setup()
+        EPS.zero()
+        its, _ = mg.solve(RES, EPS, outer="gmres" if nl > 1 else "preonly", rtol=1e-12, atol=1e-20, maxit=int(lin_maxit))
+        if PA is not None:
+            RES.matrix_mult(EPS, PA)
+            EPS.assign(RES)
+        SOL.add(1.0, EPS)
+        return its, rn, EPS.l2_norm(), SOL.l2_norm()
+
+    def destroy(self):
+        seen = set()
+        for q in sorted(reversed(self.owned), key=lambda q: not isinstance(q, capi.Multigrid)):       # the cycle before the operators it holds
+            if id(q) not in seen:
+                seen.add(id(q))
+                q.destroy()
+        for lv in self.resident:
+            lv.destroy()
+        self.owned, self.resident = [], []
+
+
 class QuasilinearElements:
     def __init__(self, ctx, level0, fe, nlevels, form, dirichlet=None, flux=None, order="seventh", npre=1, npost=1):
         """level0: (kind, ed, xs, ff, own), the arrays of mixed_mesh.read_gambit / tri_box; fe: "linear", "serendipity" or "biquadratic"; nlevels: levels of
@@ -41,122 +200,25 @@ class QuasilinearElements:
         Returns {"solution", "coords", "newton_history": [(Krylov steps, ||RES||_2 before the step, ||EPS||_2 / ||SOL||_2 after it)], "converged", "dofs"};
         with exact (an expression over "x,y,z,t"; exact_gradient: dim of them, else the nodal interpolant is the yardstick) also "l2_error" and "h1_error" from
         capi.ElementMesh.error_norms; with selective_levels also "hanging", "constraints" (capi.ElementMesh.amr_constraints of the top level), "elem_levels"."""
-        ctx, nl, fam = self.ctx, self.nlevels, FAMILY[self.fe]
-        selective_levels = int(selective_levels)
-        if selective_levels and (not 0 < selective_levels < nl or flag is None):
-            raise ValueError("selective_levels must be 0 .. nlevels - 1 = %d and come with a flag expression over x, y, z, level" % (nl - 1))
-        if amr_mode not in ("reference", "coarsest"):
-            raise ValueError("amr_mode must be \"reference\" or \"coarsest\", not %r" % (amr_mode,))
         if exact is None and exact_gradient is not None:
             raise ValueError("exact_gradient without exact")
-        top, n_uniform = nl - 1, nl - selective_levels
-        d_flags = sorted(int(f) for f in self.dirichlet)
-        f_flags = sorted(int(f) for f in self.flux)
-        owned, resident = [], [capi.ElementMesh.from_arrays(ctx, *self.level0)]       # owned: every device object made here, destroyed at the end
+        h = ResidentHierarchy(self.ctx, self.level0, self.fe, self.nlevels, self.dirichlet, self.flux, self.order, selective_levels, flag, amr_mode)
         try:
-            for l in range(1, nl):
-                if l < n_uniform:
-                    resident.append(resident[-1].refine())
-                else:
-                    resident[-1].flag(flag)
-                    resident.append(resident[-1].refine("resident"))
-            m = resident[top]
-            hanging, P_amr, constraints = [np.zeros(0, np.int32)] * nl, [None] * nl, None
-            for l, lv in enumerate(resident):
-                if not lv.homogeneous:
-                    c = lv.amr_constraints(fam, amr_mode)
-                    hanging[l], P_amr[l] = c[0], lv.amr_prolongator(fam, amr_mode)
-                    owned.append(P_amr[l])
-                    if l == top:
-                        constraints = c
-            bdc, P = [], [None]
-            for l, lv in enumerate(resident):
-                bdc.append(np.union1d(lv.boundary_dofs(fam, d_flags), hanging[l]).astype(np.int32))
-                if l:
-                    P.append(resident[l - 1].prolongator(lv, fam))
-                    owned.append(P[l])
-            K = m.matrix(fam)
-            owned.append(K)
-            gen = capi.GenericAssembler.from_mesh(m, fam, K, order=self.order)
-            owned.append(gen)
-            b_dofs, b_flag, b_xy = m.boundary_owners(fam, d_flags)
-            faces = {f: m.boundary_faces(fam, [f]) for f in f_flags}
-            xs, ndof, dim = m.coords(), m.own[fam], m.dim
+            SOL, RES, K = h.SOL, h.RES, h.K
             # the start vector: 0 with the boundary values
-            sol0 = np.zeros(ndof)
-            for f in np.unique(b_flag):
-                fn = self.dirichlet[int(f)]
-                if fn is not None:
-                    sel = b_flag == f
-                    x4 = np.zeros((int(sel.sum()), 4))
-                    x4[:, :dim] = b_xy[sel]
-                    sol0[b_dofs[sel]] = fn(x4)
-            # the flux faces by kind of face (a prism has quadrilaterals and triangles), each flag's in (element, face) order
-            exprs, flux_calls = [self.flux[f] for f in f_flags], []
-            widths = sorted({int(n) for f in f_flags for n in faces[f][3]})
-            for nn in widths:
-                nodes = np.concatenate([faces[f][2][faces[f][3] == nn][:, :nn] for f in f_flags])
-                which = np.concatenate([np.full(int((faces[f][3] == nn).sum()), k) for k, f in enumerate(f_flags)])
-                flux_calls.append(("lineface" if dim == 2 else "triface" if nn in (3, 6, 7) else "quadface", nodes, which))
-            for l in range(1, nl):                                    # PP[l] <- PP[l] PPamr[l - 1], before the Dirichlet zeroing; then ZeroInterpolatorDirichletNodes
-                if P_amr[l - 1] is not None:
-                    P[l] = P[l].matmul(P_amr[l - 1])
-                    owned.append(P[l])
-                if bdc[l].size:
-                    P[l].mat_zero_rows(bdc[l], 0.0)
-                if bdc[l - 1].size:
-                    P[l].zero_cols(bdc[l - 1])
-            SOL, RES, EPS = ctx.vector(ndof), ctx.vector(ndof), ctx.vector(ndof)
-            owned += [SOL, RES, EPS]
+            sol0 = np.zeros(h.ndof)
+            dofs, values = h.boundary_values()
+            sol0[dofs] = values
             SOL.upload(sol0)
-            PA = P_amr[top]
-            if PA is not None:                                        # a conforming start
-                RES.matrix_mult(SOL, PA)
-                SOL.assign(RES)
-            mg = capi.Multigrid(ctx, nl)
-            owned.append(mg)
-            A = [None] * nl
-            if PA is None:
-                A[top] = K
+            h.make_conforming(SOL)
+
+            def assemble():
+                h.gen.assemble_form(K, RES, SOL, self.form)
+                h.add_flux(RES)
+
             history, converged = [], False
             for it in range(int(max_newton)):
-                gen.assemble_form(K, RES, SOL, self.form)
-                for fgeom, nodes, which in flux_calls:
-                    if dim == 2:
-                        capi.assemble_neumann_edges(ctx, self.fe, nodes, which, exprs, xs, RES, order=self.order)
-                    else:
-                        capi.assemble_neumann_faces_expr(ctx, fgeom, self.fe, nodes, which, exprs, xs, RES, order=self.order)
-                if PA is not None:
-                    EPS.matrix_mult_transpose(RES, PA)
-                    RES.assign(EPS)
-                    if A[top] is None:
-                        A[top] = capi.Mat.ptap(PA, K)
-                        owned.append(A[top])
-                    else:
-                        A[top].ptap_numeric(PA, K)
-                if bdc[top].size:
-                    A[top].mat_zero_rows(bdc[top], 1.0)
-                    RES.set(bdc[top], np.zeros(bdc[top].size))
-                rn = RES.l2_norm()
-                for l in range(top, 0, -1):
-                    if A[l - 1] is None:
-                        A[l - 1] = capi.Mat.ptap(P[l], A[l])
-                        owned.append(A[l - 1])
-                    else:
-                        A[l - 1].ptap_numeric(P[l], A[l])
-                for l in range(top):
-                    if bdc[l].size:
-                        A[l].mat_zero_rows(bdc[l], 1.0)
-                for l in range(nl):
-                    mg.set_level(l, A[l], P[l], None, smoother, omega, self.npre if l > 0 else 1, self.npost if l > 0 else 0)
-                mg.setup()
-                EPS.zero()
-                its, _ = mg.solve(RES, EPS, outer="gmres" if nl > 1 else "preonly", rtol=1e-12, atol=1e-20, maxit=int(lin_maxit))
-                if PA is not None:
-                    RES.matrix_mult(EPS, PA)
-                    EPS.assign(RES)
-                SOL.add(1.0, EPS)
-                en, sn = EPS.l2_norm(), SOL.l2_norm()
+                its, rn, en, sn = h.newton_iteration(assemble, lin_maxit, smoother, omega, self.npre, self.npost)
                 rel = en / (sn + 1e-50)
                 history.append((its, rn, rel))
                 if log:
@@ -164,18 +226,12 @@ class QuasilinearElements:
                 if rel < tol or en < 1e-12 or sn < 1e-12:
                     converged = True
                     break
-            out = {"solution": SOL.to_numpy(), "coords": xs[:ndof], "newton_history": history, "converged": converged, "dofs": ndof}
+            out = {"solution": SOL.to_numpy(), "coords": h.xs[:h.ndof], "newton_history": history, "converged": converged, "dofs": h.ndof}
             if exact is not None:
-                en = m.error_norms(fam, SOL, exact=exact, gradient=exact_gradient, order=self.order)
+                en = h.top.error_norms(h.fam, SOL, exact=exact, gradient=exact_gradient, order=self.order)
                 out["l2_error"], out["h1_error"] = en["l2"], en["h1"]
-            if selective_levels:
-                out["hanging"], out["constraints"], out["elem_levels"] = hanging[top], constraints, m.elem_levels()[0]
+            if h.selective_levels:
+                out["hanging"], out["constraints"], out["elem_levels"] = h.hanging[h.nl - 1], h.constraints, h.top.elem_levels()[0]
             return out
         finally:
-            seen = set()
-            for q in sorted(reversed(owned), key=lambda q: not isinstance(q, capi.Multigrid)):       # the cycle before the operators it holds
-                if id(q) not in seen:
-                    seen.add(id(q))
-                    q.destroy()
-            for lv in resident:
-                lv.destroy()
+            h.destroy()

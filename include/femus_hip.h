@@ -627,6 +627,26 @@ typedef struct { fh_expr_t f, a, a_u, c, c_u, c_g[3]; } fh_quasilinear_form_t;  
 int fh_generic_assembler_assemble_form(fh_generic_assembler_t as, fh_vec_t sol, const fh_quasilinear_form_t* form, fh_mat_t KK, fh_vec_t RES);
 /* the Gauss points one chunk of assemble_form's element pass takes per shape (0 beyond the last shape, and for every shape before the first assemble_form) */
 int fh_generic_assembler_form_chunks(fh_generic_assembler_t as, int gauss_chunk[3]);
+/* The TIME-DEPENDENT equation  u_t - grad.(a grad u) + c = f  on the same object (fh_transient.hip): Jacobian and residual of one Newton iteration of one
+ * theta-step of TransientSystem<NonLinearImplicitSystem> (src/08_equations/01_time_dependent/TransientSystem.cpp:62-113), scaled by dt as the callback of
+ * applications/000_tutorial/ex20_time_dependent scales it (AssembleMatrixRes, main.cpp:348-593), the old state sol_old read beside sol at every Gauss point:
+ *   RES_i = sum_g w [ -(u - uo) phi_i + dt theta (f phi_i - a grad phi_i . grad u - c phi_i)|new + dt (1 - theta) (f phi_i - a grad phi_i . grad uo - c phi_i)|old ]
+ *   KK_ij = sum_g w [ phi_i phi_j + dt theta ( a grad phi_i . grad phi_j + a_u phi_j grad phi_i . grad u + phi_i (c_u phi_j + c_g . grad phi_j) ) ]
+ * The form's programs may be compiled over EIGHT variables (x, y, z, u, ux, uy, uz, t).  |new: f, a, c at (x, u, grad u, t = time); |old: the same three programs
+ * at (x, uo, grad uo, t = time - dt); the derivative programs at the new state only; no text is rewritten.  `time` is the time at the END of the step
+ * (TransientSystem::SetUpForSolve advances _time before the assembly).  The Jacobian is the exact one, with the factor theta: ex20 (main.cpp:571) leaves theta out
+ * of its Jacobian -- an inexact Newton, not reproduced.  time, dt and theta are kernel arguments, never part of the program buffer: a step with a new time uploads
+ * nothing.  With theta == 1 nothing is evaluated at the old state, which enters through the mass term alone (a program that is NaN at uo does not matter); with
+ * theta == 0 nothing is evaluated at the new state, and KK is the mass matrix.  sol_old must cover the object's dofs as sol and RES must, and where sol is given
+ * it must have exactly sol's local size; with sol NULL any sol_old that covers the dofs is taken.
+ * assemble_form's contract otherwise (enqueue only, no allocation after the first call but a growing program buffer, KK and RES overwritten, fixed summation
+ * orders, sol NULL = 0).  Refused before anything is enqueued, the object still usable: a NULL form or sol_old, sol_old of another size, a program over more than
+ * 8 variables, c_g[d] for d >= dim, a foreign matrix, dt <= 0, theta outside [0, 1], a time, dt or theta that is not finite, and -- at the first call, when this
+ * body's own Gauss chunk and table staging are chosen -- a shape that does not fit the LDS of a workgroup.  assemble_form keeps refusing more than 7 variables. */
+int fh_generic_assembler_assemble_transient(fh_generic_assembler_t as, fh_vec_t sol, fh_vec_t sol_old, const fh_quasilinear_form_t* form, double time, double dt,
+                                            double theta, fh_mat_t KK, fh_vec_t RES);
+/* the Gauss points one chunk of assemble_transient's element pass takes per shape (0 beyond the last shape, and before the first assemble_transient) */
+int fh_generic_assembler_transient_chunks(fh_generic_assembler_t as, int gauss_chunk[3]);
 /* Open-boundary pressure term of the steady Navier-Stokes residual (src/08_equations/assemble/03_navier_stokes.hpp:185-290): on every listed boundary
  * face  aResV[k][node_i] += phi_i * tau * normal[k] * weight  for the dim velocity components (Q2 face nodes), tau = the prescribed pressure -- one
  * number per face (tau) or expression face_expr[f] of the nexpr expressions evaluated at the face Gauss point, as the bdc callback is (:280) -- and
