@@ -396,6 +396,19 @@ class Mat:
         _chk(self.L.fh_mat_transpose(self.h, ctypes.byref(h)))
         return Mat(self.ctx, h)
 
+    def block_system(self, m):
+        """the pattern of kron(ones(m, m), self) with zero values (fh_mat_block_system): the matrix of m stacked variables of one family on the pattern self,
+        unknown (k, i) = k rows + i, made on the device"""
+        h = ctypes.c_void_p()
+        _chk(self.L.fh_mat_block_system(self.h, int(m), ctypes.byref(h)))
+        return Mat(self.ctx, h)
+
+    def block_diagonal(self, m):
+        """kron(I_m, self) with self's values (fh_mat_block_diagonal): the transfer of m stacked variables of one family, made on the device"""
+        h = ctypes.c_void_p()
+        _chk(self.L.fh_mat_block_diagonal(self.h, int(m), ctypes.byref(h)))
+        return Mat(self.ctx, h)
+
     def matrix_PtAP(self, P, A, reuse=False):
         """self = P^T A P ; call as C = Mat.ptap(P, A) for the first product"""
         h = self.h if reuse else ctypes.c_void_p()
@@ -1193,6 +1206,20 @@ class GenericAssembler:
         _chk(self.L.fh_generic_assembler_transient_chunks(self.h, gc))
         return {s: gc[k] for k, s in enumerate(self.shapes[:3])}
 
+    def assemble_system(self, K, res, sol, form):
+        """K and res are overwritten with the Jacobian and residual of the SystemForm at sol (None: 0): fh_generic_assembler_assemble_system.  K is
+        S.block_system(form.m) of the matrix S this object was created on, sol and res hold form.m * ndof entries, unknown (k, i) = k ndof + i"""
+        _chk(self.L.fh_generic_assembler_assemble_system(self.h, sol.h if sol is not None else None, form.pointer() if form is not None else None,
+                                                         K.h if K is not None else None, res.h))
+        self._system_m = form.m
+
+    def system_chunks(self, m=None):
+        """{shape: (Gauss points per LDS chunk, lanes per element)} of assemble_system's element pass with m variables (None: as many as the last
+        assemble_system of this object had); 0 before the first such call"""
+        gc, ln = (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+        _chk(self.L.fh_generic_assembler_system_chunks(self.h, int(m if m is not None else getattr(self, "_system_m", 1)), gc, ln))
+        return {s: (gc[k], ln[k]) for k, s in enumerate(self.shapes[:3])}
+
     def info(self):
         """elements per 256-thread workgroup of the element pass by shape, bytes held on the device, bytes one assembly cannot avoid moving, device
         allocations made so far"""
@@ -1586,6 +1613,80 @@ class TransientForm(QuasilinearForm):
     """the same programs for GenericAssembler.assemble_transient (u_t - div(a grad u) + c = f): texts over eight variables, the last the time"""
 
     VARIABLES = "x,y,z,u,ux,uy,uz,t"
+
+
+class SystemForm:
+    """fh_system_form_t: the coefficient programs of m = 1 .. 4 coupled equations  -sum_l div(A_kl grad u_l) + c_k = f_k  of one family for
+    GenericAssembler.assemble_system.  f[k], A[k][l], A_u[k][p][l] (= dA_kp/du_l), c[k], c_u[k][l] (= dc_k/du_l), c_g[k][l][d] (= dc_k/d(d_d u_l)): nested lists
+    of exactly these shapes (c_g's innermost of at most 3), or None for a whole argument; every entry a text over SystemForm.variables(m) (compiled here and
+    owned by this object), an Expr of the caller's (left alone by destroy()) or None.  A missing A[k][k] is 1, every other missing program 0.
+    ex04 in the order multigrid needs (row u: -lap u + v = 0, row v: -lap v = -f):  m=2, f=[None, "-(...)"], c=["u1", None], c_u=[[None, "1"], [None, None]]"""
+
+    MAXM = 4
+
+    class _Struct(ctypes.Structure):
+        _fields_ = [("m", ctypes.c_int), ("f", ctypes.c_void_p * 4), ("A", ctypes.c_void_p * 16), ("A_u", ctypes.c_void_p * 64), ("c", ctypes.c_void_p * 4),
+                    ("c_u", ctypes.c_void_p * 16), ("c_g", ctypes.c_void_p * 48)]
+
+    @staticmethod
+    def variables(m):
+        return ",".join(["x", "y", "z"] + ["u%d" % k for k in range(m)] + ["u%d%s" % (k, d) for k in range(m) for d in "xyz"])
+
+    def __init__(self, m, f=None, A=None, A_u=None, c=None, c_u=None, c_g=None):
+        m = int(m)
+        if not 1 <= m <= self.MAXM:
+            raise ValueError("SystemForm: %d variables, 1 .. %d are served" % (m, self.MAXM))
+        self.m, self._owned, self.exprs = m, [], {}
+        names = self.variables(m)
+
+        def walk(name, value, shape, index=()):
+            """every (index, entry) of one argument, its list shapes checked"""
+            if value is None:
+                return
+            if not shape:
+                yield index, value
+                return
+            label = name + "".join("[%d]" % i for i in index)
+            if isinstance(value, (str, Expr)) or not hasattr(value, "__len__"):
+                raise ValueError("SystemForm: %s must be a list of %d entries" % (label, shape[0]))
+            directions = name == "c_g" and len(shape) == 1            # c_g's innermost list: one entry per space dimension, at most 3
+            if len(value) > shape[0] if directions else len(value) != shape[0]:
+                raise ValueError("SystemForm: %s has %d entries, %s%d are expected" % (label, len(value), "at most " if directions else "", shape[0]))
+            for i, v in enumerate(value):
+                yield from walk(name, v, shape[1:], index + (i,))
+
+        try:
+            for name, value, shape in (("f", f, (m,)), ("A", A, (m, m)), ("A_u", A_u, (m, m, m)), ("c", c, (m,)), ("c_u", c_u, (m, m)), ("c_g", c_g, (m, m, 3))):
+                for index, e in walk(name, value, shape):
+                    label = name + "".join("[%d]" % i for i in index)
+                    if not isinstance(e, Expr):
+                        e = Expr(str(e), names)
+                        self._owned.append(e)
+                    if e.n_variables() > 3 + 4 * m:
+                        raise ValueError("SystemForm: the program %s has %d variables, at most %d (%s) are served" % (label, e.n_variables(), 3 + 4 * m, names))
+                    self.exprs[(name, index)] = e
+        except BaseException:
+            self.destroy()
+            raise
+        self._refresh()
+
+    def _refresh(self):
+        s = self._Struct()
+        s.m = self.m
+        stride = {"f": (1,), "A": (4, 1), "A_u": (16, 4, 1), "c": (1,), "c_u": (4, 1), "c_g": (12, 3, 1)}
+        for (name, index), e in self.exprs.items():
+            if e.h is not None:
+                getattr(s, name)[sum(i * w for i, w in zip(index, stride[name]))] = e.h.value
+        self._s = s
+
+    def pointer(self):
+        return ctypes.cast(ctypes.pointer(self._s), ctypes.c_void_p)
+
+    def destroy(self):
+        for e in self._owned:
+            e.destroy()
+        self._owned, self.exprs = [], {}
+        self._refresh()
 
 
 def system_elem_dofs(mesh, fes):

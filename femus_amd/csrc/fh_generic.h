@@ -63,6 +63,15 @@ struct fh_generic_assembler_s {
   int tr_gcm[3] = {0, 0, 0};
   bool tr_tl[3] = {false, false, false};
   size_t tr_lds[3] = {0, 0, 0};
+  // the system element body (fh_system.hip), per number of variables m = 1 .. 4: lanes per element, Gauss chunk, table staging and LDS per shape, the lanes and
+  // LDS of the block row pass, and the work buffers of m^2 / m times the scalar size (m = 1: the scalar ones), all made at the first assemble_system with that m
+  bool sys_ready[5] = {false, false, false, false, false};
+  int sys_lanes[5][3] = {}, sys_gcm[5][3] = {};
+  bool sys_tl[5][3] = {};
+  size_t sys_lds[5][3] = {};
+  int sys_lpr[5] = {0, 0, 0, 0, 0};
+  size_t sys_row_lds[5] = {0, 0, 0, 0, 0};
+  double *d_sysK[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *d_sysF[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int64_t device_bytes = 0, algorithmic_bytes = 0, device_allocations = 0;
   std::vector<void*> dv;         // every device allocation but d_prog
 };

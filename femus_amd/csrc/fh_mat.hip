@@ -1022,6 +1022,69 @@ int fh_mat_refresh_transpose(fh_mat_t A) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Block matrices of m stacked variables of one family (unknown (k, i) = k rows + i), made by kernels from the resident CSR arrays; the row table alone is
+// scanned on the host, from the host copy every matrix keeps.  Columns ascend in every row.
+//   block_system(S, m)   = kron(ones(m, m), S), values zero: row (k, i) starts at k m nnz + m rowptr[i], block l of it at l len(i) further
+//   block_diagonal(P, m) = kron(I_m, P) with P's values: row (k, i) is P's row i, its columns shifted by k cols
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_block_system_cols(int rows, int m, int ncols, long long nnz, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                           int* __restrict__ out) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;      // (k, i, l)
+  if (idx >= (long long)rows * m * m) return;
+  const int l = (int)(idx % m), i = (int)((idx / m) % rows), k = (int)(idx / ((long long)m * rows));
+  const int rs = rowptr[i], n = rowptr[i + 1] - rs;
+  int* o = out + (long long)k * m * nnz + (long long)m * rs + (long long)l * n;
+  for (int t = 0; t < n; t++) o[t] = l * ncols + col[rs + t];
+}
+
+__global__ __launch_bounds__(256) void k_block_diagonal_fill(int m, int ncols, long long nnz, const int* __restrict__ col, const double* __restrict__ val,
+                                                             int* __restrict__ ocol, double* __restrict__ oval) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;      // (k, entry)
+  if (idx >= nnz * m) return;
+  const int k = (int)(idx / nnz);
+  const long long e = idx - (long long)k * nnz;
+  ocol[idx] = k * ncols + col[e];
+  oval[idx] = val[e];
+}
+
+static int block_matrix(const char* who, fh_mat_t A, int m, bool diagonal, fh_mat_t* out) {
+  FH_GUARD_BEGIN
+  FH_REQUIRE(A && out, "%s: null argument", who);
+  FH_REQUIRE(m >= 1 && m <= 4, "%s: %d variables, 1 .. 4 are served", who, m);
+  FH_REQUIRE((int)A->h_rowptr.size() == A->m + 1, "%s: the matrix has no host row table", who);
+  const int rows = A->m, f = diagonal ? 1 : m;
+  const long long nnz = A->nnz, total = nnz * m * f;
+  FH_REQUIRE(total < 2147483647ll && (long long)rows * m < 2147483647ll && (long long)A->n * m < 2147483647ll, "%s: the block matrix overflows int32", who);
+  *out = nullptr;
+  std::vector<int> rp((size_t)rows * m + 1);
+  for (int k = 0; k < m; k++)
+    for (int i = 0; i < rows; i++) rp[(size_t)k * rows + i] = (int)(k * f * nnz + (long long)f * A->h_rowptr[i]);
+  rp[(size_t)rows * m] = (int)total;
+  fh_ctx_t c = A->ctx;
+  fh_mat_t B = nullptr;
+  if (fh_mat_alloc_device_pattern(c, rows * m, A->n * m, std::move(rp), &B)) {
+    fh_mat_destroy(B);
+    return 2;
+  }
+  if (diagonal) {
+    if (total) hipLaunchKernelGGL(k_block_diagonal_fill, dim3(fh_div_up(total, 256)), dim3(256), 0, c->stream, m, A->n, nnz, A->d_col, A->d_val, B->d_col, B->d_val);
+  } else {
+    if (rows) hipLaunchKernelGGL(k_block_system_cols, dim3(fh_div_up((long long)rows * m * m, 256)), dim3(256), 0, c->stream, rows, m, A->n, nnz, A->d_rowptr, A->d_col, B->d_col);
+  }
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess || fh_mat_build_rowblocks(B, c->spmv_tile)) {
+    fh_mat_destroy(B);
+    fh_set_error("%s: the fill kernel failed", who);
+    return 1;
+  }
+  *out = B;
+  return 0;
+  FH_GUARD_END(who)
+}
+
+extern "C" int fh_mat_block_system(fh_mat_t S, int m, fh_mat_t* out) { return block_matrix("fh_mat_block_system", S, m, false, out); }
+extern "C" int fh_mat_block_diagonal(fh_mat_t P, int m, fh_mat_t* out) { return block_matrix("fh_mat_block_diagonal", P, m, true, out); }
+
+// ------------------------------------------------------------------------------------------------
 // norms (l1 = max column sum, linfty = max row sum) -- setup/diagnostic only: via the host
 // ------------------------------------------------------------------------------------------------
 extern "C" int fh_mat_norm(fh_mat_t A, int kind, double* out) {

@@ -15,9 +15,14 @@ FAMILY = {"linear": 0, "serendipity": 1, "biquadratic": 2}
 class ResidentHierarchy:
     """What the Newton drivers on resident element meshes share (QuasilinearElements here, transient.TransientQuasilinearElements): the levels, transfers,
     boundary lists, P_amr wiring of flagged levels, pattern, plan, flux faces, work vectors and the Multigrid object, made once and kept until destroy(); and one
-    nonlinear iteration on them.  dirichlet: {face flag: Expr over "x,y,z,t" or None (= 0)}; flux: {face flag: Expr}."""
+    nonlinear iteration on them.  dirichlet: {face flag: Expr over "x,y,z,t" or None (= 0)}; flux: {face flag: Expr}.
+    nvars > 1 (system.SystemElements): that many variables of the one family stacked, unknown (k, i) = k ndof + i; dirichlet and flux are lists of nvars such
+    dicts; the boundary rows of a level are k ndof_l + the Dirichlet dofs of variable k and the hanging dofs, for every k; the transfers and P_amr are
+    Mat.block_diagonal of the scalar ones (PP after its P_amr product); K is Mat.block_system of the scalar pattern S, on which the plan is made; the flux faces
+    of every variable are integrated once into one vector of the system's size."""
 
-    def __init__(self, ctx, level0, fe, nlevels, dirichlet, flux, order, selective_levels=0, flag=None, amr_mode="reference"):
+    def __init__(self, ctx, level0, fe, nlevels, dirichlet, flux, order, selective_levels=0, flag=None, amr_mode="reference", nvars=1):
+        nv = self.nvars = int(nvars)
         nl, fam = int(nlevels), FAMILY[fe]
         selective_levels = int(selective_levels)
         if selective_levels and (not 0 < selective_levels < nl or flag is None):
@@ -27,8 +32,8 @@ class ResidentHierarchy:
         self.ctx, self.fe, self.fam, self.nl, self.order, self.selective_levels = ctx, fe, fam, nl, order, selective_levels
         self.dirichlet, self.flux = dirichlet, flux
         top, n_uniform = nl - 1, nl - selective_levels
-        d_flags = sorted(int(f) for f in dirichlet)
-        f_flags = sorted(int(f) for f in flux)
+        dirichlets, fluxes = ([dirichlet], [flux]) if nv == 1 else (list(dirichlet), list(flux))
+        d_flags = [sorted(int(f) for f in d) for d in dirichlets]
         owned = self.owned = []                                       # every device object made here but the levels
         resident = self.resident = [capi.ElementMesh.from_arrays(ctx, *level0)]
         try:
@@ -50,7 +55,7 @@ class ResidentHierarchy:
             self.hanging = hanging
             bdc, P = self.bdc, self.P = [], [None]
             for l, lv in enumerate(resident):
-                bdc.append(np.union1d(lv.boundary_dofs(fam, d_flags), hanging[l]).astype(np.int32))
+                bdc.append(np.concatenate([k * lv.own[fam] + np.union1d(lv.boundary_dofs(fam, d_flags[k]), hanging[l]) for k in range(nv)]).astype(np.int32))
                 if l:
                     P.append(resident[l - 1].prolongator(lv, fam))
                     owned.append(P[l])
@@ -58,27 +63,34 @@ class ResidentHierarchy:
             owned.append(self.K)
             self.gen = capi.GenericAssembler.from_mesh(m, fam, self.K, order=order)
             owned.append(self.gen)
-            self.b_dofs, self.b_flag, self.b_xy = m.boundary_owners(fam, d_flags)
-            faces = {f: m.boundary_faces(fam, [f]) for f in f_flags}
+            if nv > 1:                                                # the plan stays on the scalar pattern S; the system's matrix is its block matrix
+                self.S, self.K = self.K, self.K.block_system(nv)
+                owned.append(self.K)
             self.xs, self.ndof, self.dim = m.coords(), m.own[fam], m.dim
-            # the flux faces by kind of face (a prism has quadrilaterals and triangles), each flag's in (element, face) order
-            self.flux_exprs, self.flux_calls = [flux[f] for f in f_flags], []
-            widths = sorted({int(n) for f in f_flags for n in faces[f][3]})
-            for nn in widths:
-                nodes = np.concatenate([faces[f][2][faces[f][3] == nn][:, :nn] for f in f_flags])
-                which = np.concatenate([np.full(int((faces[f][3] == nn).sum()), k) for k, f in enumerate(f_flags)])
-                self.flux_calls.append(("lineface" if self.dim == 2 else "triface" if nn in (3, 6, 7) else "quadface", nodes, which))
+            self.owners = [m.boundary_owners(fam, d_flags[k]) for k in range(nv)]
+            self.b_dofs, self.b_flag, self.b_xy = self.owners[0]
+            self.flux_exprs, self.flux_calls = self.flux_faces(fluxes[0])
+            self.dirichlets, self.fluxes = dirichlets, fluxes
             for l in range(1, nl):                                    # PP[l] <- PP[l] PPamr[l - 1], before the Dirichlet zeroing; then ZeroInterpolatorDirichletNodes
                 if P_amr[l - 1] is not None:
                     P[l] = P[l].matmul(P_amr[l - 1])
+                    owned.append(P[l])
+                if nv > 1:
+                    P[l] = P[l].block_diagonal(nv)
                     owned.append(P[l])
                 if bdc[l].size:
                     P[l].mat_zero_rows(bdc[l], 0.0)
                 if bdc[l - 1].size:
                     P[l].zero_cols(bdc[l - 1])
-            self.SOL, self.RES, self.EPS = ctx.vector(self.ndof), ctx.vector(self.ndof), ctx.vector(self.ndof)
+            n = nv * self.ndof
+            self.SOL, self.RES, self.EPS = ctx.vector(n), ctx.vector(n), ctx.vector(n)
             owned += [self.SOL, self.RES, self.EPS]
             self.PA = P_amr[top]
+            if nv > 1:
+                if self.PA is not None:
+                    self.PA = self.PA.block_diagonal(nv)
+                    owned.append(self.PA)
+                self.FLUX = self.system_flux()
             self.mg = capi.Multigrid(ctx, nl)
             owned.append(self.mg)
             self.A = [None] * nl
@@ -88,20 +100,51 @@ class ResidentHierarchy:
             self.destroy()
             raise
 
-    def boundary_values(self, time=0.0, zeros=False):
-        """(dofs, values): the Dirichlet dofs whose flag has an expression, and that expression at their coordinates and `time`; with zeros also the dofs of
-        the flags given as None, with the value 0 they stand for (a start vector of zeros has them already, a state that was set from outside has not)"""
+    def flux_faces(self, flux):
+        """(exprs, calls) of one variable's flux faces: by kind of face (a prism has quadrilaterals and triangles), each flag's in (element, face) order"""
+        f_flags = sorted(int(f) for f in flux)
+        faces = {f: self.top.boundary_faces(self.fam, [f]) for f in f_flags}
+        calls = []
+        widths = sorted({int(n) for f in f_flags for n in faces[f][3]})
+        for nn in widths:
+            nodes = np.concatenate([faces[f][2][faces[f][3] == nn][:, :nn] for f in f_flags])
+            which = np.concatenate([np.full(int((faces[f][3] == nn).sum()), k) for k, f in enumerate(f_flags)])
+            calls.append(("lineface" if self.dim == 2 else "triface" if nn in (3, 6, 7) else "quadface", nodes, which))
+        return [flux[f] for f in f_flags], calls
+
+    def system_flux(self):
+        """the flux faces of every variable, integrated once into a scalar vector each and composed into one vector of the system's size (set-up)"""
+        if not any(self.fluxes):
+            return None
+        scalar, parts = self.ctx.vector(self.ndof), []
+        try:
+            for k in range(self.nvars):
+                scalar.zero()
+                self.add_flux(scalar, *self.flux_faces(self.fluxes[k]))
+                parts.append(scalar.to_numpy())
+        finally:
+            scalar.destroy()
+        out = self.ctx.vector_from(np.concatenate(parts))
+        self.owned.append(out)
+        return out
+
+    def boundary_values(self, time=0.0, zeros=False, var=0):
+        """(dofs, values): the Dirichlet dofs of variable `var` whose flag has an expression, numbered in the system, and that expression at their coordinates
+        and `time`; with zeros also the dofs of the flags given as None, with the value 0 they stand for (a start vector of zeros has them already, a state
+        that was set from outside has not)"""
+        b_dofs, b_flag, b_xy = self.owners[var]
+        b_dofs = b_dofs + var * self.ndof if var else b_dofs
         dofs, values = [], []
-        for f in np.unique(self.b_flag):
-            fn = self.dirichlet[int(f)]
-            sel = self.b_flag == f
+        for f in np.unique(b_flag):
+            fn = self.dirichlets[var][int(f)]
+            sel = b_flag == f
             if fn is not None:
                 x4 = np.zeros((int(sel.sum()), 4))
-                x4[:, :self.dim], x4[:, 3] = self.b_xy[sel], time
-                dofs.append(self.b_dofs[sel])
+                x4[:, :self.dim], x4[:, 3] = b_xy[sel], time
+                dofs.append(b_dofs[sel])
                 values.append(fn(x4))
             elif zeros:
-                dofs.append(self.b_dofs[sel])
+                dofs.append(b_dofs[sel])
                 values.append(np.zeros(int(sel.sum())))
         return (np.concatenate(dofs), np.concatenate(values)) if dofs else (np.zeros(0, np.int32), np.zeros(0))
 
@@ -111,13 +154,18 @@ class ResidentHierarchy:
             self.RES.matrix_mult(v, self.PA)
             v.assign(self.RES)
 
-    def add_flux(self, res):
-        """res += the integrals of the flux faces"""
-        for fgeom, nodes, which in self.flux_calls:
+    def add_flux(self, res, exprs=None, calls=None):
+        """res += the integrals of the flux faces (of the one variable, or those given); a system adds the vector composed at set-up"""
+        if self.nvars > 1 and calls is None:
+            if self.FLUX is not None:
+                res.add(1.0, self.FLUX)
+            return
+        exprs, calls = (self.flux_exprs, self.flux_calls) if calls is None else (exprs, calls)
+        for fgeom, nodes, which in calls:
             if self.dim == 2:
-                capi.assemble_neumann_edges(self.ctx, self.fe, nodes, which, self.flux_exprs, self.xs, res, order=self.order)
+                capi.assemble_neumann_edges(self.ctx, self.fe, nodes, which, exprs, self.xs, res, order=self.order)
             else:
-                capi.assemble_neumann_faces_expr(self.ctx, fgeom, self.fe, nodes, which, self.flux_exprs, self.xs, res, order=self.order)
+                capi.assemble_neumann_faces_expr(self.ctx, fgeom, self.fe, nodes, which, exprs, self.xs, res, order=self.order)
 
     def newton_iteration(self, assemble, lin_maxit, smoother, omega, npre, npost):
         """assemble() has to leave Jacobian and residual at SOL in K and RES; then, on a flagged top level, RES <- P_amr^T RES and the operator P_amr^T KK P_amr;

@@ -173,6 +173,12 @@ int fh_mat_restrict_check(fh_mat_t src, int nrows, const int* rows, const int* n
 int fh_mat_value_map(fh_mat_t dst, fh_mat_t src, const int* src_row /* [dst m] or NULL */, const int* src_col /* [dst n] or NULL */, fh_index_t* map);
 int fh_mat_get_diagonal(fh_mat_t A, fh_vec_t d);                 /* get_diagonal :224 */
 int fh_mat_transpose(fh_mat_t A, fh_mat_t* At);                  /* get_transpose :227 (PetscMatrix.cpp:1031-1070) */
+/* Block matrices of m = 1 .. 4 stacked variables of one family, unknown (k, i) = k rows + i (KKoffset order on one process), made by kernels from the
+ * resident CSR arrays (no download; the row table is scanned from the host copy every matrix keeps); columns ascend in every row.
+ * block_system: the pattern of kron(ones(m, m), S), values zero -- row (k, i) starts at k m nnz_S + m rowptr_S[i], block l of it l len_S(i) further.
+ * block_diagonal: kron(I_m, P) with P's values (the transfers of a system of one family). */
+int fh_mat_block_system(fh_mat_t S, int m, fh_mat_t* out);
+int fh_mat_block_diagonal(fh_mat_t P, int m, fh_mat_t* out);
 /* matrix_PtAP(P, A, reuse) :183 (PetscMatrix.cpp:733-751): C = P^T A P.  *C==NULL: symbolic+numeric; else numeric reuse */
 int fh_mat_ptap(fh_mat_t P, fh_mat_t A, fh_mat_t* C);
 /* general sparse product C = A*B (symbolic + numeric); matrix_ABC :186 (PetscMatrix.cpp:833-856), matrix_RightMatMult :189,
@@ -647,6 +653,27 @@ int fh_generic_assembler_assemble_transient(fh_generic_assembler_t as, fh_vec_t 
                                             double theta, fh_mat_t KK, fh_vec_t RES);
 /* the Gauss points one chunk of assemble_transient's element pass takes per shape (0 beyond the last shape, and before the first assemble_transient) */
 int fh_generic_assembler_transient_chunks(fh_generic_assembler_t as, int gauss_chunk[3]);
+/* A COUPLED SYSTEM of m = 1 .. 4 variables of the object's family on the same object (fh_system.hip): equation k is
+ *   - sum_l div(A_kl grad u_l) + c_k = f_k   with A_kl(x, U), c_k(x, U, grad U), and one Newton step forms
+ *   RES_(k,i)      = sum_g [ f_k phi_i - sum_l A_kl (grad phi_i . grad u_l) - c_k phi_i ] w
+ *   KK_(k,i),(l,j) = sum_g [ A_kl (grad phi_i . grad phi_j) + (grad phi_i . W_kl) phi_j + phi_i ( C_kl phi_j + D_kl . grad phi_j ) ] w
+ *   W_kl = sum_p A_u[k][p][l] grad u_p (A_u[k][p][l] = dA_kp/du_l),  C_kl = c_u[k][l] = dc_k/du_l,  D_kl = c_g[k][l][.] = dc_k/d(grad u_l)
+ * The programs are over x, y, z, u0 .. u{m-1}, u0x, u0y, u0z, u1x, ...: u_k is variable 3 + k, d_d u_k variable 3 + m + 3 k + d.  Only the entries with
+ * indices below m are read.  A missing A[k][k] is 1; every other missing program is 0 and its term is left out.  Unknown (k, i) has the number k ndof + i:
+ * sol and RES hold m ndof entries, KK is fh_mat_block_system(S, m) of the matrix S the object was created on (m = 1: S itself serves), which must be alive.
+ * assemble_form's contract otherwise (enqueue only, KK and RES overwritten, fixed summation orders, no atomics, sol NULL = 0).  The first call with a given m
+ * chooses the launch geometry and allocates work buffers of m^2 and m times the scalar size (counted by fh_generic_assembler_info, freed with the object); later
+ * calls with that m allocate nothing but a growing program buffer.  Refused before anything is enqueued, the object still usable: m outside 1 .. 4, a NULL
+ * form, c_g[k][l][d] for d >= dim, a program over more than 3 + 4 m variables, a matrix that is not m ndof square with m^2 nnz_S entries, vectors shorter than
+ * m ndof, and -- at the first call with that m -- a shape or a row that does not fit the LDS of a workgroup, or work buffers that do not fit the device. */
+typedef struct {
+  int m;
+  fh_expr_t f[4], A[4][4], A_u[4][4][4], c[4], c_u[4][4], c_g[4][4][3];
+} fh_system_form_t;
+int fh_generic_assembler_assemble_system(fh_generic_assembler_t as, fh_vec_t sol, const fh_system_form_t* form, fh_mat_t KK, fh_vec_t RES);
+/* Gauss points per chunk and lanes per element of assemble_system's element pass with m variables, per shape (0 beyond the last shape and before the first
+ * assemble_system with that m) */
+int fh_generic_assembler_system_chunks(fh_generic_assembler_t as, int m, int gauss_chunk[3], int lanes[3]);
 /* Open-boundary pressure term of the steady Navier-Stokes residual (src/08_equations/assemble/03_navier_stokes.hpp:185-290): on every listed boundary
  * face  aResV[k][node_i] += phi_i * tau * normal[k] * weight  for the dim velocity components (Q2 face nodes), tau = the prescribed pressure -- one
  * number per face (tau) or expression face_expr[f] of the nexpr expressions evaluated at the face Gauss point, as the bdc callback is (:280) -- and
