@@ -2,11 +2,14 @@
 // (fh_elemplan.hip), sees of it.  Both builders make the same object; assemble, set_coords, info and destroy do not know which one did.
 #pragma once
 #include "fh_internal.h"
+#include <algorithm>
 
 constexpr int GP_THREADS = 256;
 constexpr size_t GP_LDS_BUDGET = 64 * 1024;   // per workgroup: two workgroups and more per CU (160 KB of LDS), and no opt-in to large dynamic LDS needed
 constexpr size_t GP_PROG_BYTES = 4096;        // first size of the source program's buffer
 constexpr int GEN_NC = 27;                    // most nodes of an element (HEX27); the node stride of the one-shot kernel
+// entries of the nc x nc element matrix a lane holds in the bodies that form every (i, j): 729 of HEX27 on 64 lanes, at most 4 L where elements share a wave
+constexpr int gp_entries_per_lane(int L) { return L == 64 ? (GEN_NC * GEN_NC + 63) / 64 : 4; }
 
 struct GenRowShapes {
   int row_base[3];        // first element-row id of the shape (INT_MAX: no such shape)
@@ -24,15 +27,25 @@ struct GenMesh {
   std::vector<int> adj_ptr;                                               // [ndof + 1] the element rows of dof d are adj_ptr[d] .. adj_ptr[d + 1]
 };
 
+// The launch geometry of one element body on the shapes of one object: lanes per element, Gauss points per chunk, whether the shape's tables are staged in
+// LDS beside the chunk, and the dynamic LDS of a workgroup.  Filled by gp_plan_body, all shapes or none
+struct GenBodyPlan {
+  bool ready = false;
+  int lanes[3] = {0, 0, 0}, gcm[3] = {0, 0, 0};
+  bool tl[3] = {false, false, false};
+  size_t lds[3] = {0, 0, 0};
+};
+
 struct fh_generic_assembler_s {
   fh_ctx_t ctx = nullptr;
   uint64_t mat_uid = 0;          // the matrix of create: its uid and non-zero count, never its address
   int mat_nnz = 0;
   int ndof = 0, nnode = 0, dim = 0, ns = 0, nel = 0;
   int shapes[3] = {-1, -1, -1};  // shape codes in the order of their first elements
-  int nc[3] = {0, 0, 0}, ng[3] = {0, 0, 0}, lanes[3] = {0, 0, 0}, gcm[3] = {0, 0, 0}, nslot[3] = {0, 0, 0};
-  bool tl[3] = {false, false, false};
-  size_t lds[3] = {0, 0, 0};
+  int nc[3] = {0, 0, 0}, ng[3] = {0, 0, 0}, nslot[3] = {0, 0, 0};
+  // one plan per element body: the Poisson body's at create, the others at the first call that needs them -- the quasilinear (fh_quasilinear.hip) and the
+  // transient body (fh_transient.hip) on the Poisson body's lanes, the system body (fh_system.hip) per number of variables m = 1 .. 4 on lanes of its own
+  GenBodyPlan poisson, form, transient, sys[5];
   GenRowShapes rows;
   int* d_ed[3] = {nullptr, nullptr, nullptr};
   double *d_w[3] = {nullptr, nullptr, nullptr}, *d_phi[3] = {nullptr, nullptr, nullptr}, *d_dphi[3] = {nullptr, nullptr, nullptr};
@@ -53,22 +66,8 @@ struct fh_generic_assembler_s {
   std::vector<int> code;
   std::vector<double> consts;
   bool have_prog = false;
-  // the quasilinear element body (fh_quasilinear.hip): its Gauss chunk, table staging and LDS per shape, chosen at the first assemble_form
-  bool form_ready = false;
-  int form_gcm[3] = {0, 0, 0};
-  bool form_tl[3] = {false, false, false};
-  size_t form_lds[3] = {0, 0, 0};
-  // the transient element body (fh_transient.hip): the same three of its own, chosen at the first assemble_transient
-  bool tr_ready = false;
-  int tr_gcm[3] = {0, 0, 0};
-  bool tr_tl[3] = {false, false, false};
-  size_t tr_lds[3] = {0, 0, 0};
-  // the system element body (fh_system.hip), per number of variables m = 1 .. 4: lanes per element, Gauss chunk, table staging and LDS per shape, the lanes and
-  // LDS of the block row pass, and the work buffers of m^2 / m times the scalar size (m = 1: the scalar ones), all made at the first assemble_system with that m
-  bool sys_ready[5] = {false, false, false, false, false};
-  int sys_lanes[5][3] = {}, sys_gcm[5][3] = {};
-  bool sys_tl[5][3] = {};
-  size_t sys_lds[5][3] = {};
+  // the system body's block row pass and work buffers, per m: lanes per row and LDS, Kb / Fb of m^2 / m times the scalar size (m = 1: the scalar ones), made
+  // with sys[m]
   int sys_lpr[5] = {0, 0, 0, 0, 0};
   size_t sys_row_lds[5] = {0, 0, 0, 0, 0};
   double *d_sysK[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *d_sysF[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -89,6 +88,49 @@ int gp_plan_work(const char* who, fh_generic_assembler_t as, const GenMesh& m, f
 // consts then code into the object's program buffer, when they are not what is already there (`who`: the entry point, for the refusals).  A set of several
 // programs goes through here laid back to back in both arrays, its directory with the caller: the buffer of a single program is the set of one
 int gp_upload_program(const char* who, fh_generic_assembler_t as, std::vector<int>& code, std::vector<double>& consts);
+// The plan of one element body: per shape the lanes given, the largest Gauss chunk <= 32 with which the 256 / lanes elements of a workgroup, at
+// elem_doubles(nc, gc) doubles of LDS each, fit GP_LDS_BUDGET -- halved until it fits, or with `evened` stepped down by one and then evened out over the chunks
+// it makes (ng = 16 at a limit of 14 goes as 8 + 8, not 14 + 2) -- and the tables staged where they still fit beside it.  Refusals, per shape in this order:
+// under every_entry (the bodies that form every (i, j); the Poisson body forms pairs) the gp_entries_per_lane(L) entries of each of the L lanes do not cover
+// the nc^2 entries of `entries_of` ("an element", "a block");
+// the shape does not fit at one point per chunk (`body` ends that message: "" or " with the ... element body").  plan is written only when every shape fits
+template <class Doubles>
+int gp_plan_body(const char* who, fh_generic_assembler_t as, const int lanes[3], Doubles elem_doubles, bool evened, bool every_entry, const char* entries_of,
+                 const char* body, GenBodyPlan& plan) {
+  GenBodyPlan P;
+  for (int k = 0; k < as->ns; k++) {
+    const int L = lanes[k], epg = GP_THREADS / L, nc = as->nc[k], ng = as->ng[k];
+    FH_REQUIRE(!every_entry || gp_entries_per_lane(L) * L >= nc * nc, "%s: shape %d: %d entries of %s on %d lanes", who, as->shapes[k], nc * nc, entries_of, L);
+    const auto bytes = [&](int gc) { return epg * elem_doubles(nc, gc) * sizeof(double); };
+    int gc = std::min(ng, 32);
+    while (gc > 1 && bytes(gc) > GP_LDS_BUDGET) gc = evened ? gc - 1 : (gc + 1) / 2;
+    FH_REQUIRE(bytes(gc) <= GP_LDS_BUDGET, "%s: shape %d does not fit the LDS of a workgroup%s", who, as->shapes[k], body);
+    if (evened) {
+      const int nchunk = (ng + gc - 1) / gc;
+      gc = (ng + nchunk - 1) / nchunk;
+    }
+    const size_t tab = ((size_t)ng * (1 + nc + nc * as->dim)) * sizeof(double);
+    P.lanes[k] = L, P.gcm[k] = gc;
+    P.tl[k] = bytes(gc) + tab <= GP_LDS_BUDGET;
+    P.lds[k] = bytes(gc) + (P.tl[k] ? tab : 0);
+  }
+  P.ready = true;
+  plan = P;
+  return 0;
+}
+// what the *_chunks exports report of a plan: 0 for a shape the mesh does not have, and for every shape before the plan is made
+void gp_read_plan(fh_generic_assembler_t as, const GenBodyPlan& plan, int gauss_chunk[3], int lanes[3]);
+// the <L, TL> kernel of shape k's plan: f(std::integral_constant<int, L>, std::bool_constant<TL>) is called with the plan's two
+template <class F>
+void gp_dispatch(const GenBodyPlan& plan, int k, F&& f) {
+  using std::integral_constant;
+  const bool tl = plan.tl[k];
+  switch (plan.lanes[k]) {
+    case 16: tl ? f(integral_constant<int, 16>(), std::true_type()) : f(integral_constant<int, 16>(), std::false_type()); break;
+    case 32: tl ? f(integral_constant<int, 32>(), std::true_type()) : f(integral_constant<int, 32>(), std::false_type()); break;
+    default: tl ? f(integral_constant<int, 64>(), std::true_type()) : f(integral_constant<int, 64>(), std::false_type()); break;
+  }
+}
 // the checks assemble and assemble_form make of their matrix and vectors
 int gp_check_call(const char* who, fh_generic_assembler_t as, fh_vec_t sol, fh_mat_t KK, fh_vec_t RES);
 // the row pass: Kb / Fb into KK's values and RES

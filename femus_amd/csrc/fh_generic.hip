@@ -27,9 +27,11 @@
 // split one element row's entries (distinct positions), LDS operations of one wave complete in order -- so every entry sees its additions in ascending element
 // order, starting from 0.0 as the one-shot row thread does.  No search, no atomics, no read-modify-write of global memory.
 //
-// fh_quasilinear.hip puts a second element body on the same plan (fh_generic_assembler_assemble_form: an unsymmetric Jacobian from run-time coefficient
-// programs); it shares the row pass, the program buffer and the call checks below (gp_launch_rows, gp_upload_program, gp_check_call) and nothing of this body.
-#include "fh_generic.h"
+// fh_quasilinear.hip, fh_transient.hip and fh_system.hip put three more element bodies on the same plan (unsymmetric Jacobians from run-time coefficient
+// programs).  They share the row pass, the program buffer and the call checks below (gp_launch_rows, gp_upload_program, gp_check_call), the plan step of a body
+// (gp_plan_body: Gauss chunk, table staging, LDS; gp_dispatch: its <L, TL> kernel), and most of them with this body the phases of fh_elembody.h: the kernel's
+// prologue, (A) and (B).
+#include "fh_elembody.h"
 #include "fh_fe.h"
 #include "fh_expr_device.h"
 #include <algorithm>
@@ -97,53 +99,12 @@ __device__ __forceinline__ void gen_element_pass(bool active, int lane, int nc, 
     if (active)
       for (int l = lane; l < gc; l += L) {             // (A)
         const int g = g0 + l;
-        const double* dp = dphi + (size_t)g * nc * dim;
-        double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, Ji[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, det;
-        for (int n = 0; n < nc; n++)
-          for (int p = 0; p < dim; p++)
-            for (int q = 0; q < dim; q++) J[p][q] += dp[n * dim + p] * X[n * 3 + q];
-        if (dim == 1) {
-          det = J[0][0];
-          Ji[0][0] = 1 / det;
-        } else if (dim == 2) {
-          det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-          Ji[0][0] = J[1][1] / det;
-          Ji[0][1] = -J[0][1] / det;
-          Ji[1][0] = -J[1][0] / det;
-          Ji[1][1] = J[0][0] / det;
-        } else {
-          det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) + J[0][1] * (J[1][2] * J[2][0] - J[1][0] * J[2][2]) + J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-          Ji[0][0] = (-J[1][2] * J[2][1] + J[1][1] * J[2][2]) / det;
-          Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
-          Ji[0][2] = (-J[0][2] * J[1][1] + J[0][1] * J[1][2]) / det;
-          Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) / det;
-          Ji[1][1] = (-J[0][2] * J[2][0] + J[0][0] * J[2][2]) / det;
-          Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
-          Ji[2][0] = (-J[1][1] * J[2][0] + J[1][0] * J[2][1]) / det;
-          Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
-          Ji[2][2] = (-J[0][1] * J[1][0] + J[0][0] * J[1][1]) / det;
-        }
-        for (int q = 0; q < 3; q++)
-          for (int p = 0; p < 3; p++) JI[l * 9 + q * 3 + p] = Ji[q][p];
-        WG[l] = det * w[g];
-        double xq[4] = {0, 0, 0, 0};
-        for (int n = 0; n < nc; n++) {
-          const double ph = phi[(size_t)g * nc + n];
-          for (int q = 0; q < dim; q++) xq[q] += X[n * 3 + q] * ph;
-        }
+        double xq[4] = {0, 0, 0, 0};                      // x_g and t = 0 for the source program
+        eb_point_geometry(X, dphi + (size_t)g * nc * dim, phi + (size_t)g * nc, w + g, nc, dim, JI + l * 9, WG + l, xq);
         FS[l] = prog ? scale * fh_expr_device_eval(prog, nprog, pconst, xq) : 0.0;
       }
     __syncthreads();
-    if (active)
-      for (int t = lane; t < gc * nc; t += L) {        // (B)
-        const int l = t / nc, n = t - l * nc;
-        const double* dp = dphi + ((size_t)(g0 + l) * nc + n) * dim;
-        for (int q = 0; q < dim; q++) {
-          double sacc = 0.0;
-          for (int p = 0; p < dim; p++) sacc += JI[l * 9 + q * 3 + p] * dp[p];
-          G[(l * ns + n) * 3 + q] = sacc;
-        }
-      }
+    if (active) eb_chunk_gradients<L, false>(lane, g0, gc, nc, ns, dim, dphi, JI, 9, G);     // (B)
     __syncthreads();
     if (active)
       for (int l = lane; l < gc; l += L) {             // (C)
@@ -187,38 +148,21 @@ __global__ __launch_bounds__(GP_THREADS) void k_gen_pairs(int nslot, int nc, int
                                                           const double* __restrict__ sol, double scale, const int* __restrict__ prog, int nprog,
                                                           const double* __restrict__ pconst, double* __restrict__ Kb, double* __restrict__ Fb) {
   extern __shared__ __attribute__((aligned(16))) double gen_smem[];
-  constexpr int EPG = GP_THREADS / L;
   constexpr int NPL = gp_pairs_per_lane(L);
-  const int ntab = TL ? ng + ng * nc + ng * nc * dim : 0;
-  const int per = nc * 4 + gcm * 14 + gcm * nc * 3;
-  const int sub = threadIdx.x / L, lane = threadIdx.x % L;
-  const int slot = blockIdx.x * EPG + sub;
-  const bool active = slot < nslot;              // tail sub-groups keep the barriers and touch nothing
-  const double *w, *phi, *dphi;
-  if (TL) {
-    double* tw = gen_smem;
-    double* tphi = tw + ng;
-    double* tdphi = tphi + ng * nc;
-    for (int t = threadIdx.x; t < ng; t += GP_THREADS) tw[t] = gw[t];
-    for (int t = threadIdx.x; t < ng * nc; t += GP_THREADS) tphi[t] = gphi[t];
-    for (int t = threadIdx.x; t < ng * nc * dim; t += GP_THREADS) tdphi[t] = gdphi[t];
-    w = tw, phi = tphi, dphi = tdphi;
-  } else {
-    w = gw, phi = gphi, dphi = gdphi;
-  }
+  const EbGroup g = eb_prologue<L, TL>(gen_smem, nslot, nc, ng, dim, nc * 4 + gcm * 14 + gcm * nc * 3, gw, gphi, gdphi);
   int pi[NPL], pj[NPL];
   double acc[NPL], F;
-  gen_element_pass<L, NPL>(active, lane, nc, ng, gcm, nc, dim, w, phi, dphi, ed + (size_t)slot * nc, coords, sol, scale, prog, nprog, pconst,
-                           gen_smem + ntab + (size_t)sub * per, pi, pj, acc, F);
-  if (!active) return;
-  double* out = Kb + (size_t)slot * nc * nc;
+  gen_element_pass<L, NPL>(g.active, g.lane, nc, ng, gcm, nc, dim, g.w, g.phi, g.dphi, ed + (size_t)g.slot * nc, coords, sol, scale, prog, nprog, pconst, g.lds, pi,
+                           pj, acc, F);
+  if (!g.active) return;
+  double* out = Kb + (size_t)g.slot * nc * nc;
 #pragma unroll
   for (int k = 0; k < NPL; k++)
     if (pi[k] >= 0) {
       out[(size_t)pi[k] * nc + pj[k]] = acc[k];
       if (pi[k] != pj[k]) out[(size_t)pj[k] * nc + pi[k]] = acc[k];
     }
-  if (lane < nc) Fb[(size_t)slot * nc + lane] = F;
+  if (g.lane < nc) Fb[(size_t)g.slot * nc + g.lane] = F;
 }
 
 // create: the CSR position of every entry of every element row of one shape, by binary search in the sorted row; the smallest entry the pattern misses -> *miss
@@ -338,18 +282,20 @@ void gp_free(fh_generic_assembler_t as) {
   delete as;
 }
 
-template <int L, bool TL>
-static void gp_launch_pairs_t(fh_generic_assembler_t as, int k, const double* sol, double scale, const int* prog, int nprog, const double* pconst) {
-  hipLaunchKernelGGL((k_gen_pairs<L, TL>), dim3(fh_div_up(as->nslot[k], GP_THREADS / L)), dim3(GP_THREADS), as->lds[k], as->ctx->stream, as->nslot[k], as->nc[k],
-                     as->ng[k], as->gcm[k], as->dim, as->d_w[k], as->d_phi[k], as->d_dphi[k], as->d_ed[k], as->d_coords, sol, scale, prog, nprog, pconst,
-                     as->d_Kb + as->rows.kb_base[k], as->d_Fb + as->rows.row_base[k]);
-}
 static void gp_launch_pairs(fh_generic_assembler_t as, int k, const double* sol, double scale, const int* prog, int nprog, const double* pconst) {
-  const bool tl = as->tl[k];
-  switch (as->lanes[k]) {
-    case 16: tl ? gp_launch_pairs_t<16, true>(as, k, sol, scale, prog, nprog, pconst) : gp_launch_pairs_t<16, false>(as, k, sol, scale, prog, nprog, pconst); break;
-    case 32: tl ? gp_launch_pairs_t<32, true>(as, k, sol, scale, prog, nprog, pconst) : gp_launch_pairs_t<32, false>(as, k, sol, scale, prog, nprog, pconst); break;
-    default: tl ? gp_launch_pairs_t<64, true>(as, k, sol, scale, prog, nprog, pconst) : gp_launch_pairs_t<64, false>(as, k, sol, scale, prog, nprog, pconst); break;
+  const GenBodyPlan& P = as->poisson;
+  gp_dispatch(P, k, [&](auto lanes, auto staged) {
+    constexpr int L = decltype(lanes)::value;
+    hipLaunchKernelGGL((k_gen_pairs<L, decltype(staged)::value>), dim3(fh_div_up(as->nslot[k], GP_THREADS / L)), dim3(GP_THREADS), P.lds[k], as->ctx->stream,
+                       as->nslot[k], as->nc[k], as->ng[k], P.gcm[k], as->dim, as->d_w[k], as->d_phi[k], as->d_dphi[k], as->d_ed[k], as->d_coords, sol, scale, prog, nprog,
+                       pconst, as->d_Kb + as->rows.kb_base[k], as->d_Fb + as->rows.row_base[k]);
+  });
+}
+
+void gp_read_plan(fh_generic_assembler_t as, const GenBodyPlan& plan, int gauss_chunk[3], int lanes[3]) {
+  for (int k = 0; k < 3; k++) {
+    gauss_chunk[k] = k < as->ns ? plan.gcm[k] : 0;
+    if (lanes) lanes[k] = k < as->ns ? plan.lanes[k] : 0;
   }
 }
 
@@ -392,21 +338,13 @@ int gp_plan_host(const char* who, fh_ctx_t ctx, const GenMesh& m, int nel, int n
       as->rows.row_base[k] = rb, as->rows.nc[k] = ncs[k], as->rows.kb_base[k] = kb;
       rb += nslot[k] * ncs[k];
       kb += (long long)nslot[k] * ncs[k] * ncs[k];
-      const int L = gp_lanes_per_element(ncs[k], ctx->generic_pack);
-      const int epg = GP_THREADS / L;
-      int gcm = std::min(as->ng[k], 32);
-      while (gcm > 1 && epg * gp_elem_doubles(ncs[k], gcm) * sizeof(double) > GP_LDS_BUDGET) gcm = (gcm + 1) / 2;
-      const size_t base = epg * gp_elem_doubles(ncs[k], gcm) * sizeof(double);
-      const size_t tab = ((size_t)as->ng[k] * (1 + ncs[k] + ncs[k] * dim)) * sizeof(double);
-      as->lanes[k] = L, as->gcm[k] = gcm;
-      as->tl[k] = base + tab <= GP_LDS_BUDGET;
-      as->lds[k] = base + (as->tl[k] ? tab : 0);
-      if (as->lds[k] > GP_LDS_BUDGET) {
-        delete as;
-        fh_set_error("%s: shape %d does not fit the LDS of a workgroup", who, m.shapes[k]);
-        return 2;
-      }
     }
+  }
+  int lanes[3] = {64, 64, 64};
+  for (int k = 0; k < ns; k++) lanes[k] = gp_lanes_per_element(ncs[k], ctx->generic_pack);
+  if (const int rc = gp_plan_body(who, as, lanes, gp_elem_doubles, false, false, "", "", as->poisson)) {
+    delete as;
+    return rc;
   }
   as->nrows = nrows, as->nent = nent;
   // what one assembly cannot avoid moving: element tables, coordinates and state in; values and residual out
@@ -662,7 +600,7 @@ extern "C" int fh_generic_assembler_info(fh_generic_assembler_t as, int elems_pe
                                          int64_t* device_allocations) {
   FH_REQUIRE(as, "fh_generic_assembler_info: null argument");
   if (elems_per_workgroup)
-    for (int k = 0; k < 3; k++) elems_per_workgroup[k] = k < as->ns ? GP_THREADS / as->lanes[k] : 0;
+    for (int k = 0; k < 3; k++) elems_per_workgroup[k] = k < as->ns ? GP_THREADS / as->poisson.lanes[k] : 0;
   if (device_bytes) *device_bytes = as->device_bytes;
   if (algorithmic_bytes) *algorithmic_bytes = as->algorithmic_bytes;
   if (device_allocations) *device_allocations = as->device_allocations;

@@ -4,13 +4,10 @@
 #include "fh_generic.h"
 
 enum { QF_F = 0, QF_A, QF_AU, QF_C, QF_CU, QF_CG, QF_NPROG = QF_CG + 3 };
-constexpr int QF_PT = 7;                     // a, a_u, c, c_u, c_g[3] of a Gauss point
 
 struct GenFormDir {
   int code[QF_NPROG], ncode[QF_NPROG], kons[QF_NPROG];     // first word, words (-1: no such program), first constant
 };
-
-constexpr int qf_entries_per_lane(int L) { return L == 64 ? (GEN_NC * GEN_NC + 63) / 64 : 4; }
 
 // every refusal a form can earn on this object (c_g beyond the dimension, a program over more than max_vars variables: `vars` names them in the message), then
 // all constants and all code of its programs back to back with their directory.  Nothing is enqueued and nothing of the object changes

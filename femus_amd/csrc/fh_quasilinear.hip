@@ -8,14 +8,16 @@
 // The plan is the Poisson object's, untouched: the same element tables, Kb / Pos / Fb / adj and the same row pass (k_gen_rows adds full nc x nc element rows
 // already).  What is new is the element body: the Poisson body stores the pairs i <= j and mirrors them, this one forms every (i, j) -- the advection and
 // the a_u term are not symmetric.  Launch geometry per shape as there (L = 64 / 32 / 16 lanes per element, 256-thread workgroups, tables staged where they
-// fit); the Gauss points go through LDS in chunks of form_gcm, chosen at the first assemble_form within GP_LDS_BUDGET because an element needs more here:
+// fit); the Gauss points go through LDS in chunks of a plan of its own (the object's `form`), made at the first assemble_form within GP_LDS_BUDGET because an
+// element needs more here:
 //   X[nc][3] U[nc] | JI[gc][9] WG[gc] FS[gc] GU[gc][3] PT[gc][7] | G[gc][nc][3] ST[gc][nc][2]      = nc 4 + gc 21 + gc nc 5 doubles
-// (the Poisson body's nc 4 + gc 14 + gc nc 3, and gc 7 + gc nc 2 more).  Phases of one chunk, a workgroup barrier between them:
-//   (A)  lane = Gauss point: Jacobian, inverse, det w, x_g (kept in the point's c_g slots until (C) has read it: the same lane)
-//   (B)  lanes over (point, node): G_n = Jac^-1 dphi_n
+// (the Poisson body's nc 4 + gc 14 + gc nc 3, and gc 7 + gc nc 2 more).  Phases of one chunk, a workgroup barrier between them; (A) and (C') are those of
+// fh_elembody.h, as the kernel's prologue is:
+//   (A)  x_g is kept in the point's c_g slots until (C) has read it: the same lane
+//   (B)  lanes over (point, node): G_n = Jac^-1 dphi_n -- the text of eb_chunk_gradients, kept in this body on purpose: as a helper it gives these kernels
+//        another schedule (profiles/elembody_share_isa.md); a change to it there is made here too
 //   (C)  lane = Gauss point: u_g = sum phi_n U_n, grad u_g = sum G_n U_n (nodes ascending), then the programs at (x_g, u_g, grad u_g):
 //        FS = f, PT = (a, a_u, c, c_u, c_g[3])
-//   (C') lanes over (point, node): S_n = G_n . grad u_g,  T_n = c_u phi_n + c_g . G_n
 //   (D)  lanes over the nc^2 entries e = i nc + j (at most 12 per lane at L = 64 for HEX27's 729, at most 4 where elements share a wave: nc <= 10 there):
 //        acc += (a (G_i . G_j) + a_u S_i phi_j + phi_i T_j) WG, points ascending; lanes < nc: F += (f phi_i - a S_i - c phi_i) WG
 // Every sum has one order, whatever the chunk: a repeated call gives the same bits, and there is no atomic anywhere.  Every entry of Kb and Fb of an active
@@ -25,6 +27,7 @@
 // paths share the buffer and its cache: it is uploaded only when its content differs from the last call's, whichever path made that.  The directory (where
 // each program starts, how long it is) is 96 bytes of kernel argument.
 #include "fh_quasilinear.h"
+#include "fh_elembody.h"
 #include "fh_expr_device.h"
 #include <algorithm>
 
@@ -56,13 +59,12 @@ __device__ __forceinline__ void form_element_pass(bool active, int lane, int nc,
   }
   const bool useS = dir.ncode[QF_AU] >= 0;           // uniform: a term whose programs are all missing is left out, not multiplied by 0
   const bool useT = dir.ncode[QF_CU] >= 0 || dir.ncode[QF_CG] >= 0 || dir.ncode[QF_CG + 1] >= 0 || dir.ncode[QF_CG + 2] >= 0;
-  const int nent = nc * nc;
   int ei[NPL], ej[NPL];
-  double acc[NPL];
+  double acc[NPL], F = 0.0;
 #pragma unroll
   for (int k = 0; k < NPL; k++) {
     const int e = lane + L * k;
-    if (active && e < nent) {
+    if (active && e < nc * nc) {
       ei[k] = e / nc;
       ej[k] = e - ei[k] * nc;
     } else {
@@ -70,47 +72,14 @@ __device__ __forceinline__ void form_element_pass(bool active, int lane, int nc,
     }
     acc[k] = 0.0;
   }
-  double F = 0.0;
   __syncthreads();
   for (int g0 = 0; g0 < ng; g0 += gcm) {
     const int gc = min(gcm, ng - g0);
     if (active)
       for (int l = lane; l < gc; l += L) {             // (A)
         const int g = g0 + l;
-        const double* dp = dphi + (size_t)g * nc * dim;
-        double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, Ji[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, det;
-        for (int n = 0; n < nc; n++)
-          for (int p = 0; p < dim; p++)
-            for (int q = 0; q < dim; q++) J[p][q] += dp[n * dim + p] * X[n * 3 + q];
-        if (dim == 1) {
-          det = J[0][0];
-          Ji[0][0] = 1 / det;
-        } else if (dim == 2) {
-          det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-          Ji[0][0] = J[1][1] / det;
-          Ji[0][1] = -J[0][1] / det;
-          Ji[1][0] = -J[1][0] / det;
-          Ji[1][1] = J[0][0] / det;
-        } else {
-          det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) + J[0][1] * (J[1][2] * J[2][0] - J[1][0] * J[2][2]) + J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-          Ji[0][0] = (-J[1][2] * J[2][1] + J[1][1] * J[2][2]) / det;
-          Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
-          Ji[0][2] = (-J[0][2] * J[1][1] + J[0][1] * J[1][2]) / det;
-          Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) / det;
-          Ji[1][1] = (-J[0][2] * J[2][0] + J[0][0] * J[2][2]) / det;
-          Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
-          Ji[2][0] = (-J[1][1] * J[2][0] + J[1][0] * J[2][1]) / det;
-          Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
-          Ji[2][2] = (-J[0][1] * J[1][0] + J[0][0] * J[1][1]) / det;
-        }
-        for (int q = 0; q < 3; q++)
-          for (int p = 0; p < 3; p++) JI[l * 9 + q * 3 + p] = Ji[q][p];
-        WG[l] = det * w[g];
         double xq[3] = {0, 0, 0};
-        for (int n = 0; n < nc; n++) {
-          const double ph = phi[(size_t)g * nc + n];
-          for (int q = 0; q < dim; q++) xq[q] += X[n * 3 + q] * ph;
-        }
+        eb_point_geometry(X, dphi + (size_t)g * nc * dim, phi + (size_t)g * nc, w + g, nc, dim, JI + l * 9, WG + l, xq);
         for (int q = 0; q < 3; q++) PT[l * QF_PT + 4 + q] = xq[q];
       }
     __syncthreads();
@@ -143,17 +112,7 @@ __device__ __forceinline__ void form_element_pass(bool active, int lane, int nc,
         }
       }
     __syncthreads();
-    if (active && (useS || useT))
-      for (int t = lane; t < gc * nc; t += L) {        // (C')
-        const int l = t / nc, n = t - l * nc;
-        const double* gn = G + (l * ns + n) * 3;
-        double S = 0.0;
-        for (int q = 0; q < dim; q++) S += gn[q] * GU[l * 3 + q];
-        double T = PT[l * QF_PT + 3] * phi[(size_t)(g0 + l) * nc + n];
-        for (int q = 0; q < dim; q++) T += PT[l * QF_PT + 4 + q] * gn[q];
-        ST[(l * ns + n) * 2] = S;
-        ST[(l * ns + n) * 2 + 1] = T;
-      }
+    if (active && (useS || useT)) eb_chunk_st<L>(lane, g0, gc, nc, dim, phi, G, GU, PT, ST);     // (C')
     if (useS || useT) __syncthreads();
 #pragma unroll
     for (int k = 0; k < NPL; k++)                      // (D)
@@ -196,65 +155,19 @@ __global__ __launch_bounds__(GP_THREADS) void k_gen_form(int nslot, int nc, int 
                                                          const double* __restrict__ sol, GenFormDir dir, const int* __restrict__ pcode,
                                                          const double* __restrict__ pconst, double* __restrict__ Kb, double* __restrict__ Fb) {
   extern __shared__ __attribute__((aligned(16))) double form_smem[];
-  constexpr int EPG = GP_THREADS / L;
-  constexpr int NPL = qf_entries_per_lane(L);
-  const int ntab = TL ? ng + ng * nc + ng * nc * dim : 0;
-  const int per = (int)qf_elem_doubles(nc, gcm);
-  const int sub = threadIdx.x / L, lane = threadIdx.x % L;
-  const int slot = blockIdx.x * EPG + sub;
-  const bool active = slot < nslot;              // tail sub-groups keep the barriers and touch nothing
-  const double *w, *phi, *dphi;
-  if (TL) {
-    double* tw = form_smem;
-    double* tphi = tw + ng;
-    double* tdphi = tphi + ng * nc;
-    for (int t = threadIdx.x; t < ng; t += GP_THREADS) tw[t] = gw[t];
-    for (int t = threadIdx.x; t < ng * nc; t += GP_THREADS) tphi[t] = gphi[t];
-    for (int t = threadIdx.x; t < ng * nc * dim; t += GP_THREADS) tdphi[t] = gdphi[t];
-    w = tw, phi = tphi, dphi = tdphi;
-  } else {
-    w = gw, phi = gphi, dphi = gdphi;
-  }
-  form_element_pass<L, NPL>(active, lane, nc, ng, gcm, dim, w, phi, dphi, ed + (size_t)slot * nc, coords, sol, dir, pcode, pconst,
-                            form_smem + ntab + (size_t)sub * per, Kb + (size_t)slot * nc * nc, Fb + (size_t)slot * nc);
+  const EbGroup g = eb_prologue<L, TL>(form_smem, nslot, nc, ng, dim, (int)qf_elem_doubles(nc, gcm), gw, gphi, gdphi);
+  form_element_pass<L, gp_entries_per_lane(L)>(g.active, g.lane, nc, ng, gcm, dim, g.w, g.phi, g.dphi, ed + (size_t)g.slot * nc, coords, sol, dir, pcode, pconst, g.lds,
+                                               Kb + (size_t)g.slot * nc * nc, Fb + (size_t)g.slot * nc);
 }
 
-template <int L, bool TL>
-static void qf_launch_t(fh_generic_assembler_t as, int k, const double* sol, const GenFormDir& dir, const int* pcode, const double* pconst) {
-  hipLaunchKernelGGL((k_gen_form<L, TL>), dim3(fh_div_up(as->nslot[k], GP_THREADS / L)), dim3(GP_THREADS), as->form_lds[k], as->ctx->stream, as->nslot[k], as->nc[k],
-                     as->ng[k], as->form_gcm[k], as->dim, as->d_w[k], as->d_phi[k], as->d_dphi[k], as->d_ed[k], as->d_coords, sol, dir, pcode, pconst,
-                     as->d_Kb + as->rows.kb_base[k], as->d_Fb + as->rows.row_base[k]);
-}
 static void qf_launch(fh_generic_assembler_t as, int k, const double* sol, const GenFormDir& dir, const int* pcode, const double* pconst) {
-  const bool tl = as->form_tl[k];
-  switch (as->lanes[k]) {
-    case 16: tl ? qf_launch_t<16, true>(as, k, sol, dir, pcode, pconst) : qf_launch_t<16, false>(as, k, sol, dir, pcode, pconst); break;
-    case 32: tl ? qf_launch_t<32, true>(as, k, sol, dir, pcode, pconst) : qf_launch_t<32, false>(as, k, sol, dir, pcode, pconst); break;
-    default: tl ? qf_launch_t<64, true>(as, k, sol, dir, pcode, pconst) : qf_launch_t<64, false>(as, k, sol, dir, pcode, pconst); break;
-  }
-}
-
-// first assemble_form: the Gauss chunk, table staging and LDS of the larger element body per shape; nothing is kept unless every shape fits
-static int qf_plan(fh_generic_assembler_t as) {
-  int gcm[3] = {0, 0, 0};
-  bool tl[3] = {false, false, false};
-  size_t lds[3] = {0, 0, 0};
-  for (int k = 0; k < as->ns; k++) {
-    const int L = as->lanes[k], epg = GP_THREADS / L, nc = as->nc[k];
-    FH_REQUIRE(qf_entries_per_lane(L) * L >= nc * nc, "fh_generic_assembler_assemble_form: shape %d: %d entries of an element on %d lanes", as->shapes[k], nc * nc, L);
-    int gc = std::min(as->ng[k], 32);
-    while (gc > 1 && epg * qf_elem_doubles(nc, gc) * sizeof(double) > GP_LDS_BUDGET) gc = (gc + 1) / 2;
-    const size_t base = epg * qf_elem_doubles(nc, gc) * sizeof(double);
-    FH_REQUIRE(base <= GP_LDS_BUDGET, "fh_generic_assembler_assemble_form: shape %d does not fit the LDS of a workgroup with the quasilinear element body",
-               as->shapes[k]);
-    const size_t tab = ((size_t)as->ng[k] * (1 + nc + nc * as->dim)) * sizeof(double);
-    gcm[k] = gc;
-    tl[k] = base + tab <= GP_LDS_BUDGET;
-    lds[k] = base + (tl[k] ? tab : 0);
-  }
-  for (int k = 0; k < 3; k++) as->form_gcm[k] = gcm[k], as->form_tl[k] = tl[k], as->form_lds[k] = lds[k];
-  as->form_ready = true;
-  return 0;
+  const GenBodyPlan& P = as->form;
+  gp_dispatch(P, k, [&](auto lanes, auto staged) {
+    constexpr int L = decltype(lanes)::value;
+    hipLaunchKernelGGL((k_gen_form<L, decltype(staged)::value>), dim3(fh_div_up(as->nslot[k], GP_THREADS / L)), dim3(GP_THREADS), P.lds[k], as->ctx->stream,
+                       as->nslot[k], as->nc[k], as->ng[k], P.gcm[k], as->dim, as->d_w[k], as->d_phi[k], as->d_dphi[k], as->d_ed[k], as->d_coords, sol, dir, pcode, pconst,
+                       as->d_Kb + as->rows.kb_base[k], as->d_Fb + as->rows.row_base[k]);
+  });
 }
 
 int qf_gather_programs(const char* who, fh_generic_assembler_t as, const fh_quasilinear_form_t* form, int max_vars, const char* vars, GenFormDir& dir,
@@ -291,7 +204,8 @@ extern "C" int fh_generic_assembler_assemble_form(fh_generic_assembler_t as, fh_
   std::vector<int> code;
   std::vector<double> consts;
   FH_TRY(qf_gather_programs(who, as, form, QF_VARS, "x, y, z, u, ux, uy, uz", dir, code, consts));
-  if (!as->form_ready) FH_TRY(qf_plan(as));
+  // the first call: the Gauss chunk, table staging and LDS of the larger element body per shape, on the Poisson body's lanes
+  if (!as->form.ready) FH_TRY(gp_plan_body(who, as, as->poisson.lanes, qf_elem_doubles, false, true, "an element", " with the quasilinear element body", as->form));
   FH_TRY(gp_upload_program(who, as, code, consts));
   const double* d_k = (const double*)as->d_prog;
   const int* d_code = (const int*)(as->d_prog + as->consts.size() * sizeof(double));
@@ -307,6 +221,6 @@ extern "C" int fh_generic_assembler_assemble_form(fh_generic_assembler_t as, fh_
 
 extern "C" int fh_generic_assembler_form_chunks(fh_generic_assembler_t as, int gauss_chunk[3]) {
   FH_REQUIRE(as && gauss_chunk, "fh_generic_assembler_form_chunks: null argument");
-  for (int k = 0; k < 3; k++) gauss_chunk[k] = k < as->ns ? as->form_gcm[k] : 0;
+  gp_read_plan(as, as->form, gauss_chunk, nullptr);
   return 0;
 }

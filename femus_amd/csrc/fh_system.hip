@@ -14,8 +14,10 @@
 //   element pass  k_sys_elements: L lanes per element (the scalar body's width times 1 / 2 / 4 for m = 1 / 2 / 3 and 4, at most 64).  LDS of an element:
 //                   X[nc][3] U[m][nc] | PV[gc][13 + 6 m + 8 m^2] | G[gc][nc][3]
 //                 one PV block per Gauss point: JI[9] WG | state[3 + 4 m] | f[m] c[m] A[m^2] C[m^2] W[m^2][3] D[m^2][3].  Phases of a chunk, a barrier between:
-//                   (A)  lane = point: Jacobian, inverse, det w, x_g into the state
-//                   (B)  lanes over (point, node): G_n = Jac^-1 dphi_n
+//                   (A)  of fh_elembody.h: the inverse and det w head the point's PV block, x_g goes into the state
+//                   (B)  lanes over (point, node): G_n = Jac^-1 dphi_n.  This and the kernel's prologue are the texts of eb_chunk_gradients and
+//                        eb_prologue, kept in this file on purpose: as helpers they give these kernels another schedule and cost time
+//                        (profiles/elembody_share_isa.md); a change to them there is made here too
 //                   (C1) lanes over (point, variable): u_k, grad u_k into the state (nodes ascending)
 //                   (C2) lanes over (point, task): the directory's tasks.  A simple task runs one program and stores its value; a W task runs the at most m
 //                        programs dA_kp/du_l, p ascending, and stores W_kl.  The state is read from LDS
@@ -26,7 +28,7 @@
 //   row pass      k_sys_rows: lpr lanes per system row, m maxrow doubles of LDS per group, the scalar Pos / adj / rowptr_S
 //   programs      all constants, then all code, then the directory (16 ints per task) in the object's program buffer: the directory is part of the code array
 //                 gp_upload_program compares, so no other path's upload can leave a stale one behind
-#include "fh_quasilinear.h"
+#include "fh_elembody.h"
 #include "fh_expr_device.h"
 #include <algorithm>
 #include <cstdio>
@@ -59,12 +61,11 @@ __device__ __forceinline__ void system_element_pass(bool active, int lane, int m
     for (int d = 0; d < 3; d++) X[lane * 3 + d] = d < dim ? coords[(size_t)dof * dim + d] : 0.0;
     for (int k = 0; k < m; k++) U[k * nc + lane] = sol ? sol[(size_t)k * ndof + dof] : 0.0;
   }
-  const int nent = nc * nc;
   int ei[NPL], ej[NPL];
 #pragma unroll
   for (int k = 0; k < NPL; k++) {
     const int e = lane + L * k;
-    if (active && e < nent) {
+    if (active && e < nc * nc) {
       ei[k] = e / nc;
       ej[k] = e - ei[k] * nc;
     } else {
@@ -78,41 +79,9 @@ __device__ __forceinline__ void system_element_pass(bool active, int lane, int m
     if (active)
       for (int l = lane; l < gc; l += L) {             // (A)
         const int g = g0 + l;
-        const double* dp = dphi + (size_t)g * nc * dim;
         double* P = PV + l * PS;
-        double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, Ji[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, det;
-        for (int n = 0; n < nc; n++)
-          for (int p = 0; p < dim; p++)
-            for (int q = 0; q < dim; q++) J[p][q] += dp[n * dim + p] * X[n * 3 + q];
-        if (dim == 1) {
-          det = J[0][0];
-          Ji[0][0] = 1 / det;
-        } else if (dim == 2) {
-          det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-          Ji[0][0] = J[1][1] / det;
-          Ji[0][1] = -J[0][1] / det;
-          Ji[1][0] = -J[1][0] / det;
-          Ji[1][1] = J[0][0] / det;
-        } else {
-          det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) + J[0][1] * (J[1][2] * J[2][0] - J[1][0] * J[2][2]) + J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-          Ji[0][0] = (-J[1][2] * J[2][1] + J[1][1] * J[2][2]) / det;
-          Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
-          Ji[0][2] = (-J[0][2] * J[1][1] + J[0][1] * J[1][2]) / det;
-          Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) / det;
-          Ji[1][1] = (-J[0][2] * J[2][0] + J[0][0] * J[2][2]) / det;
-          Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
-          Ji[2][0] = (-J[1][1] * J[2][0] + J[1][0] * J[2][1]) / det;
-          Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
-          Ji[2][2] = (-J[0][1] * J[1][0] + J[0][0] * J[1][1]) / det;
-        }
-        for (int q = 0; q < 3; q++)
-          for (int p = 0; p < 3; p++) P[q * 3 + p] = Ji[q][p];
-        P[9] = det * w[g];
         double xq[3] = {0, 0, 0};
-        for (int n = 0; n < nc; n++) {
-          const double ph = phi[(size_t)g * nc + n];
-          for (int q = 0; q < dim; q++) xq[q] += X[n * 3 + q] * ph;
-        }
+        eb_point_geometry(X, dphi + (size_t)g * nc * dim, phi + (size_t)g * nc, w + g, nc, dim, P, P + 9, xq);
         for (int q = 0; q < 3; q++) P[oST + q] = xq[q];
       }
     __syncthreads();
@@ -233,7 +202,7 @@ __global__ __launch_bounds__(GP_THREADS) void k_sys_elements(int nslot, int m, i
                                                              const double* __restrict__ pconst, double* Kb, long long kstride, double* Fb, long long fstride) {
   extern __shared__ __attribute__((aligned(16))) double sys_smem[];
   constexpr int EPG = GP_THREADS / L;
-  constexpr int NPL = qf_entries_per_lane(L);
+  constexpr int NPL = gp_entries_per_lane(L);
   const int ntab = TL ? ng + ng * nc + ng * nc * dim : 0;
   const int per = (int)sy_elem_doubles(m, nc, gcm);
   const int sub = threadIdx.x / L, lane = threadIdx.x % L;
@@ -300,40 +269,25 @@ struct SysCall {
 };
 }  // namespace
 
-template <int L, bool TL>
-static void sy_launch_t(fh_generic_assembler_t as, int k, const SysCall& c) {
-  const int m = c.m;
-  hipLaunchKernelGGL((k_sys_elements<L, TL>), dim3(fh_div_up(as->nslot[k], GP_THREADS / L)), dim3(GP_THREADS), as->sys_lds[m][k], as->ctx->stream, as->nslot[k], m,
-                     as->nc[k], as->ng[k], as->sys_gcm[m][k], as->dim, as->d_w[k], as->d_phi[k], as->d_dphi[k], as->d_ed[k], as->d_coords, c.sol, as->ndof, c.mk, c.dir,
-                     c.ntask, c.pcode, c.pconst, c.Kb + as->rows.kb_base[k], (long long)as->nent, c.Fb + as->rows.row_base[k], (long long)as->nrows);
-}
 static void sy_launch(fh_generic_assembler_t as, int k, const SysCall& c) {
-  const bool tl = as->sys_tl[c.m][k];
-  switch (as->sys_lanes[c.m][k]) {
-    case 16: tl ? sy_launch_t<16, true>(as, k, c) : sy_launch_t<16, false>(as, k, c); break;
-    case 32: tl ? sy_launch_t<32, true>(as, k, c) : sy_launch_t<32, false>(as, k, c); break;
-    default: tl ? sy_launch_t<64, true>(as, k, c) : sy_launch_t<64, false>(as, k, c); break;
-  }
+  const GenBodyPlan& P = as->sys[c.m];
+  gp_dispatch(P, k, [&](auto lanes, auto staged) {
+    constexpr int L = decltype(lanes)::value;
+    hipLaunchKernelGGL((k_sys_elements<L, decltype(staged)::value>), dim3(fh_div_up(as->nslot[k], GP_THREADS / L)), dim3(GP_THREADS), P.lds[k], as->ctx->stream,
+                       as->nslot[k], c.m, as->nc[k], as->ng[k], P.gcm[k], as->dim, as->d_w[k], as->d_phi[k], as->d_dphi[k], as->d_ed[k], as->d_coords, c.sol, as->ndof, c.mk,
+                       c.dir, c.ntask, c.pcode, c.pconst, c.Kb + as->rows.kb_base[k], (long long)as->nent, c.Fb + as->rows.row_base[k], (long long)as->nrows);
+  });
 }
 
-// first assemble_system with this m: lanes, Gauss chunk, table staging and LDS per shape, the lanes of the row pass -- every refusal before the work buffers are
-// allocated; nothing is kept unless all of it succeeds
+// first assemble_system with this m: lanes (the scalar body's times 1 / 2 / 4, at most 64), Gauss chunk, table staging and LDS per shape, the lanes of the row
+// pass -- every refusal before the work buffers are allocated; nothing is kept unless all of it succeeds
 static int sy_plan(const char* who, fh_generic_assembler_t as, int m) {
-  int lanes[3] = {0, 0, 0}, gcm[3] = {0, 0, 0};
-  bool tl[3] = {false, false, false};
-  size_t lds[3] = {0, 0, 0};
-  for (int k = 0; k < as->ns; k++) {
-    const int L = std::min(64, as->lanes[k] * (m == 1 ? 1 : m == 2 ? 2 : 4)), epg = GP_THREADS / L, nc = as->nc[k];
-    FH_REQUIRE(qf_entries_per_lane(L) * L >= nc * nc, "%s: shape %d: %d entries of a block on %d lanes", who, as->shapes[k], nc * nc, L);
-    int gc = std::min(as->ng[k], 32);
-    while (gc > 1 && epg * sy_elem_doubles(m, nc, gc) * sizeof(double) > GP_LDS_BUDGET) gc = (gc + 1) / 2;
-    const size_t base = epg * sy_elem_doubles(m, nc, gc) * sizeof(double);
-    FH_REQUIRE(base <= GP_LDS_BUDGET, "%s: shape %d does not fit the LDS of a workgroup with the element body of %d variables", who, as->shapes[k], m);
-    const size_t tab = ((size_t)as->ng[k] * (1 + nc + nc * as->dim)) * sizeof(double);
-    lanes[k] = L, gcm[k] = gc;
-    tl[k] = base + tab <= GP_LDS_BUDGET;
-    lds[k] = base + (tl[k] ? tab : 0);
-  }
+  int lanes[3] = {64, 64, 64};
+  for (int k = 0; k < as->ns; k++) lanes[k] = std::min(64, as->poisson.lanes[k] * (m == 1 ? 1 : m == 2 ? 2 : 4));
+  char body[64];
+  snprintf(body, sizeof body, " with the element body of %d variables", m);
+  GenBodyPlan plan;
+  FH_TRY(gp_plan_body(who, as, lanes, [m](int nc, int gc) { return sy_elem_doubles(m, nc, gc); }, false, true, "a block", body, plan));
   int lpr = as->lpr;
   while (lpr < 64 && (size_t)(GP_THREADS / lpr) * m * as->maxrow * sizeof(double) > GP_LDS_BUDGET) lpr *= 2;
   FH_REQUIRE((size_t)(GP_THREADS / lpr) * m * as->maxrow * sizeof(double) <= GP_LDS_BUDGET, "%s: %d rows of %d entries are longer than the row pass holds", who, m,
@@ -354,10 +308,9 @@ static int sy_plan(const char* who, fh_generic_assembler_t as, int m) {
   } else {
     as->d_sysK[1] = as->d_Kb, as->d_sysF[1] = as->d_Fb;
   }
-  for (int k = 0; k < 3; k++) as->sys_lanes[m][k] = lanes[k], as->sys_gcm[m][k] = gcm[k], as->sys_tl[m][k] = tl[k], as->sys_lds[m][k] = lds[k];
+  as->sys[m] = plan;
   as->sys_lpr[m] = lpr;
   as->sys_row_lds[m] = (size_t)(GP_THREADS / lpr) * m * as->maxrow * sizeof(double);
-  as->sys_ready[m] = true;
   return 0;
 }
 
@@ -476,7 +429,7 @@ extern "C" int fh_generic_assembler_assemble_system(fh_generic_assembler_t as, f
   std::vector<int> code, dir;
   std::vector<double> consts;
   FH_TRY(sy_gather(who, as, form, c.mk, c.ntask, code, dir, consts));
-  if (!as->sys_ready[m]) FH_TRY(sy_plan(who, as, m));
+  if (!as->sys[m].ready) FH_TRY(sy_plan(who, as, m));
   const size_t ncode = code.size();
   code.insert(code.end(), dir.begin(), dir.end());       // the directory travels, and is compared, as part of the code array
   FH_TRY(gp_upload_program(who, as, code, consts));
@@ -501,9 +454,6 @@ extern "C" int fh_generic_assembler_assemble_system(fh_generic_assembler_t as, f
 
 extern "C" int fh_generic_assembler_system_chunks(fh_generic_assembler_t as, int m, int gauss_chunk[3], int lanes[3]) {
   FH_REQUIRE(as && gauss_chunk && lanes && m >= 1 && m <= SY_MAXM, "fh_generic_assembler_system_chunks: null argument, or a number of variables outside 1 .. 4");
-  for (int k = 0; k < 3; k++) {
-    gauss_chunk[k] = k < as->ns ? as->sys_gcm[m][k] : 0;
-    lanes[k] = k < as->ns ? as->sys_lanes[m][k] : 0;
-  }
+  gp_read_plan(as, as->sys[m], gauss_chunk, lanes);
   return 0;
 }

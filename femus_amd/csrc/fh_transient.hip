@@ -14,19 +14,21 @@
 // (= 0) there is no second vector to hold it against, and any sol_old that covers the dofs is taken.
 //
 // Plan, Kb / Pos / Fb / adj, row pass, program buffer and launch widths are the form body's; the element body is new and larger per element, so it has a Gauss
-// chunk, table staging and LDS of its own (tr_*, chosen at the first assemble_transient within GP_LDS_BUDGET):
+// chunk, table staging and LDS of its own (the object's `transient` plan, made at the first assemble_transient within GP_LDS_BUDGET):
 //   X[nc][3] U[nc] Uo[nc] | JI[gc][9] WG[gc] FS[gc] GU[gc][3] PT[gc][7] UD[gc] GO[gc][3] PO[gc][3] | G[gc][nc][3] ST[gc][nc][2]    = nc 5 + gc 28 + gc nc 5 doubles
-// (the form body's nc 4 + gc 21 + gc nc 5; UD = u - uo, GO = grad uo, PO = (f, a, c)|old of a point).  Phases of one chunk as there, a workgroup barrier between:
-//   (A)  lane = Gauss point: Jacobian, inverse, det w, x_g (kept in the point's c_g slots until (C) has read it: the same lane)
-//   (B)  lanes over (point, node): G_n = Jac^-1 dphi_n
+// (the form body's nc 4 + gc 21 + gc nc 5; UD = u - uo, GO = grad uo, PO = (f, a, c)|old of a point).  Phases of one chunk, a workgroup barrier between; (B)
+// and (C') are those of fh_elembody.h, as the kernel's prologue is:
+//   (A)  lane = Gauss point: Jacobian, inverse, det w, x_g -- the text of eb_point_geometry, kept in this body on purpose: as a helper it costs these kernels
+//        registers and time (profiles/elembody_share_isa.md); a change to it there is made here too.  x_g is kept in the point's c_g slots until (C) has
+//        read it: the same lane
 //   (C)  lane = Gauss point: u_g, uo_g, grad u_g (nodes ascending), the eight programs at the new state; unless theta == 1 also grad uo_g and f, a, c at the old one;
 //        every value is stored times dt theta (old: dt (1 - theta)), once per point, so that (D) and the residual lanes add the mass term and nothing else
-//   (C') lanes over (point, node): S_n = G_n . grad u_g,  T_n = c_u phi_n + c_g . G_n
 //   (D)  lanes over the nc^2 entries: acc += (phi_i phi_j + a (G_i . G_j) + a_u S_i phi_j + phi_i T_j) WG, points ascending (a, a_u, T scaled);
 //        lanes < nc: F += (-UD phi_i + (f phi_i - a S_i - c phi_i) + (fo phi_i - ao So_i - co phi_i)) WG with So_i = G_i . grad uo_g (all nine scaled)
 // Every sum has one order, whatever the chunk: a repeated call gives the same bits, and there is no atomic anywhere.  Every entry of Kb and Fb of an active
 // element is written; tail sub-groups keep the barriers and touch nothing.
 #include "fh_quasilinear.h"
+#include "fh_elembody.h"
 #include "fh_expr_device.h"
 #include <algorithm>
 #include <cmath>
@@ -68,13 +70,12 @@ __device__ __forceinline__ void transient_element_pass(bool active, int lane, in
   const bool useS = dir.ncode[QF_AU] >= 0;           // uniform: a term whose programs are all missing is left out, not multiplied by 0
   const bool useT = dir.ncode[QF_CU] >= 0 || dir.ncode[QF_CG] >= 0 || dir.ncode[QF_CG + 1] >= 0 || dir.ncode[QF_CG + 2] >= 0;
   const double sn = dt * theta, so = dt * (1.0 - theta);
-  const int nent = nc * nc;
   int ei[NPL], ej[NPL];
-  double acc[NPL];
+  double acc[NPL], F = 0.0;
 #pragma unroll
   for (int k = 0; k < NPL; k++) {
     const int e = lane + L * k;
-    if (active && e < nent) {
+    if (active && e < nc * nc) {
       ei[k] = e / nc;
       ej[k] = e - ei[k] * nc;
     } else {
@@ -82,7 +83,6 @@ __device__ __forceinline__ void transient_element_pass(bool active, int lane, in
     }
     acc[k] = 0.0;
   }
-  double F = 0.0;
   __syncthreads();
   for (int g0 = 0; g0 < ng; g0 += gcm) {
     const int gc = min(gcm, ng - g0);
@@ -126,17 +126,7 @@ __device__ __forceinline__ void transient_element_pass(bool active, int lane, in
         for (int q = 0; q < 3; q++) PT[l * QF_PT + 4 + q] = xq[q];
       }
     __syncthreads();
-    if (active)
-      for (int t = lane; t < gc * nc; t += L) {        // (B)
-        const int l = t / nc, n = t - l * nc;
-        const double* dp = dphi + ((size_t)(g0 + l) * nc + n) * dim;
-        for (int q = 0; q < 3; q++) {
-          double sacc = 0.0;
-          if (q < dim)
-            for (int p = 0; p < dim; p++) sacc += JI[l * 9 + q * 3 + p] * dp[p];
-          G[(l * ns + n) * 3 + q] = sacc;
-        }
-      }
+    if (active) eb_chunk_gradients<L, true>(lane, g0, gc, nc, ns, dim, dphi, JI, 9, G);      // (B)
     __syncthreads();
     if (active)
       for (int l = lane; l < gc; l += L) {             // (C)
@@ -172,17 +162,7 @@ __device__ __forceinline__ void transient_element_pass(bool active, int lane, in
         }
       }
     __syncthreads();
-    if (active && (useS || useT))
-      for (int t = lane; t < gc * nc; t += L) {        // (C')
-        const int l = t / nc, n = t - l * nc;
-        const double* gn = G + (l * ns + n) * 3;
-        double S = 0.0;
-        for (int q = 0; q < dim; q++) S += gn[q] * GU[l * 3 + q];
-        double T = PT[l * QF_PT + 3] * phi[(size_t)(g0 + l) * nc + n];
-        for (int q = 0; q < dim; q++) T += PT[l * QF_PT + 4 + q] * gn[q];
-        ST[(l * ns + n) * 2] = S;
-        ST[(l * ns + n) * 2 + 1] = T;
-      }
+    if (active && (useS || useT)) eb_chunk_st<L>(lane, g0, gc, nc, dim, phi, G, GU, PT, ST);     // (C')
     if (useS || useT) __syncthreads();
 #pragma unroll
     for (int k = 0; k < NPL; k++)                      // (D)
@@ -233,28 +213,9 @@ __global__ __launch_bounds__(GP_THREADS) void k_gen_transient(int nslot, int nc,
                                                               GenFormDir dir, const int* __restrict__ pcode, const double* __restrict__ pconst,
                                                               double* __restrict__ Kb, double* __restrict__ Fb) {
   extern __shared__ __attribute__((aligned(16))) double transient_smem[];
-  constexpr int EPG = GP_THREADS / L;
-  constexpr int NPL = qf_entries_per_lane(L);
-  const int ntab = TL ? ng + ng * nc + ng * nc * dim : 0;
-  const int per = (int)tr_elem_doubles(nc, gcm);
-  const int sub = threadIdx.x / L, lane = threadIdx.x % L;
-  const int slot = blockIdx.x * EPG + sub;
-  const bool active = slot < nslot;              // tail sub-groups keep the barriers and touch nothing
-  const double *w, *phi, *dphi;
-  if (TL) {
-    double* tw = transient_smem;
-    double* tphi = tw + ng;
-    double* tdphi = tphi + ng * nc;
-    for (int t = threadIdx.x; t < ng; t += GP_THREADS) tw[t] = gw[t];
-    for (int t = threadIdx.x; t < ng * nc; t += GP_THREADS) tphi[t] = gphi[t];
-    for (int t = threadIdx.x; t < ng * nc * dim; t += GP_THREADS) tdphi[t] = gdphi[t];
-    w = tw, phi = tphi, dphi = tdphi;
-  } else {
-    w = gw, phi = gphi, dphi = gdphi;
-  }
-  const size_t s0 = active ? (size_t)slot : 0;   // a tail sub-group forms no address past the tables
-  transient_element_pass<L, NPL>(active, lane, nc, ng, gcm, dim, w, phi, dphi, ed + s0 * nc, coords, sol, sol_old, time, dt, theta, dir, pcode, pconst,
-                                 transient_smem + ntab + (size_t)sub * per, Kb + s0 * nc * nc, Fb + s0 * nc);
+  const EbGroup g = eb_prologue<L, TL>(transient_smem, nslot, nc, ng, dim, (int)tr_elem_doubles(nc, gcm), gw, gphi, gdphi);
+  transient_element_pass<L, gp_entries_per_lane(L)>(g.active, g.lane, nc, ng, gcm, dim, g.w, g.phi, g.dphi, ed + (size_t)g.slot * nc, coords, sol, sol_old, time, dt,
+                                                    theta, dir, pcode, pconst, g.lds, Kb + (size_t)g.slot * nc * nc, Fb + (size_t)g.slot * nc);
 }
 
 namespace {
@@ -267,45 +228,14 @@ struct TrCall {
 };
 }  // namespace
 
-template <int L, bool TL>
-static void tr_launch_t(fh_generic_assembler_t as, int k, const TrCall& c) {
-  hipLaunchKernelGGL((k_gen_transient<L, TL>), dim3(fh_div_up(as->nslot[k], GP_THREADS / L)), dim3(GP_THREADS), as->tr_lds[k], as->ctx->stream, as->nslot[k], as->nc[k],
-                     as->ng[k], as->tr_gcm[k], as->dim, as->d_w[k], as->d_phi[k], as->d_dphi[k], as->d_ed[k], as->d_coords, c.sol, c.sol_old, c.time, c.dt, c.theta, c.dir,
-                     c.pcode, c.pconst, as->d_Kb + as->rows.kb_base[k], as->d_Fb + as->rows.row_base[k]);
-}
 static void tr_launch(fh_generic_assembler_t as, int k, const TrCall& c) {
-  const bool tl = as->tr_tl[k];
-  switch (as->lanes[k]) {
-    case 16: tl ? tr_launch_t<16, true>(as, k, c) : tr_launch_t<16, false>(as, k, c); break;
-    case 32: tl ? tr_launch_t<32, true>(as, k, c) : tr_launch_t<32, false>(as, k, c); break;
-    default: tl ? tr_launch_t<64, true>(as, k, c) : tr_launch_t<64, false>(as, k, c); break;
-  }
-}
-
-// first assemble_transient: per shape the largest Gauss chunk <= 32 that fits GP_LDS_BUDGET, evened out over the chunks it makes (ng = 16 at a limit of 14 goes
-// as 8 + 8, not 14 + 2); the tables are staged where they still fit beside it.  Nothing is kept unless every shape fits
-static int tr_plan(fh_generic_assembler_t as) {
-  int gcm[3] = {0, 0, 0};
-  bool tl[3] = {false, false, false};
-  size_t lds[3] = {0, 0, 0};
-  for (int k = 0; k < as->ns; k++) {
-    const int L = as->lanes[k], epg = GP_THREADS / L, nc = as->nc[k], ng = as->ng[k];
-    FH_REQUIRE(qf_entries_per_lane(L) * L >= nc * nc, "fh_generic_assembler_assemble_transient: shape %d: %d entries of an element on %d lanes", as->shapes[k], nc * nc,
-               L);
-    int gmax = std::min(ng, 32);
-    while (gmax > 1 && epg * tr_elem_doubles(nc, gmax) * sizeof(double) > GP_LDS_BUDGET) gmax--;
-    FH_REQUIRE(epg * tr_elem_doubles(nc, gmax) * sizeof(double) <= GP_LDS_BUDGET,
-               "fh_generic_assembler_assemble_transient: shape %d does not fit the LDS of a workgroup with the transient element body", as->shapes[k]);
-    const int nchunk = (ng + gmax - 1) / gmax, gc = (ng + nchunk - 1) / nchunk;
-    const size_t base = epg * tr_elem_doubles(nc, gc) * sizeof(double);
-    const size_t tab = ((size_t)ng * (1 + nc + nc * as->dim)) * sizeof(double);
-    gcm[k] = gc;
-    tl[k] = base + tab <= GP_LDS_BUDGET;
-    lds[k] = base + (tl[k] ? tab : 0);
-  }
-  for (int k = 0; k < 3; k++) as->tr_gcm[k] = gcm[k], as->tr_tl[k] = tl[k], as->tr_lds[k] = lds[k];
-  as->tr_ready = true;
-  return 0;
+  const GenBodyPlan& P = as->transient;
+  gp_dispatch(P, k, [&](auto lanes, auto staged) {
+    constexpr int L = decltype(lanes)::value;
+    hipLaunchKernelGGL((k_gen_transient<L, decltype(staged)::value>), dim3(fh_div_up(as->nslot[k], GP_THREADS / L)), dim3(GP_THREADS), P.lds[k], as->ctx->stream,
+                       as->nslot[k], as->nc[k], as->ng[k], P.gcm[k], as->dim, as->d_w[k], as->d_phi[k], as->d_dphi[k], as->d_ed[k], as->d_coords, c.sol, c.sol_old, c.time,
+                       c.dt, c.theta, c.dir, c.pcode, c.pconst, as->d_Kb + as->rows.kb_base[k], as->d_Fb + as->rows.row_base[k]);
+  });
 }
 
 extern "C" int fh_generic_assembler_assemble_transient(fh_generic_assembler_t as, fh_vec_t sol, fh_vec_t sol_old, const fh_quasilinear_form_t* form, double time,
@@ -326,7 +256,9 @@ extern "C" int fh_generic_assembler_assemble_transient(fh_generic_assembler_t as
   std::vector<int> code;
   std::vector<double> consts;
   FH_TRY(qf_gather_programs(who, as, form, TR_VARS, "x, y, z, u, ux, uy, uz, t", c.dir, code, consts));
-  if (!as->tr_ready) FH_TRY(tr_plan(as));
+  // the first call: this body's plan on the Poisson body's lanes, with the evened chunk rule (ng = 16 at a limit of 14 goes as 8 + 8, not 14 + 2)
+  if (!as->transient.ready)
+    FH_TRY(gp_plan_body(who, as, as->poisson.lanes, tr_elem_doubles, true, true, "an element", " with the transient element body", as->transient));
   FH_TRY(gp_upload_program(who, as, code, consts));
   c.sol = sol ? sol->d : nullptr, c.sol_old = sol_old->d, c.time = time, c.dt = dt, c.theta = theta;
   c.pconst = (const double*)as->d_prog;
@@ -343,6 +275,6 @@ extern "C" int fh_generic_assembler_assemble_transient(fh_generic_assembler_t as
 
 extern "C" int fh_generic_assembler_transient_chunks(fh_generic_assembler_t as, int gauss_chunk[3]) {
   FH_REQUIRE(as && gauss_chunk, "fh_generic_assembler_transient_chunks: null argument");
-  for (int k = 0; k < 3; k++) gauss_chunk[k] = k < as->ns ? as->tr_gcm[k] : 0;
+  gp_read_plan(as, as->transient, gauss_chunk, nullptr);
   return 0;
 }
