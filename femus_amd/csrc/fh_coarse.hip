@@ -7,9 +7,6 @@
 #include <memory>
 #include <cmath>
 
-int fh_direct_solve_ptr(fh_direct_t d, const double* b, double* x);
-uint64_t fh_direct_generation(fh_direct_t d);      // changes whenever the object re-analysed its operator (new device buffers, new launch shapes)
-
 // y = Ainv b, one wave per row, 16-byte loads
 __global__ __launch_bounds__(256) void k_dense_gemv(const double* __restrict__ M, const double* __restrict__ b, double* __restrict__ y, int n) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);

@@ -162,9 +162,7 @@ extern "C" int fh_halo_sizes(fh_halo_t h, int* nsend, int* nrecv) {
   return 0;
 }
 
-int fh_halo_update_ptr(fh_halo_t h, double* vd, int n_owned);
 int fh_halo_begin_ptr(fh_halo_t h, double* vd, int n_owned, bool prepacked = false);
-int fh_halo_end_ptr(fh_halo_t h);
 
 extern "C" int fh_halo_update(fh_halo_t h, fh_vec_t v) {
   FH_REQUIRE(h && v, "fh_halo_update: null argument");

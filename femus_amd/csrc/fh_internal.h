@@ -277,6 +277,12 @@ int fh_dev_spmv_part(fh_mat_t A, int n_own_cols, int part, const double* x, doub
 // y = op(A, x) for an operator over [owned | ghost] columns: ghost exchange of x overlapped with the rows that need no ghost
 int fh_dev_halo_spmv(fh_halo_t h, fh_mat_t A, double* x, int n_own, double* y, int mode, const double* b, const double* dinv, double omega,
                      bool prepacked = false);
+int fh_dev_get_diag(fh_mat_t A, double* d, int invert);
+int fh_halo_update_ptr(fh_halo_t h, double* vd, int n_owned);
+int fh_halo_end_ptr(fh_halo_t h);
+int fh_halo_allreduce_ptr(fh_halo_t h, double* d, int n);
+int fh_direct_solve_ptr(fh_direct_t d, const double* b, double* x);
+uint64_t fh_direct_generation(fh_direct_t d);      // changes whenever the object re-analysed its operator (new device buffers, new launch shapes)
 void fh_halo_send_plan(fh_halo_t h, const int** send_idx, double** sendbuf, int* nsend);
 
 static inline int fh_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

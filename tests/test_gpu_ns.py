@@ -52,36 +52,54 @@ def test_element_jacobian_and_assembly_match_oracle(ctx, box):
     asm.destroy(), A.destroy(), mh.destroy()
 
 
-@pytest.mark.parametrize("persistent", [0, 1, 2])
-def test_vanka_vcycle_matches_oracle(ctx, persistent):
-    """one multiplicative V(2,2) cycle with the block Schwarz smoother on the Jacobian of a non-trivial state; the sweep as one residual + one
-    patch launch per colour (default) and as one launch with device-wide barriers between the colours (two barrier forms)"""
-    ctx.set_option("vanka_persistent", persistent)
-    ctx.set_option("patch_invert_lds", 0 if persistent == 2 else 1)      # patch inverses by the workgroup kernel on global memory as well
-    nu, nl = 0.01, 3
-    pb = NavierStokesMG(ctx, 4, 4, 0, nl, nu).init()
-    ms, lays = ns.build_ns_levels(4, 4, 0, nl, LO, HI)
-    bcs = [ns.cavity_bc(m, l) for m, l in zip(ms, lays)]
-    rng = np.random.default_rng(5)
-    top = nl - 1
-    state = 0.3 * rng.standard_normal(lays[top].n)
-    state[bcs[top][0]] = bcs[top][1]
-    pb.SOL[top].upload(state)
-    mg = pb.prepare(top)
-    H = ns.newton_step_operators(ms, lays, bcs, top, state, nu, omega=pb.omega, npre=pb.npre, npost=pb.npost)
-    for l in range(nl):
-        assert np.array_equal(pb.bdc[l], bcs[l][0])
-        assert abs(pb.A[(top, l)].to_scipy() - H.A[l]).max() <= 1e-11 * abs(H.A[l]).max()
-    assert rel(pb.RES[top].to_numpy(), H.b) < 1e-12
-    b = rng.standard_normal(lays[top].n)
-    b[bcs[top][0]] = 0.0
-    x = ctx.vector(lays[top].n)
-    mg.vcycle(ctx.vector_from(b), x)
-    ref = ns.vcycle(H, top, b)
-    assert rel(x.to_numpy(), ref) < 1e-9
-    pb.destroy()
-    ctx.set_option("vanka_persistent", 0)
-    ctx.set_option("patch_invert_lds", 1)
+@pytest.mark.parametrize("persistent,fused", [pytest.param(0, 1, id="0"), pytest.param(1, 1, id="1"), pytest.param(2, 1, id="2"), pytest.param(0, 0, id="unfused")])
+def test_vanka_vcycle_matches_oracle(ctx, persistent, fused):
+    """one multiplicative V(2,2) cycle with the block Schwarz smoother on the Jacobian of a non-trivial state; the sweep as one patch launch per
+    colour (default), as one launch with device-wide barriers between the colours (two barrier forms), and as one residual of the whole level
+    + one patch launch per colour (option vanka_fused 0: the statement the oracle's smoother makes; the residual goes through the level's
+    residual vector).  The unfused cycle of a second, fresh object under the same options has the same bits."""
+    made = []
+    try:
+        ctx.set_option("vanka_persistent", persistent)
+        ctx.set_option("vanka_fused", fused)
+        ctx.set_option("patch_invert_lds", 0 if persistent == 2 else 1)      # patch inverses by the workgroup kernel on global memory as well
+        nu, nl = 0.01, 3
+        pb = NavierStokesMG(ctx, 4, 4, 0, nl, nu).init()
+        made.append(pb)
+        ms, lays = ns.build_ns_levels(4, 4, 0, nl, LO, HI)
+        bcs = [ns.cavity_bc(m, l) for m, l in zip(ms, lays)]
+        rng = np.random.default_rng(5)
+        top = nl - 1
+        state = 0.3 * rng.standard_normal(lays[top].n)
+        state[bcs[top][0]] = bcs[top][1]
+        pb.SOL[top].upload(state)
+        mg = pb.prepare(top)
+        H = ns.newton_step_operators(ms, lays, bcs, top, state, nu, omega=pb.omega, npre=pb.npre, npost=pb.npost)
+        for l in range(nl):
+            assert np.array_equal(pb.bdc[l], bcs[l][0])
+            assert abs(pb.A[(top, l)].to_scipy() - H.A[l]).max() <= 1e-11 * abs(H.A[l]).max()
+        assert rel(pb.RES[top].to_numpy(), H.b) < 1e-12
+        b = rng.standard_normal(lays[top].n)
+        b[bcs[top][0]] = 0.0
+        x = ctx.vector(lays[top].n)
+        mg.vcycle(ctx.vector_from(b), x)
+        ref = ns.vcycle(H, top, b)
+        err = rel(x.to_numpy(), ref)
+        print("vanka_persistent %d vanka_fused %d: %.2e from the oracle's cycle" % (persistent, fused, err))
+        assert err < 1e-9
+        if not fused:
+            fresh = NavierStokesMG(ctx, 4, 4, 0, nl, nu).init()
+            made.append(fresh)
+            fresh.SOL[top].upload(state)
+            y = ctx.vector(lays[top].n)
+            fresh.prepare(top).vcycle(ctx.vector_from(b), y)
+            assert np.array_equal(x.to_numpy(), y.to_numpy())
+    finally:
+        ctx.set_option("vanka_persistent", 0)
+        ctx.set_option("vanka_fused", 1)
+        ctx.set_option("patch_invert_lds", 1)
+        for o in made:
+            o.destroy()
 
 
 def test_cavity_newton_fcycle_matches_oracle(ctx):
@@ -215,49 +233,60 @@ def test_three_dimensional_cavity_matches_oracle(ctx):
     pb.destroy()
 
 
-@pytest.mark.parametrize("level_solver,n_exact", [("richardson", 0), ("gmres", 0), ("richardson", 5)])
-def test_pcasm_as_the_reference_configures_it(ctx, level_solver, n_exact):
+@pytest.mark.parametrize("level_solver,n_exact,fused", [pytest.param("richardson", 0, 1, id="richardson-0"), pytest.param("gmres", 0, 1, id="gmres-0"),
+                                                        pytest.param("richardson", 5, 1, id="richardson-5"),
+                                                        pytest.param("richardson", 0, 0, id="richardson-0-unfused"), pytest.param("gmres", 0, 0, id="gmres-0-unfused")])
+def test_pcasm_as_the_reference_configures_it(ctx, level_solver, n_exact, fused):
     """FH_SMOOTH_ASM: PC_ASM_BASIC + PC_COMPOSITE_MULTIPLICATIVE over the element blocks in their index order with ILU(0) (zero pivot 1e-16,
     MAT_SHIFT_NONZERO) sub-solves (PetscPreconditioner.cpp:179-184, LinearEquationSolverPetscAsm.cpp:278-335): one V(2,2) cycle on the
     Jacobian of a non-trivial state against the oracle's sequential restatement, Richardson and GMRES level solvers; n_exact: the leading blocks
-    with the EXACT sub-solve the reference gives the solid / porous blocks (`_blockTypeRange[1]`, :298-307)"""
-    nu, nl = 0.01, 3
-    pb = NavierStokesMG(ctx, 4, 4, 0, nl, nu).init()
-    pb.smoother = capi.SMOOTH_ASM
-    ms, lays = ns.build_ns_levels(4, 4, 0, nl, LO, HI)
-    bcs = [ns.cavity_bc(m, l) for m, l in zip(ms, lays)]
-    rng = np.random.default_rng(5)
-    top = nl - 1
-    state = 0.3 * rng.standard_normal(lays[top].n)
-    state[bcs[top][0]] = bcs[top][1]
-    pb.SOL[top].upload(state)
-    mg = pb.prepare(top)
-    if level_solver == "gmres" or n_exact:
-        for l in range(1, nl):
-            if level_solver == "gmres":
-                mg.set_level_solver(l, "gmres", 30)
-            mg.set_level_patches_exact(l, n_exact)
-        mg.setup()
-    # ILU(0) fills the ALLOCATED pattern (stored zeros included): the pattern is taken from the device operators, the values are the oracle's
-    H = ns.newton_step_operators(ms, lays, bcs, top, state, nu, omega=pb.omega, npre=pb.npre, npost=pb.npost, smoother="asm",
-                                 patterns=[pb.A[(top, l)].pattern() for l in range(nl)], asm_exact=n_exact)
-    b = rng.standard_normal(lays[top].n)
-    b[bcs[top][0]] = 0.0
-    x = ctx.vector(lays[top].n)
-    mg.vcycle(ctx.vector_from(b), x)
-    if level_solver == "richardson":
-        ref = ns.vcycle(H, top, b)
-    else:
-        def cyc(level, rhs):
-            if level == 0:
-                return H.coarse_solve(rhs)
-            A, sm = H.A[level], H.smoother[level]
-            xx = fo.smooth_gmres(A, rhs, np.zeros_like(rhs), H.npre, True, sm.apply)
-            xx = xx + H.P[level] @ cyc(level - 1, H.P[level].T @ (rhs - A @ xx))
-            return fo.smooth_gmres(A, rhs, xx, H.npost, False, sm.apply)
-        ref = cyc(top, b)
-    assert rel(x.to_numpy(), ref) < 1e-9
-    pb.destroy()
+    with the EXACT sub-solve the reference gives the solid / porous blocks (`_blockTypeRange[1]`, :298-307); fused 0 (option vanka_fused): the
+    block sweep behind a residual of the whole level, whose work vector the two level solvers hand over from different places"""
+    pb = None
+    try:
+        ctx.set_option("vanka_fused", fused)
+        nu, nl = 0.01, 3
+        pb = NavierStokesMG(ctx, 4, 4, 0, nl, nu).init()
+        pb.smoother = capi.SMOOTH_ASM
+        ms, lays = ns.build_ns_levels(4, 4, 0, nl, LO, HI)
+        bcs = [ns.cavity_bc(m, l) for m, l in zip(ms, lays)]
+        rng = np.random.default_rng(5)
+        top = nl - 1
+        state = 0.3 * rng.standard_normal(lays[top].n)
+        state[bcs[top][0]] = bcs[top][1]
+        pb.SOL[top].upload(state)
+        mg = pb.prepare(top)
+        if level_solver == "gmres" or n_exact:
+            for l in range(1, nl):
+                if level_solver == "gmres":
+                    mg.set_level_solver(l, "gmres", 30)
+                mg.set_level_patches_exact(l, n_exact)
+            mg.setup()
+        # ILU(0) fills the ALLOCATED pattern (stored zeros included): the pattern is taken from the device operators, the values are the oracle's
+        H = ns.newton_step_operators(ms, lays, bcs, top, state, nu, omega=pb.omega, npre=pb.npre, npost=pb.npost, smoother="asm",
+                                     patterns=[pb.A[(top, l)].pattern() for l in range(nl)], asm_exact=n_exact)
+        b = rng.standard_normal(lays[top].n)
+        b[bcs[top][0]] = 0.0
+        x = ctx.vector(lays[top].n)
+        mg.vcycle(ctx.vector_from(b), x)
+        if level_solver == "richardson":
+            ref = ns.vcycle(H, top, b)
+        else:
+            def cyc(level, rhs):
+                if level == 0:
+                    return H.coarse_solve(rhs)
+                A, sm = H.A[level], H.smoother[level]
+                xx = fo.smooth_gmres(A, rhs, np.zeros_like(rhs), H.npre, True, sm.apply)
+                xx = xx + H.P[level] @ cyc(level - 1, H.P[level].T @ (rhs - A @ xx))
+                return fo.smooth_gmres(A, rhs, xx, H.npost, False, sm.apply)
+            ref = cyc(top, b)
+        err = rel(x.to_numpy(), ref)
+        print("%s level solver, %d exact blocks, vanka_fused %d: %.2e from the oracle's cycle" % (level_solver, n_exact, fused, err))
+        assert err < 1e-9
+    finally:
+        ctx.set_option("vanka_fused", 1)
+        if pb is not None:
+            pb.destroy()
 
 
 def _channel_bc(inlet, outlet, p_in, p_out):
