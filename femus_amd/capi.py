@@ -1812,7 +1812,8 @@ class Multigrid:
                                     int(smoother), float(omega), int(npre), int(npost)))
 
     def set_level_patches(self, level, ptr, dofs):
-        """dof patches of the block Schwarz (Vanka) smoother of a level (smoother=2)"""
+        """dof patches of the block Schwarz smoothers of a level (SMOOTH_VANKA, SMOOTH_ASM): 1..512 dofs each, every dof once; the order of the dofs
+        inside a patch does not matter (the library sorts it), the order of the patches is the one SMOOTH_ASM visits them in"""
         ptr, dofs = _i32(ptr), _i32(dofs)
         _chk(self.L.fh_mg_set_level_patches(self.h, int(level), ptr.size - 1, _p(ptr), _p(dofs)))
 

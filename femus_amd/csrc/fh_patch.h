@@ -6,7 +6,10 @@
 // buffers of the sweep.  Lifetime: the patch lists live from fh_patch_set to the next fh_patch_set; everything derived from the matrix pattern
 // (colours, device copies, inverses) lives from fh_patch_setup to fh_patch_drop_setup, fh_patch_set or a fh_patch_setup of the other kind
 struct PatchSmoother;
-// the patches of the level (ptr: npatch + 1 offsets into dofs); creates *ps on first use, drops the setup, no block gets the exact sub-solve
+// the patches of the level (ptr: npatch + 1 offsets into dofs); creates *ps on first use, drops the setup, no block gets the exact sub-solve.
+// The ORDER of the dofs inside a patch does not matter: every patch is kept sorted ascending (the order of PCASM's index sets, in which ILU(0) of a
+// block is taken).  Refused, leaving the patches of the level as they were: a patch that is empty or has more than 512 dofs, a dof listed twice
+// in one patch.  (A dof outside the matrix and a singular patch matrix are refused by fh_patch_setup, which is the first to see the matrix.)
 int fh_patch_set(PatchSmoother** ps, int npatch, const int* ptr, const int* dofs);
 // FH_SMOOTH_ASM: the first nfirst blocks get the exact sub-solve instead of ILU(0)
 int fh_patch_set_exact(PatchSmoother* ps, int nfirst);

@@ -456,17 +456,32 @@ void fh_patch_destroy(PatchSmoother* ps) {
 int fh_patch_count(const PatchSmoother* ps) { return ps ? ps->npatch : 0; }
 
 int fh_patch_set(PatchSmoother** ps, int npatch, const int* ptr, const int* dofs) {
+  // checked on a copy: a list that is refused leaves the patches of the level as they were
+  for (int p = 0; p < npatch; p++) {
+    const int np = ptr[p + 1] - ptr[p];
+    FH_REQUIRE(np > 0 && np <= 512, "fh_mg_set_level_patches: patch %d has %d dofs (1..512 supported)", p, np);
+  }
+  // every patch in ASCENDING dof order, whatever order the caller gave it in: the order PCASM's index sets have (the reference sorts every block before
+  // ISCreateGeneral, LinearEquationSolverPetscAsm.cpp:253-254) and the one ILU(0) of a block is defined in; the Vanka sweep does not depend on it beyond
+  // rounding.  A dof listed twice would give x[d] two writers in one patch and two equal rows in its matrix
+  std::vector<int> sorted(dofs + ptr[0], dofs + ptr[npatch]);
+  for (int p = 0; p < npatch; p++) {
+    auto b = sorted.begin() + (ptr[p] - ptr[0]), e = sorted.begin() + (ptr[p + 1] - ptr[0]);
+    std::sort(b, e);
+    auto dup = std::adjacent_find(b, e);
+    FH_REQUIRE(dup == e, "fh_mg_set_level_patches: patch %d lists dof %d twice", p, dup == e ? 0 : *dup);
+  }
   if (!*ps) *ps = new PatchSmoother();
   PatchSmoother& S = **ps;
   fh_patch_drop_setup(&S);
   S.npatch = npatch;
-  S.h_pptr.assign(ptr, ptr + npatch + 1);
-  S.h_pdofs.assign(dofs, dofs + ptr[npatch]);
+  S.h_pptr.resize(npatch + 1);
+  for (int p = 0; p <= npatch; p++) S.h_pptr[p] = ptr[p] - ptr[0];
+  S.h_pdofs.swap(sorted);
   S.h_poff.assign(npatch + 1, 0);
   S.max_patch = 0;
   for (int p = 0; p < npatch; p++) {
-    const int np = ptr[p + 1] - ptr[p];
-    FH_REQUIRE(np > 0 && np <= 512, "fh_mg_set_level_patches: patch %d has %d dofs (1..512 supported)", p, np);
+    const int np = S.h_pptr[p + 1] - S.h_pptr[p];
     S.max_patch = std::max(S.max_patch, np);
     S.h_poff[p + 1] = S.h_poff[p] + (int64_t)np * np;
   }

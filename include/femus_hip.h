@@ -773,7 +773,11 @@ int fh_mg_set_level(fh_mg_t mg, int level, fh_mat_t A, fh_mat_t P, fh_mat_t R, i
 /* FH_SMOOTH_VANKA: block Schwarz smoother for saddle-point systems (the FEMuS_ASM choice of the Navier-Stokes applications,
  * petsc_asm/LinearEquationSolverPetscAsm.cpp:91-345): x_p += omega A_pp^-1 (b - A x)_p per patch of dofs, multiplicative over
  * conflict-free colours of patches.  Patches (fh_mesh_vertex_patches) are given per level before fh_mg_setup, which
- * extracts and inverts the patch matrices (dense, partial pivoting) from the level's current operator. */
+ * extracts and inverts the patch matrices (dense, partial pivoting) from the level's current operator.
+ * A patch has 1..512 dofs, each listed once; the order of the dofs INSIDE a patch does not matter (the library keeps every patch sorted ascending, the
+ * order of PCASM's index sets -- LinearEquationSolverPetscAsm.cpp:253-254 -- in which FH_SMOOTH_ASM takes ILU(0) of a block); the order of the PATCHES
+ * is the order FH_SMOOTH_ASM visits them in.  An empty or too large patch and a dof listed twice are refused here, a dof that is no row of the level's
+ * operator and a singular patch matrix by fh_mg_setup; a refused list leaves the patches of the level as they were. */
 int fh_mg_set_level_patches(fh_mg_t mg, int level, int npatch, const int* ptr /* [npatch+1] */, const int* dofs);
 /* FH_SMOOTH_ASM only: the first `nfirst` blocks of the list get the EXACT sub-solve instead of ILU(0) -- what FEMuS_ASM gives the blocks of the solid and
  * the porous elements, which MeshASMPartitioning::DoPartition puts first (`_blockTypeRange[1]`; MLU_PRECOND on them, LinearEquationSolverPetscAsm.cpp:298-307).
