@@ -26,6 +26,7 @@
 // marks and a compaction give the ascending list.
 #include "fh_elemmesh.h"
 #include "fh_fe.h"
+#include "fh_spmv.h"
 
 namespace {
 constexpr int ET_CAP = 1024;                    // candidates one wave sorts in LDS
@@ -385,7 +386,7 @@ extern "C" int fh_elem_mesh_prolongator(fh_elem_mesh_t C, fh_elem_mesh_t F, int 
   if (ns) hipLaunchKernelGGL(k_et_slow_fill, dim3(ns), dim3(256), 0, st, A, d_srow, d_soff, d_gcol, d_gkey, d_gwin, P->d_rowptr, P->d_col, P->d_val);
   he = hipGetLastError();
   if (he == hipSuccess) he = hipStreamSynchronize(st);
-  if (he == hipSuccess && fh_mat_build_rowblocks(P, ctx->spmv_tile)) {
+  if (he == hipSuccess && fh_spmv_build_rowblocks(P)) {
     fh_mat_destroy(P);
     return fail(2);
   }

@@ -155,6 +155,7 @@ struct fh_vec_s {
   bool gacc_dirty = false;
 };
 
+struct SpmvPlan;
 struct fh_mat_s {
   fh_ctx_t ctx = nullptr;
   fh_stage_s* stage = nullptr;
@@ -166,27 +167,8 @@ struct fh_mat_s {
   int* d_col = nullptr;
   double* d_val = nullptr;
   std::vector<int> h_rowptr, h_col;   // host copy of the pattern (setup-time integer work)
-  // CSR-stream row blocks
-  int tile = 0;
-  int tile_kernel = 0;
-  int nblk = 0;
-  int* d_rowblk = nullptr;
-  std::vector<int> h_rowblk;
-  // tile-local column compaction (spmv_kernel 3): unique columns per row block + 16-bit local indices
-  int* d_uptr = nullptr;
-  int* d_ucols = nullptr;
-  unsigned short* d_lcol = nullptr;
-  int* d_tile_s = nullptr;             // first non-zero of every row block (persistent pipelined kernel)
-  int* d_blkinfo = nullptr;            // 8 ints per row block: r0, r1, s, e, u0, nu (one descriptor load instead of a pointer chain)
-  int lx_tile = 0;
-  int64_t nu_total = 0;                // sum over the row blocks of their distinct columns (entries of d_ucols)
   int max_row = 0;
-  // interior / interface split of the row blocks for operators over [owned | ghost] columns (fh_dev_spmv_part):
-  // descriptors permuted so that blocks without a ghost column come first
-  int split_nown = -1;                 // number of owned columns the split was built for (-1: none)
-  int split_tile = 0;
-  int nblk_int = 0;
-  int* d_blkinfo_split = nullptr;
+  SpmvPlan* spmv = nullptr;            // row blocks, local columns and interior / interface split of the product kernels (fh_spmv.h)
   int* d_diagpos = nullptr;            // position of every row's diagonal entry (-1: none), built by the first fh_dev_get_diag
   // cached explicit transpose for matrix_mult_transpose
   fh_mat_t At = nullptr;
@@ -267,8 +249,6 @@ int fh_mesh_device(fh_ctx_t ctx, fh_mesh_t m, fh_mesh_dev** dev);
 
 // kernels / helpers implemented across TUs
 int fh_reserve_reduction(fh_ctx_t ctx, size_t ndoubles);
-int fh_mat_build_rowblocks(fh_mat_t A, int tile);
-int fh_mat_build_localcols(fh_mat_t A);
 int fh_mat_refresh_transpose(fh_mat_t A);   // re-gather values into the cached transpose
 int fh_dev_spmv(fh_mat_t A, const double* x, double* y, int mode, const double* b, const double* dinv, double omega);
 // part 0: the row blocks that read no column >= n_own_cols (no ghost), part 1: the others; part 0 + part 1 = fh_dev_spmv

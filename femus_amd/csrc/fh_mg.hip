@@ -15,6 +15,7 @@
 #include "fh_coarse.h"
 #include "fh_krylov.h"
 #include "fh_patch.h"
+#include "fh_spmv.h"
 #include "fh_trisolve.h"
 #include <algorithm>
 #include <memory>
@@ -204,11 +205,9 @@ static uint64_t cycle_signature(fh_mg_t mg) {
     if (M) {
       mix(M->uid);
       mixp(M->d_val);
-      mixp(M->d_blkinfo);
-      mixp(M->d_rowblk);
-      mix((uint64_t)M->nblk);
-      mix((uint64_t)M->tile);
-      mix((uint64_t)M->lx_tile);
+      std::vector<uint64_t> sw;
+      fh_spmv_signature(M, sw);
+      for (uint64_t w : sw) mix(w);
     }
   };
   mix((uint64_t)mg->nlevels);

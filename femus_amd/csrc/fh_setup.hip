@@ -1,6 +1,6 @@
 // Setup work that runs on the device but belongs to host-side modules (fh_mesh.cpp stays plain host C++ so that the sanitizer pass of
 // tests/asan_host.sh can rebuild it without the device compiler): the prolongator builder of fh_build_prolongator.
-#include "fh_internal.h"
+#include "fh_spmv.h"
 #include <algorithm>
 #include <vector>
 
@@ -144,7 +144,7 @@ int fh_prolongator_device(fh_ctx_t ctx, int nl, int nc, int nch, int nel_c, cons
                              P->d_rowptr, P->d_col, P->d_val);
   FH_CHECK_HIP(hipGetLastError());
   FH_CHECK_HIP(hipStreamSynchronize(st));
-  FH_TRY(fh_mat_build_rowblocks(P, ctx->spmv_tile));
+  FH_TRY(fh_spmv_build_rowblocks(P));
   *out = P;
   return 0;
 }

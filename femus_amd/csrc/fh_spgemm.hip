@@ -8,7 +8,7 @@
 //            output row, each lane owns output slots of the known sorted pattern and accumulates
 //            sum_k A[i,k] * B[k,c] in increasing k with a binary search in the short sorted row B[k,:].
 //            No atomics, no hash tables: deterministic, bit-reproducible operators.
-#include "fh_internal.h"
+#include "fh_spmv.h"
 #include <algorithm>
 #include <thread>
 
@@ -556,7 +556,7 @@ static int spgemm_symbolic_device(fh_mat_t A, fh_mat_t B, fh_mat_t* Cout) {
   FH_TRACE("spgemm symbolic: columns filled");
   hipFree(d_len);
   hipFree(d_err);
-  FH_TRY(fh_mat_build_rowblocks(C, c->spmv_tile));
+  FH_TRY(fh_spmv_build_rowblocks(C));
   FH_TRACE("spgemm symbolic: row blocks");
   *Cout = C;
   return 0;

@@ -169,6 +169,71 @@ def test_spmv_lds_buffer_modes(ctx, q2_matrix):
     assert rel(outs[0], A @ xs) < 1e-14
 
 
+SPMV_OPTION_DEFAULTS = {"spmv_threads": 256, "spmv_nt": 0, "spmv_xcd_remap": 32}
+
+
+@pytest.fixture(scope="module")
+def option_matrix():
+    """2049 x 2049 (one past the 2048 granularity), 64 sorted distinct columns per row: 129 row blocks at tile 1024 and 65 at tile 2048, so the
+    XCD remap (taken from 64 row blocks on) is crossed, with workgroups beyond the last block"""
+    rng = np.random.default_rng(2049)
+    n, per = 2049, 64
+    indices = np.concatenate([np.sort(rng.choice(n, size=per, replace=False)) for _ in range(n)]).astype(np.int32)
+    A = sp.csr_matrix((rng.uniform(-1, 1, n * per), indices, np.arange(n + 1) * per), shape=(n, n))
+    xs, bs, y0, dinv = rng.uniform(-1, 1, n), rng.uniform(-1, 1, n), rng.uniform(-1, 1, n), rng.uniform(0.5, 2.0, n)
+    Ax = A @ xs
+    return A, xs, bs, y0, dinv, [Ax, y0 + Ax, bs - Ax, xs + 0.7 * dinv * (bs - Ax)]
+
+
+@pytest.mark.parametrize("kernel,tile,option,value", [
+    (3, 1024, "spmv_threads", 128), (3, 2048, "spmv_threads", 128),
+    (2, 256, "spmv_nt", 1), (2, 1024, "spmv_nt", 1),
+    (0, 1024, "spmv_xcd_remap", 0), (0, 1024, "spmv_xcd_remap", 1),
+    (3, 1024, "spmv_xcd_remap", 0), (3, 1024, "spmv_xcd_remap", 1),
+    (4, 1024, "spmv_xcd_remap", 0), (4, 1024, "spmv_xcd_remap", 1)])
+def test_spmv_instantiation_and_grid_options(ctx, option_matrix, kernel, tile, option, value):
+    """the options that pick another instantiation or another grid of the same kernel: y = Ax, y += Ax, b - Ax and the Jacobi sweep against scipy, and
+    the same bits as under the option's default.  The same arithmetic in the same order in every case: spmv_xcd_remap only renumbers the workgroups;
+    spmv_nt only changes the cache hint of the matrix loads; spmv_threads 128 runs the row reduction of k_spmv_lx in twice as many passes, but the
+    lanes per row, the stride of a lane's partial sum and the shuffle tree depend on the block's row count alone, and the epilogue of the first pass
+    and that of the later ones (spmv_store) are the same expressions (no row here is longer than the tile: the long-row path does sum in NT strides)"""
+    A, xs, bs, y0, dinv, refs = option_matrix
+    n = A.shape[0]
+    ctx.set_option("spmv_kernel", kernel)
+    ctx.set_option("spmv_tile", tile)
+    try:
+        M = ctx.matrix_scipy(A)
+        x, b, d, y = ctx.vector_from(xs), ctx.vector_from(bs), ctx.vector_from(dinv), ctx.vector(n)
+
+        def four_modes():
+            out = []
+            y.matrix_mult(x, M)
+            out.append(y.to_numpy().copy())
+            y.assign(ctx.vector_from(y0))
+            y.add_vector(x, M)
+            out.append(y.to_numpy().copy())
+            y.resid(b, x, M)
+            out.append(y.to_numpy().copy())
+            y.jacobi_sweep(b, x, M, d, 0.7)
+            out.append(y.to_numpy().copy())
+            return out
+
+        ctx.set_option(option, value)
+        got = four_modes()
+        ctx.set_option(option, SPMV_OPTION_DEFAULTS[option])
+        base = four_modes()
+        for mode in range(4):
+            assert rel(got[mode], refs[mode]) < 1e-14, mode
+            assert rel(base[mode], refs[mode]) < 1e-14, mode
+            assert np.array_equal(got[mode], base[mode]), mode
+        M.destroy()
+    finally:
+        for name, default in SPMV_OPTION_DEFAULTS.items():
+            ctx.set_option(name, default)
+        ctx.set_option("spmv_tile", 2048)
+        ctx.set_option("spmv_kernel", 3)
+
+
 @pytest.mark.parametrize("seed", range(10))
 def test_spmv_family_random_shapes(ctx, seed):
     """random CSR matrices of awkward shapes (one row, one column, empty rows in runs, rows longer than several LDS tiles, blocks that
