@@ -1834,6 +1834,19 @@ class Multigrid:
         _chk(self.L.fh_mg_coarse_info(self.h, *[ctypes.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def sweep_info(self, level):
+        """which path serves the natural-order sweeps (SMOOTH_SOR, SMOOTH_ILU0) of a level, from the library's host bookkeeping: per direction the
+        levels of the schedule, the runs of small levels (one workgroup each), the levels inside runs, the longest run, the largest level inside a run
+        and the register slots of the run kernel; for ILU(0) the kernel of the last factorisation ("plan", "ahead", "lds_columns", "plain"; None before
+        one), its LDS bytes, the longest row the device grants each kernel, and the diagonal shift taken"""
+        f, b, u = (ctypes.c_int * 6)(), (ctypes.c_int * 6)(), (ctypes.c_int * 6)()
+        shift = ctypes.c_double()
+        _chk(self.L.fh_mg_sweep_info(self.h, int(level), f, b, u, ctypes.byref(shift)))
+        keys = ("levels", "runs", "levels_in_runs", "longest_run", "largest_level_in_run", "slots")
+        kernels = (None, "plain", "lds_columns", "ahead", "plan")
+        return {"forward": dict(zip(keys, f)), "backward": dict(zip(keys, b)),
+                "ilu": {"kernel": kernels[u[0]], "lds_bytes": u[1], "row_limit": dict(zip(kernels[:0:-1], u[2:6])), "shift": shift.value}}
+
     def set_coarse_coords(self, coords):
         """coordinates of the unknowns of level 0: the exact coarse solve then dissects its dense problem (fh_mg_set_coarse_coords)"""
         xy = _f64(coords)

@@ -682,6 +682,13 @@ extern "C" int fh_mg_coarse_info(fh_mg_t mg, int* n_dense, int* nd_blocks, int* 
   return 0;
 }
 
+extern "C" int fh_mg_sweep_info(fh_mg_t mg, int level, int* forward, int* backward, int* ilu, double* ilu_shift) {
+  FH_REQUIRE(mg && mg->setup_done, "fh_mg_sweep_info: fh_mg_setup has not been called");
+  FH_REQUIRE(level >= 0 && level < mg->nlevels && mg->lv[level].tri, "fh_mg_sweep_info: level %d has no natural-order sweep (FH_SMOOTH_SOR, FH_SMOOTH_ILU0)", level);
+  fh_tri_info(mg->lv[level].tri, forward, backward, ilu, ilu_shift);
+  return 0;
+}
+
 extern "C" int fh_mg_destroy(fh_mg_t mg) {
   if (!mg) return 0;
   hipStreamSynchronize(mg->ctx->stream);

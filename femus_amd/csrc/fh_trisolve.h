@@ -27,6 +27,9 @@ struct fh_tri_s {
   int* d_flag = nullptr;
   double* d_t = nullptr;                // symmetric sweep: t = r - L z of the forward half, read by the backward half
   double shift = 0.0;                   // diagonal shift the last factorisation needed (MAT_SHIFT_NONZERO)
+  // which path served the last factorisation (fh_tri_info): the kernel (FH_ILU_KERNEL_*, 0 before the first factorisation), the LDS bytes it asked for, and the
+  // longest row this device grants k_ilu_factor_plan / k_ilu_factor_ahead / k_ilu_factor<true> / k_ilu_factor<false>
+  int ilu_kernel = 0, ilu_lds = 0, ilu_rows[4] = {0, 0, 0, 0};
 };
 typedef fh_tri_s* fh_tri_t;
 
@@ -35,3 +38,7 @@ void fh_tri_destroy(fh_tri_t T);
 int fh_tri_ssor_apply(fh_tri_t T, fh_mat_t A, const double* dinv, const double* r, double* z);
 int fh_tri_ilu_factor(fh_tri_t T, fh_mat_t A);
 int fh_tri_ilu_apply(fh_tri_t T, fh_mat_t A, const double* r, double* z);
+// which path serves the sweeps (fh_mg_sweep_info; host fields only, nothing is launched).  forward / backward[6]: levels, runs of small levels, levels inside
+// runs, longest run, largest level inside a run, register slots per lane of the run kernel; ilu[6]: kernel of the last factorisation, its LDS bytes, the four
+// row limits above.  Any pointer may be null
+void fh_tri_info(const fh_tri_s* T, int* forward, int* backward, int* ilu, double* ilu_shift);

@@ -221,6 +221,29 @@ void fh_tri_destroy(fh_tri_t T) {
   delete T;
 }
 
+void fh_tri_info(const fh_tri_s* T, int* forward, int* backward, int* ilu, double* ilu_shift) {
+  auto direction = [](const std::vector<int>& ptr, const std::vector<int>& seg, int slots, int* out) {
+    if (!out) return;
+    int runs = 0, inside = 0, longest = 0, largest = 0;
+    for (size_t q = 0; q < seg.size(); q += 3) {
+      if (!seg[q + 2]) continue;
+      runs++;
+      inside += seg[q + 1];
+      longest = std::max(longest, seg[q + 1]);
+      for (int l = seg[q]; l < seg[q] + seg[q + 1]; l++) largest = std::max(largest, ptr[l + 1] - ptr[l]);
+    }
+    out[0] = (int)ptr.size() - 1; out[1] = runs; out[2] = inside; out[3] = longest; out[4] = largest; out[5] = slots;
+  };
+  direction(T->fptr, T->fseg, T->run_pf, forward);
+  direction(T->bptr, T->bseg, T->run_pb, backward);
+  if (ilu) {
+    ilu[0] = T->ilu_kernel;
+    ilu[1] = T->ilu_lds;
+    for (int k = 0; k < 4; k++) ilu[2 + k] = T->ilu_rows[k];
+  }
+  if (ilu_shift) *ilu_shift = T->shift;
+}
+
 // ---- symmetric Gauss-Seidel ------------------------------------------------------------------------------------------------
 // forward, zero guess: t_i = r_i - sum_{j < i} a_ij z_j, z_i = dinv_i t_i   (entries right of the diagonal multiply zeros)
 __global__ __launch_bounds__(256) void k_gs_fwd(const int* __restrict__ rows, int nrows, const int* __restrict__ rowptr, const int* __restrict__ col,
@@ -960,6 +983,13 @@ int fh_tri_ilu_factor(fh_tri_t T, fh_mat_t A) {
   const bool planned = ahead && c->ilu_ahead >= 2 && T->plan_state == 1;
   const size_t lds = ahead ? (size_t)16 * maxrow * 28 : (size_t)16 * maxrow * (sizeof(double) + (lcol ? sizeof(int) : 0));
   FH_REQUIRE(lds <= (size_t)lds_max, "ILU(0): a row with %d entries needs %zu bytes of LDS per workgroup, the device grants %d", maxrow, lds, lds_max);
+  // for fh_tri_info: the kernel of this factorisation and the longest row the conditions above grant each kernel on this device
+  T->ilu_kernel = planned ? FH_ILU_KERNEL_PLAN : ahead ? FH_ILU_KERNEL_AHEAD : lcol ? FH_ILU_KERNEL_LDS_COLUMNS : FH_ILU_KERNEL_PLAIN;
+  T->ilu_lds = (int)lds;
+  T->ilu_rows[1] = lds_max / (16 * 28);
+  T->ilu_rows[0] = std::min(254, T->ilu_rows[1]);
+  T->ilu_rows[2] = std::min(800, lds_max / (16 * (int)(sizeof(double) + sizeof(int))));
+  T->ilu_rows[3] = std::min(1200, lds_max / (16 * (int)sizeof(double)));
   if (lds > 64 * 1024)
     FH_CHECK_HIP(hipFuncSetAttribute(planned ? reinterpret_cast<const void*>(&k_ilu_factor_plan) : ahead ? reinterpret_cast<const void*>(&k_ilu_factor_ahead) : lcol ? reinterpret_cast<const void*>(&k_ilu_factor<true>) : reinterpret_cast<const void*>(&k_ilu_factor<false>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

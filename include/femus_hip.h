@@ -825,6 +825,15 @@ int fh_mg_set_level_coords(fh_mg_t mg, int level, int dim, int n, const double* 
 /* what the last fh_mg_setup made of the coarsest level: unknowns in the dense problem (the others are solved by their diagonal), interior
  * blocks of the dissection (0 = one dense inverse), separator size, largest block; any pointer may be NULL */
 int fh_mg_coarse_info(fh_mg_t mg, int* n_dense, int* nd_blocks, int* nd_separator, int* nd_largest_block);
+/* which path serves the natural-order sweeps of a level with FH_SMOOTH_SOR or FH_SMOOTH_ILU0 after fh_mg_setup (host bookkeeping only, nothing is
+ * launched); any pointer may be NULL.
+ * forward[6], backward[6]: levels of the schedule, runs of consecutive small levels (one workgroup each), levels inside runs, longest run, largest
+ *   level inside a run (rows), register slots per lane of the run kernel.
+ * ilu[6]: the kernel of the last ILU(0) factorisation (FH_ILU_KERNEL_*, NONE where the level never factored), the LDS bytes it asked for per
+ *   workgroup, and the longest row this device grants the PLAN, AHEAD, LDS_COLUMNS and PLAIN kernels (valid once a factorisation has run).
+ * ilu_shift: the diagonal shift the last factorisation took (MAT_SHIFT_NONZERO; 0: none). */
+enum { FH_ILU_KERNEL_NONE = 0, FH_ILU_KERNEL_PLAIN = 1, FH_ILU_KERNEL_LDS_COLUMNS = 2, FH_ILU_KERNEL_AHEAD = 3, FH_ILU_KERNEL_PLAN = 4 };
+int fh_mg_sweep_info(fh_mg_t mg, int level, int* forward, int* backward, int* ilu, double* ilu_shift);
 /* diagnostic, host only (no device): the ordering [interior block 0 | ... | interior block k-1 | separator] that the dissection of option "coarse_nd"
  * gives the n unknowns of a CSR pattern with coordinates coords[n * dim], dim 1..3.  order[n]; offsets[0 .. k + 1] with offsets[k] = first separator
  * unknown and offsets[k + 1] = n, room for max(coarse_nd, 1) + 2 ints (k does not exceed max(n, 1) either); *n_offsets = k + 2.  Nothing to cut (coarse_nd < 2, fewer than 64 unknowns):
