@@ -1220,6 +1220,31 @@ class GenericAssembler:
         _chk(self.L.fh_generic_assembler_system_chunks(self.h, int(m if m is not None else getattr(self, "_system_m", 1)), gc, ln))
         return {s: (gc[k], ln[k]) for k, s in enumerate(self.shapes[:3])}
 
+    def assemble_system_transient(self, K, res, sol, sol_old, form, time, dt, theta=1.0, mass=None):
+        """K and res are overwritten with the Jacobian and residual of one Newton iteration of one theta-step of the system
+        sum_l M_kl d_t u_l - sum_l div(A_kl grad u_l) + c_k = f_k, scaled by dt (fh_generic_assembler_assemble_system_transient): sol the iterate, sol_old the
+        state at time - dt (both form.m * ndof entries), time the time at the END of the step; form a TransientSystemForm (or a SystemForm: no t in it);
+        mass: the m x m matrix M (None: the identity); an equation whose row of M is zero is algebraic and taken at the new time whatever theta"""
+        m = int(form.m) if form is not None else 0
+        M4 = None
+        if mass is not None:
+            M = np.asarray(mass, dtype=float)
+            if form is not None and M.shape != (m, m):
+                raise ValueError("mass has shape %s, the form has %d variables" % (M.shape, m))
+            M4 = np.zeros((4, 4))
+            M4[:M.shape[0], :M.shape[1]] = M
+        _chk(self.L.fh_generic_assembler_assemble_system_transient(self.h, sol.h if sol is not None else None, sol_old.h if sol_old is not None else None,
+                                                                   form.pointer() if form is not None else None, _p(M4) if M4 is not None else None, float(time),
+                                                                   float(dt), float(theta), K.h if K is not None else None, res.h))
+        self._system_transient_m = m
+
+    def system_transient_chunks(self, m=None):
+        """{shape: (Gauss points per LDS chunk, lanes per element)} of assemble_system_transient's element pass with m variables (None: as many as the last
+        such call of this object had); 0 before the first such call"""
+        gc, ln = (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+        _chk(self.L.fh_generic_assembler_system_transient_chunks(self.h, int(m if m is not None else getattr(self, "_system_transient_m", 1)), gc, ln))
+        return {s: (gc[k], ln[k]) for k, s in enumerate(self.shapes[:3])}
+
     def info(self):
         """elements per 256-thread workgroup of the element pass by shape, bytes held on the device, bytes one assembly cannot avoid moving, device
         allocations made so far"""
@@ -1633,11 +1658,12 @@ class SystemForm:
         return ",".join(["x", "y", "z"] + ["u%d" % k for k in range(m)] + ["u%d%s" % (k, d) for k in range(m) for d in "xyz"])
 
     def __init__(self, m, f=None, A=None, A_u=None, c=None, c_u=None, c_g=None):
-        m = int(m)
+        m, who = int(m), type(self).__name__
         if not 1 <= m <= self.MAXM:
-            raise ValueError("SystemForm: %d variables, 1 .. %d are served" % (m, self.MAXM))
+            raise ValueError("%s: %d variables, 1 .. %d are served" % (who, m, self.MAXM))
         self.m, self._owned, self.exprs = m, [], {}
         names = self.variables(m)
+        served = names.count(",") + 1
 
         def walk(name, value, shape, index=()):
             """every (index, entry) of one argument, its list shapes checked"""
@@ -1648,10 +1674,10 @@ class SystemForm:
                 return
             label = name + "".join("[%d]" % i for i in index)
             if isinstance(value, (str, Expr)) or not hasattr(value, "__len__"):
-                raise ValueError("SystemForm: %s must be a list of %d entries" % (label, shape[0]))
+                raise ValueError("%s: %s must be a list of %d entries" % (who, label, shape[0]))
             directions = name == "c_g" and len(shape) == 1            # c_g's innermost list: one entry per space dimension, at most 3
             if len(value) > shape[0] if directions else len(value) != shape[0]:
-                raise ValueError("SystemForm: %s has %d entries, %s%d are expected" % (label, len(value), "at most " if directions else "", shape[0]))
+                raise ValueError("%s: %s has %d entries, %s%d are expected" % (who, label, len(value), "at most " if directions else "", shape[0]))
             for i, v in enumerate(value):
                 yield from walk(name, v, shape[1:], index + (i,))
 
@@ -1662,8 +1688,8 @@ class SystemForm:
                     if not isinstance(e, Expr):
                         e = Expr(str(e), names)
                         self._owned.append(e)
-                    if e.n_variables() > 3 + 4 * m:
-                        raise ValueError("SystemForm: the program %s has %d variables, at most %d (%s) are served" % (label, e.n_variables(), 3 + 4 * m, names))
+                    if e.n_variables() > served:
+                        raise ValueError("%s: the program %s has %d variables, at most %d (%s) are served" % (who, label, e.n_variables(), served, names))
                     self.exprs[(name, index)] = e
         except BaseException:
             self.destroy()
@@ -1687,6 +1713,15 @@ class SystemForm:
             e.destroy()
         self._owned, self.exprs = [], {}
         self._refresh()
+
+
+class TransientSystemForm(SystemForm):
+    """the same programs for GenericAssembler.assemble_system_transient (sum_l M_kl d_t u_l - sum_l div(A_kl grad u_l) + c_k = f_k): texts over one variable
+    more, the last the time"""
+
+    @staticmethod
+    def variables(m):
+        return SystemForm.variables(m) + ",t"
 
 
 def system_elem_dofs(mesh, fes):

@@ -1,5 +1,6 @@
-// What the four element bodies on the resident plan of the generic assembly share on the device: gen_element_pass (fh_generic.hip), form_element_pass
-// (fh_quasilinear.hip), transient_element_pass (fh_transient.hip) and system_element_pass (fh_system.hip).  Every body takes the Gauss points of an element
+// What the five element bodies on the resident plan of the generic assembly share on the device: gen_element_pass (fh_generic.hip), form_element_pass
+// (fh_quasilinear.hip), transient_element_pass (fh_transient.hip), system_element_pass (fh_system.hip) and system_transient_element_pass
+// (fh_system_transient.hip, which calls the prologue, (A) and (B)).  Every body takes the Gauss points of an element
 // through LDS a chunk at a time, L lanes per element, with a workgroup barrier between the phases; the phases they have in common are here, inlined into
 // each, so that a change to one of them is made once:
 //   eb_prologue          the kernel's first lines: sub-group, lane, slot, active, the tables (staged in LDS under TL) and the sub-group's LDS

@@ -44,8 +44,9 @@ struct fh_generic_assembler_s {
   int shapes[3] = {-1, -1, -1};  // shape codes in the order of their first elements
   int nc[3] = {0, 0, 0}, ng[3] = {0, 0, 0}, nslot[3] = {0, 0, 0};
   // one plan per element body: the Poisson body's at create, the others at the first call that needs them -- the quasilinear (fh_quasilinear.hip) and the
-  // transient body (fh_transient.hip) on the Poisson body's lanes, the system body (fh_system.hip) per number of variables m = 1 .. 4 on lanes of its own
-  GenBodyPlan poisson, form, transient, sys[5];
+  // transient body (fh_transient.hip) on the Poisson body's lanes, the system body (fh_system.hip) and its theta-step (fh_system_transient.hip) per number of
+  // variables m = 1 .. 4 on lanes of their own
+  GenBodyPlan poisson, form, transient, sys[5], systr[5];
   GenRowShapes rows;
   int* d_ed[3] = {nullptr, nullptr, nullptr};
   double *d_w[3] = {nullptr, nullptr, nullptr}, *d_phi[3] = {nullptr, nullptr, nullptr}, *d_dphi[3] = {nullptr, nullptr, nullptr};
@@ -66,8 +67,8 @@ struct fh_generic_assembler_s {
   std::vector<int> code;
   std::vector<double> consts;
   bool have_prog = false;
-  // the system body's block row pass and work buffers, per m: lanes per row and LDS, Kb / Fb of m^2 / m times the scalar size (m = 1: the scalar ones), made
-  // with sys[m]
+  // the system bodies' block row pass and work buffers, per m: lanes per row and LDS, Kb / Fb of m^2 / m times the scalar size (m = 1: the scalar ones), made
+  // with sys[m] or systr[m], whichever comes first (sy_work_buffers, fh_system.h)
   int sys_lpr[5] = {0, 0, 0, 0, 0};
   size_t sys_row_lds[5] = {0, 0, 0, 0, 0};
   double *d_sysK[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *d_sysF[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};

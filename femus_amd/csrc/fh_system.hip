@@ -30,6 +30,7 @@
 //                 gp_upload_program compares, so no other path's upload can leave a stale one behind
 #include "fh_elembody.h"
 #include "fh_expr_device.h"
+#include "fh_system.h"
 #include <algorithm>
 #include <cstdio>
 
@@ -279,15 +280,10 @@ static void sy_launch(fh_generic_assembler_t as, int k, const SysCall& c) {
   });
 }
 
-// first assemble_system with this m: lanes (the scalar body's times 1 / 2 / 4, at most 64), Gauss chunk, table staging and LDS per shape, the lanes of the row
-// pass -- every refusal before the work buffers are allocated; nothing is kept unless all of it succeeds
-static int sy_plan(const char* who, fh_generic_assembler_t as, int m) {
-  int lanes[3] = {64, 64, 64};
-  for (int k = 0; k < as->ns; k++) lanes[k] = std::min(64, as->poisson.lanes[k] * (m == 1 ? 1 : m == 2 ? 2 : 4));
-  char body[64];
-  snprintf(body, sizeof body, " with the element body of %d variables", m);
-  GenBodyPlan plan;
-  FH_TRY(gp_plan_body(who, as, lanes, [m](int nc, int gc) { return sy_elem_doubles(m, nc, gc); }, false, true, "a block", body, plan));
+// The row pass's lanes and the work buffers of m variables, for assemble_system and assemble_system_transient alike (fh_system.h): made once per m, by
+// whichever of the two comes first
+int sy_work_buffers(const char* who, fh_generic_assembler_t as, int m) {
+  if (as->sys_lpr[m] && as->d_sysK[m] && as->d_sysF[m]) return 0;
   int lpr = as->lpr;
   while (lpr < 64 && (size_t)(GP_THREADS / lpr) * m * as->maxrow * sizeof(double) > GP_LDS_BUDGET) lpr *= 2;
   FH_REQUIRE((size_t)(GP_THREADS / lpr) * m * as->maxrow * sizeof(double) <= GP_LDS_BUDGET, "%s: %d rows of %d entries are longer than the row pass holds", who, m,
@@ -308,9 +304,22 @@ static int sy_plan(const char* who, fh_generic_assembler_t as, int m) {
   } else {
     as->d_sysK[1] = as->d_Kb, as->d_sysF[1] = as->d_Fb;
   }
-  as->sys[m] = plan;
   as->sys_lpr[m] = lpr;
   as->sys_row_lds[m] = (size_t)(GP_THREADS / lpr) * m * as->maxrow * sizeof(double);
+  return 0;
+}
+
+// first assemble_system with this m: lanes (the scalar body's times 1 / 2 / 4, at most 64), Gauss chunk, table staging and LDS per shape, then the row pass and
+// the work buffers -- every refusal before the buffers are allocated; the plan is kept only when all of it succeeds
+static int sy_plan(const char* who, fh_generic_assembler_t as, int m) {
+  int lanes[3] = {64, 64, 64};
+  for (int k = 0; k < as->ns; k++) lanes[k] = std::min(64, as->poisson.lanes[k] * (m == 1 ? 1 : m == 2 ? 2 : 4));
+  char body[64];
+  snprintf(body, sizeof body, " with the element body of %d variables", m);
+  GenBodyPlan plan;
+  FH_TRY(gp_plan_body(who, as, lanes, [m](int nc, int gc) { return sy_elem_doubles(m, nc, gc); }, false, true, "a block", body, plan));
+  FH_TRY(sy_work_buffers(who, as, m));
+  as->sys[m] = plan;
   return 0;
 }
 

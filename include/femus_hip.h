@@ -674,6 +674,33 @@ int fh_generic_assembler_assemble_system(fh_generic_assembler_t as, fh_vec_t sol
 /* Gauss points per chunk and lanes per element of assemble_system's element pass with m variables, per shape (0 beyond the last shape and before the first
  * assemble_system with that m) */
 int fh_generic_assembler_system_chunks(fh_generic_assembler_t as, int m, int gauss_chunk[3], int lanes[3]);
+/* The TIME-DEPENDENT coupled system on the same object (fh_system_transient.hip): equation k of m is
+ *   sum_l M_kl d_t u_l - sum_l div(A_kl grad u_l) + c_k = f_k   with M a constant m x m matrix, A_kl(x, U, t), c_k(x, U, grad U, t), f_k(x, U, grad U, t),
+ * a TransientNonlinearImplicitSystem with several variables stacked in one matrix (src/08_equations/01_time_dependent/TransientSystem.cpp:62-113; reaction-
+ * diffusion systems, the time-dependent biharmonic equation as (u, v = -lap u), Cahn-Hilliard-type splits).  With S and J the residual and the Jacobian of
+ * assemble_system, one Newton iteration of one theta-step, scaled by dt as assemble_transient scales it, forms
+ *   RES_(k,i)      = - sum_g w sum_l M_kl (u_l - uo_l) phi_i  +  dt th_k S_(k,i)(U, time)  +  dt (1 - th_k) S_(k,i)(Uo, time - dt)
+ *   KK_(k,i),(l,j) = sum_g w M_kl phi_i phi_j  +  dt th_k J_(k,i),(l,j)(U, time)
+ * th_k = theta for an equation whose row of M has a non-zero entry; th_k = 1 for an ALGEBRAIC equation, whose row k of M is entirely zero: a constraint (v = -lap u)
+ * holds at the new time, a theta-mix of it at two times lets it drift.  The Jacobian is the exact one, with the factor th_k.  The programs are those of
+ * fh_system_form_t over one variable more, the time as the last: x, y, z, u0 .., u0x, u0y, u0z, u1x, .., t (variable 3 + 4 m).  f_k, c_k and A_kl are run at
+ * (x, U, grad U, time) and at (x, Uo, grad Uo, time - dt), the derivative programs at the new state only.  `time` is the time at the END of the step.
+ * mass: [4][4] row-major, the entries k, l < m are read; NULL: the identity.  time, dt, theta, mass and the th_k are kernel arguments, never part of the
+ * program buffer: a step with a new time uploads nothing.  Where every th_k is 1 nothing is evaluated at the old state (a program that is NaN there does not
+ * matter); where every th_k is 0 nothing is evaluated at the new state, and KK = kron(M, mass matrix) in the block layout.
+ * The contract of assemble_system and assemble_transient together: only enqueues on the context's stream, OVERWRITES KK and RES, sol NULL = 0, every sum in one
+ * fixed order, no floating-point atomics, a repeated call gives the same bits; KK is fh_mat_block_system(S, m), unknown (k, i) = k ndof + i; sol_old holds at
+ * least m ndof entries and, where sol is given, exactly as many as sol.  The work buffers of m^2 and m times the scalar size are the ones assemble_system uses
+ * for that m, made by whichever of the two calls comes first; the first call with a given m also chooses this body's launch geometry.  Refused before anything
+ * is enqueued, the object still usable: everything assemble_system refuses; a NULL sol_old or one of another size; dt <= 0; theta outside [0, 1]; a time, dt,
+ * theta or mass entry that is not finite; a program over more than 4 + 4 m variables; and -- at the first call with that m -- a shape that does not fit the LDS
+ * of a workgroup.  assemble_system keeps refusing more than 3 + 4 m variables. */
+int fh_generic_assembler_assemble_system_transient(fh_generic_assembler_t as, fh_vec_t sol, fh_vec_t sol_old, const fh_system_form_t* form,
+                                                   const double* mass /* [4][4] row-major, entries k, l < m read; NULL: the identity */,
+                                                   double time, double dt, double theta, fh_mat_t KK, fh_vec_t RES);
+/* Gauss points per chunk and lanes per element of assemble_system_transient's element pass with m variables, per shape (0 beyond the last shape and before the
+ * first assemble_system_transient with that m) */
+int fh_generic_assembler_system_transient_chunks(fh_generic_assembler_t as, int m, int gauss_chunk[3], int lanes[3]);
 /* Open-boundary pressure term of the steady Navier-Stokes residual (src/08_equations/assemble/03_navier_stokes.hpp:185-290): on every listed boundary
  * face  aResV[k][node_i] += phi_i * tau * normal[k] * weight  for the dim velocity components (Q2 face nodes), tau = the prescribed pressure -- one
  * number per face (tau) or expression face_expr[f] of the nexpr expressions evaluated at the face Gauss point, as the bdc callback is (:280) -- and
