@@ -498,6 +498,21 @@ class Mat:
         h = ctypes.c_void_p(self.h.value if isinstance(self.h, ctypes.c_void_p) else self.h)
         _chk(self.L.fh_mat_abc(A.h, B.h, C.h, ctypes.byref(h)))
 
+    def product_info(self):
+        """which path serves the sparse product this matrix came from (fh_mat_product_info; host bookkeeping, nothing is launched): a list with one
+        dict per product -- two for Mat.ptap / Mat.abc (A P, then R (A P)), one for matmul -- of "kernel" ("searching", "lists", "slots"), "gl_log2"
+        (lists only, else None), "products" (elementary products in the map), "max_crow" and "max_arow" (what the map was sized for; zero where the
+        kernel has no such limit), "pattern" ("device", "host") and "lanes_over_b" (device builder only, else None)"""
+        n, pat, mp = ctypes.c_int(), (ctypes.c_int * 2)(), (ctypes.c_longlong * 10)()
+        _chk(self.L.fh_mat_product_info(self.h, ctypes.byref(n), pat, mp))
+        out = []
+        for p in range(n.value):
+            kernel = ("searching", "lists", "slots")[mp[5 * p]]
+            out.append({"kernel": kernel, "gl_log2": int(mp[5 * p + 1]) if kernel == "lists" else None, "products": int(mp[5 * p + 2]),
+                        "max_crow": int(mp[5 * p + 3]), "max_arow": int(mp[5 * p + 4]), "pattern": "host" if pat[p] == 1 else "device",
+                        "lanes_over_b": None if pat[p] == 1 else pat[p] - 2})
+        return out
+
     def split_info(self, n_own_cols):
         """(interior, interface) row-block counts of the overlap split for an operator over [owned | ghost] columns"""
         a, b = ctypes.c_int(), ctypes.c_int()

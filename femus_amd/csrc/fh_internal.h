@@ -177,6 +177,8 @@ struct fh_mat_s {
   // attached reusable product plan (fh_mat_ptap)
   void* plan = nullptr;
   void (*plan_destroy)(void*) = nullptr;
+  int product_pattern = 0;            // result of a sparse product (fh_spgemm.hip): its pattern came from 1 the host builder, 2 the device builder with one lane per
+                                      // B row, 3 the device builder with the lanes over the B row; 0: not a product (fh_mat_product_info)
 };
 
 // every writer of a matrix's values ends here (the Dirichlet-row replacement, fh_mat_zero_rows*, calls fh_mat_rows_replaced instead): one place, so that a new

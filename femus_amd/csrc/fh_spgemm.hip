@@ -25,6 +25,7 @@ struct SlotMap {
   unsigned short* slot = nullptr;   // alternative for long B rows: per elementary product, in (row, ka, kb) order, its position in the C row
   long long nprod = 0;
   int max_crow = 0, max_arow = 0;
+  int gl_log2 = 0;                  // lists: lanes per A entry of the two building passes (fh_mat_product_info)
   void release() {
     for (void** q : {(void**)&pa, (void**)&pb, (void**)&rowbase, (void**)&segptr, (void**)&slot})
       if (*q) {
@@ -288,6 +289,7 @@ static int build_slot_map(fh_mat_t A, fh_mat_t B, fh_mat_t C, SlotMap& M) {
   // lanes per A entry: the power of two next to the mean length of a B row, 8 to 64
   int gl_log2 = 3;
   while (gl_log2 < 6 && (double)(1 << gl_log2) < (double)B->nnz / std::max(B->m, 1)) gl_log2++;
+  M.gl_log2 = gl_log2;
   hipLaunchKernelGGL(k_spgemm_segcount, dim3(fh_div_up(m, 4)), dim3(256), lds, c->stream, A->d_rowptr, A->d_col, B->d_rowptr, B->d_col, C->d_rowptr,
                      C->d_col, M.rowbase, M.segptr, m, max_crow, gl_log2);
   std::vector<long long> rb((size_t)m + 1);
@@ -558,6 +560,7 @@ static int spgemm_symbolic_device(fh_mat_t A, fh_mat_t B, fh_mat_t* Cout) {
   hipFree(d_err);
   FH_TRY(fh_spmv_build_rowblocks(C));
   FH_TRACE("spgemm symbolic: row blocks");
+  C->product_pattern = lanes_over_b ? 3 : 2;
   *Cout = C;
   return 0;
 }
@@ -571,7 +574,9 @@ static int spgemm_pattern(fh_mat_t A, fh_mat_t B, fh_mat_t* Cout) {
   }
   std::vector<int> rp, col;
   spgemm_symbolic(A->m, B->n, A->h_rowptr, fh_hcol(A), B->h_rowptr, fh_hcol(B), rp, col);
-  return fh_mat_create_csr(A->ctx, A->m, B->n, rp.data(), col.data(), nullptr, Cout);
+  FH_TRY(fh_mat_create_csr(A->ctx, A->m, B->n, rp.data(), col.data(), nullptr, Cout));
+  (*Cout)->product_pattern = 1;
+  return 0;
 }
 
 int fh_mat_refresh_transpose(fh_mat_t A);
@@ -645,4 +650,40 @@ extern "C" int fh_mat_matmul(fh_mat_t A, fh_mat_t B, fh_mat_t* Cout) {
   *Cout = C;
   return 0;
   FH_GUARD_END("fh_mat_matmul")
+}
+
+// which path serves a product (host fields only, nothing is launched)
+extern "C" int fh_mat_product_info(fh_mat_t C, int* products, int* pattern, long long* map) {
+  FH_GUARD_BEGIN
+  FH_REQUIRE(C && products && pattern && map, "fh_mat_product_info: null argument");
+  FH_REQUIRE(C->product_pattern != 0, "fh_mat_product_info: the matrix is not the result of fh_mat_ptap, fh_mat_abc or fh_mat_matmul");
+  const PtapPlan* plan = (const PtapPlan*)C->plan;
+  for (int k = 0; k < 10; k++) map[k] = 0;
+  pattern[0] = pattern[1] = 0;
+  if (!plan) {             // fh_mat_matmul: one product, always the searching kernel
+    *products = 1;
+    pattern[0] = C->product_pattern;
+    return 0;
+  }
+  *products = 2;
+  pattern[0] = plan->AP->product_pattern;
+  pattern[1] = C->product_pattern;
+  const SlotMap* maps[2] = {&plan->map_ap, &plan->map_c};
+  for (int p = 0; p < 2; p++) {
+    const SlotMap& M = *maps[p];
+    long long* o = map + 5 * p;
+    if (M.slot) {
+      o[0] = 2;
+      o[2] = M.nprod;
+      o[3] = M.max_crow;
+    } else if (M.pa) {
+      o[0] = 1;
+      o[1] = M.gl_log2;
+      o[2] = M.nprod;
+      o[3] = M.max_crow;
+      o[4] = M.max_arow;
+    }
+  }
+  return 0;
+  FH_GUARD_END("fh_mat_product_info")
 }

@@ -187,6 +187,15 @@ int fh_mat_matmul(fh_mat_t A, fh_mat_t B, fh_mat_t* C);
 /* matrix_ABC(A, B, C, reuse) :186 (PetscMatrix.cpp:833-856): D = A B C.  *D == NULL: symbolic + numeric, the plan stays attached to D;
  * else numeric only (operands of the same patterns) */
 int fh_mat_abc(fh_mat_t A, fh_mat_t B, fh_mat_t C, fh_mat_t* D);
+/* Which path serves a sparse product, from the library's host bookkeeping (nothing is launched).  C: a result of fh_mat_ptap / fh_mat_abc (*products = 2:
+ * the inner product A P first, then R (A P)) or of fh_mat_matmul (*products = 1); any other matrix is refused.
+ * pattern[2], per product: 1 the host builder made the pattern, 2 the device builder with one lane per B row, 3 the device builder with the lanes over the B
+ * row (mean B row >= 24).  The device builder serves rows of at most 1024 distinct columns; one longer row sends the whole product to the host builder.
+ * map[2][5], per product: the numeric kernel (0 searching, 1 product lists, 2 slots), the lanes per A entry of the list builder as a power of two (3, 4, 5;
+ * lists only), the elementary products in the map, the longest C row and the longest A row (lists only) the map was sized for; zeros for the searching
+ * kernel.  Lists serve a mean B row below 32 with C rows of at most 4000 and A rows of at most 2000 entries, slots a mean B row from 32 with C rows of at
+ * most 2000; the searching kernel serves everything else, option "spgemm_slot_map" 0, and fh_mat_matmul. */
+int fh_mat_product_info(fh_mat_t C, int* products, int* pattern /* [2] */, long long* map /* [10] */);
 int fh_mat_norm(fh_mat_t A, int kind, double* out);              /* kind 1: l1_norm :211, 0: linfty_norm :214 */
 
 /* SpMV family (NumericVector::matrix_mult :283, add_vector(v,A) :281, resid :282, matrix_mult_transpose :284;
