@@ -472,9 +472,8 @@ class Mat:
         rows, newcol = _i32(rows), _i32(newcol)
         assert newcol.size == self.n_
         if check:
-            mx = ctypes.c_double()
-            _chk(self.L.fh_mat_restrict_check(self.h, rows.size, _p(rows), _p(newcol), ctypes.byref(mx)))
-            assert mx.value == 0.0, "an owned row reads a node outside the halo (|value| %g)" % mx.value
+            mx = self.restrict_check(rows, newcol)
+            assert mx == 0.0, "an owned row reads a node outside the halo (|value| %g)" % mx
         h, mh = ctypes.c_void_p(), ctypes.c_void_p()
         _chk(self.L.fh_mat_restrict(self.h, rows.size, _p(rows), _p(newcol), int(ncols_new), ctypes.byref(h), ctypes.byref(mh)))
         return Mat(self.ctx, h), Index.from_handle(self.ctx, mh, None)
@@ -512,6 +511,22 @@ class Mat:
                         "max_crow": int(mp[5 * p + 3]), "max_arow": int(mp[5 * p + 4]), "pattern": "host" if pat[p] == 1 else "device",
                         "lanes_over_b": None if pat[p] == 1 else pat[p] - 2})
         return out
+
+    def built_on(self):
+        """who made the pattern (fh_mat_built_on; host bookkeeping, nothing is launched): "csr" the caller's arrays, "device" a device builder (pattern from
+        elements, transpose, block matrices), "host_fallback" the host loop such a builder hands the whole matrix to, at its cap of 1024 or -- the transpose --
+        for a source without non-zeros"""
+        how = ctypes.c_int()
+        _chk(self.L.fh_mat_built_on(self.h, ctypes.byref(how)))
+        return ("csr", "device", "host_fallback")[how.value]
+
+    def restrict_check(self, rows, newcol):
+        """largest |value| among the entries of `rows` that restrict(rows, newcol, ...) drops (fh_mat_restrict_check, a device reduction)"""
+        rows, newcol = _i32(rows), _i32(newcol)
+        assert newcol.size == self.n_
+        mx = ctypes.c_double()
+        _chk(self.L.fh_mat_restrict_check(self.h, rows.size, _p(rows), _p(newcol), ctypes.byref(mx)))
+        return mx.value
 
     def split_info(self, n_own_cols):
         """(interior, interface) row-block counts of the overlap split for an operator over [owned | ghost] columns"""

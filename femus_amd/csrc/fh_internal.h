@@ -179,6 +179,8 @@ struct fh_mat_s {
   void (*plan_destroy)(void*) = nullptr;
   int product_pattern = 0;            // result of a sparse product (fh_spgemm.hip): its pattern came from 1 the host builder, 2 the device builder with one lane per
                                       // B row, 3 the device builder with the lanes over the B row; 0: not a product (fh_mat_product_info)
+  int built_on = 0;                   // who made the pattern: 0 the caller's arrays (fh_mat_create_csr), 1 a device builder (pattern from elements, transpose, block
+                                      // matrices), 2 the host loop a device builder hands the whole matrix to, at its cap or with nothing to launch over (fh_mat_built_on)
 };
 
 // every writer of a matrix's values ends here (the Dirichlet-row replacement, fh_mat_zero_rows*, calls fh_mat_rows_replaced instead): one place, so that a new

@@ -96,6 +96,7 @@ int fh_mat_alloc_device_pattern(fh_ctx_t c, int m, int n, std::vector<int>&& rp,
   A->n = n;
   A->h_rowptr = std::move(rp);
   A->nnz = A->h_rowptr[m];
+  A->built_on = 1;
   int maxrow = 0;
   for (int r = 0; r < m; r++) maxrow = std::max(maxrow, A->h_rowptr[r + 1] - A->h_rowptr[r]);
   A->max_row = maxrow;
@@ -262,7 +263,9 @@ int mat_create_from_elements_impl(fh_ctx_t c, int nel, int nloc, const int* elem
     FH_TRY(fh_pattern_from_elements(nel, nloc, elem_dof, n, hrp.data(), nullptr));
     hcol.resize((size_t)hrp[n]);
     FH_TRY(fh_pattern_from_elements(nel, nloc, elem_dof, n, hrp.data(), hcol.data()));
-    return fh_mat_create_csr(c, m, n, hrp.data(), hcol.data(), nullptr, out);
+    FH_TRY(fh_mat_create_csr(c, m, n, hrp.data(), hcol.data(), nullptr, out));
+    (*out)->built_on = 2;
+    return 0;
   }
   int64_t tot = 0;
   for (int r = 0; r < m; r++) {
@@ -352,6 +355,12 @@ extern "C" int fh_mat_size(fh_mat_t A, int* m, int* n, int* nnz) {
   if (m) *m = A->m;
   if (n) *n = A->n;
   if (nnz) *nnz = A->nnz;
+  return 0;
+}
+
+extern "C" int fh_mat_built_on(fh_mat_t A, int* how) {
+  FH_REQUIRE(A && how, "fh_mat_built_on: null argument");
+  *how = A->built_on;
   return 0;
 }
 
@@ -702,6 +711,7 @@ __global__ __launch_bounds__(256) void k_dropped_max(const int* __restrict__ row
 extern "C" int fh_mat_restrict_check(fh_mat_t src, int nrows, const int* rows, const int* newcol, double* max_dropped) {
   FH_REQUIRE(src && newcol && max_dropped && nrows >= 0 && (nrows == 0 || rows), "fh_mat_restrict_check: bad arguments");
   *max_dropped = 0.0;
+  for (int i = 0; i < nrows; i++) FH_REQUIRE(rows[i] >= 0 && rows[i] < src->m, "fh_mat_restrict_check: row %d out of range", rows[i]);
   if (nrows == 0) return 0;
   fh_ctx_t c = src->ctx;
   int *d_rows = nullptr, *d_new = nullptr;
@@ -778,20 +788,26 @@ __global__ __launch_bounds__(256) void k_get_diag(const int* __restrict__ pos, c
   d[r] = v;
 }
 
-int fh_dev_get_diag(fh_mat_t A, double* d, int invert) {
-  if (A->m == 0) return 0;
+// the first `count` <= m rows
+static int dev_get_diag(fh_mat_t A, double* d, int count, int invert) {
+  if (count == 0) return 0;
   if (!A->d_diagpos) {
     FH_CHECK_HIP(hipMalloc(&A->d_diagpos, (size_t)A->m * sizeof(int)));
     hipLaunchKernelGGL(k_diag_pos, dim3(fh_div_up(A->m, 256)), dim3(256), 0, A->ctx->stream, A->d_rowptr, A->d_col, A->d_diagpos, A->m);
   }
-  hipLaunchKernelGGL(k_get_diag, dim3(fh_div_up(A->m, 256)), dim3(256), 0, A->ctx->stream, A->d_diagpos, A->d_val, d, A->m, invert);
+  hipLaunchKernelGGL(k_get_diag, dim3(fh_div_up(count, 256)), dim3(256), 0, A->ctx->stream, A->d_diagpos, A->d_val, d, count, invert);
   FH_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
+int fh_dev_get_diag(fh_mat_t A, double* d, int invert) { return dev_get_diag(A, d, A->m, invert); }
+
+// the min(m, n) entries a rectangular matrix has a diagonal for: a tall matrix (a prolongator) writes nothing for its rows from n on
 extern "C" int fh_mat_get_diagonal(fh_mat_t A, fh_vec_t d) {
-  FH_REQUIRE(d->n_local >= std::min(A->m, A->n), "fh_mat_get_diagonal: vector too short");
-  return fh_dev_get_diag(A, d->d, 0);
+  FH_REQUIRE(A && d, "fh_mat_get_diagonal: null argument");
+  const int count = std::min(A->m, A->n);
+  FH_REQUIRE(d->n_local >= count, "fh_mat_get_diagonal: vector too short");
+  return dev_get_diag(A, d->d, count, 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -815,6 +831,7 @@ static int build_transpose_host(fh_mat_t A, fh_mat_t* out, int** d_perm_out) {
     }
   fh_mat_t At = nullptr;
   FH_TRY(fh_mat_create_csr(A->ctx, n, m, trp.data(), tcol.data(), nullptr, &At));
+  At->built_on = 2;
   int* d_perm = nullptr;
   FH_CHECK_HIP(hipMalloc(&d_perm, std::max(nnz, 1) * sizeof(int)));
   if (nnz) FH_CHECK_HIP(hipMemcpy(d_perm, perm.data(), nnz * sizeof(int), hipMemcpyHostToDevice));
@@ -907,6 +924,7 @@ static int build_transpose(fh_mat_t A, fh_mat_t* out, int** d_perm_out) {
   At->n = m;
   At->nnz = nnz;
   At->max_row = maxrow;
+  At->built_on = 1;
   At->h_rowptr = trp;
   int* d_perm = nullptr;
   FH_CHECK_HIP(hipMalloc(&At->d_rowptr, ((size_t)n + 1) * sizeof(int)));

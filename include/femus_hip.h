@@ -196,6 +196,11 @@ int fh_mat_abc(fh_mat_t A, fh_mat_t B, fh_mat_t C, fh_mat_t* D);
  * kernel.  Lists serve a mean B row below 32 with C rows of at most 4000 and A rows of at most 2000 entries, slots a mean B row from 32 with C rows of at
  * most 2000; the searching kernel serves everything else, option "spgemm_slot_map" 0, and fh_mat_matmul. */
 int fh_mat_product_info(fh_mat_t C, int* products, int* pattern /* [2] */, long long* map /* [10] */);
+/* Who made the pattern of a matrix, from the library's host bookkeeping (nothing is launched): *how = 0 the caller's arrays (fh_mat_create_csr), 1 a device
+ * builder (fh_mat_create_from_elements / _from_mesh, fh_mat_transpose and the cached transpose, fh_mat_block_system / _diagonal), 2 the host loop such a builder
+ * hands the WHOLE matrix to: a row of more than 1024 candidate columns (pattern from elements), a column of more than 1024 entries (transpose), or a source
+ * without non-zeros (transpose: nothing to launch over). */
+int fh_mat_built_on(fh_mat_t A, int* how);
 int fh_mat_norm(fh_mat_t A, int kind, double* out);              /* kind 1: l1_norm :211, 0: linfty_norm :214 */
 
 /* SpMV family (NumericVector::matrix_mult :283, add_vector(v,A) :281, resid :282, matrix_mult_transpose :284;
