@@ -396,12 +396,34 @@ class Mat:
         _chk(self.L.fh_mat_transpose(self.h, ctypes.byref(h)))
         return Mat(self.ctx, h)
 
-    def block_system(self, m):
+    def block_system(self, m, sizes=None):
         """the pattern of kron(ones(m, m), self) with zero values (fh_mat_block_system): the matrix of m stacked variables of one family on the pattern self,
-        unknown (k, i) = k rows + i, made on the device"""
+        unknown (k, i) = k rows + i, made on the device.  sizes: m numbers n_k <= rows (fh_mat_block_system_families) -- variables of different families on
+        the pattern of the highest: block (k, l) is the pattern of self[:n_k, :n_l], unknown (k, i) = n_0 + .. + n_{k-1} + i"""
         h = ctypes.c_void_p()
-        _chk(self.L.fh_mat_block_system(self.h, int(m), ctypes.byref(h)))
+        if sizes is None:
+            _chk(self.L.fh_mat_block_system(self.h, int(m), ctypes.byref(h)))
+        else:
+            if len(sizes) != int(m):
+                raise ValueError("sizes has %d entries, %d are expected" % (len(sizes), int(m)))
+            n = (ctypes.c_int * max(len(sizes), 1))(*[int(s) for s in sizes])
+            _chk(self.L.fh_mat_block_system_families(self.h, int(m), n, ctypes.byref(h)))
         return Mat(self.ctx, h)
+
+    @staticmethod
+    def block_diagonal_of(mats):
+        """blkdiag(mats[0], mats[1], ...) of at most four rectangular matrices of any sizes on one context, with their value bits
+        (fh_mat_block_diagonal_of): the transfer of stacked variables of different families, made on the device"""
+        mats = list(mats)
+        if not mats:
+            raise ValueError("block_diagonal_of: no matrices")
+        hs = (ctypes.c_void_p * len(mats))(*[A.h if A is not None else None for A in mats])
+        h = ctypes.c_void_p()
+        first = next((A for A in mats if A is not None), None)
+        if first is None:
+            raise ValueError("block_diagonal_of: no matrices")
+        _chk(first.L.fh_mat_block_diagonal_of(len(mats), hs, ctypes.byref(h)))
+        return Mat(first.ctx, h)
 
     def block_diagonal(self, m):
         """kron(I_m, self) with self's values (fh_mat_block_diagonal): the transfer of m stacked variables of one family, made on the device"""

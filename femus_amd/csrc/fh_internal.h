@@ -196,6 +196,9 @@ fh_mat_t fh_mat_alive(uint64_t uid);
 // host copy of the column indices: matrices whose pattern was built on the device (fh_mat_create_from_elements) fetch it at the first host use
 int fh_mat_fetch_host_cols(fh_mat_t A);
 int fh_mat_alloc_device_pattern(fh_ctx_t c, int m, int n, std::vector<int>&& rp, fh_mat_t* out);   // columns left to the caller's kernels
+// out[l rows + i] = how many columns of row i of S are < n[l], l < cnt <= 4: counted by a kernel from the resident CSR arrays (the columns ascend: a binary
+// search per row), the counts alone come to the host
+int fh_mat_prefix_counts(const char* who, fh_mat_t S, int cnt, const int* n, std::vector<int>& out);
 // dof -> the elements that hold it, by a counting pass on the device (fh_mat.hip; the pattern of fh_mat_create_from_elements and the transfers of
 // fh_elemtransfer.hip): d_ed[ne] a table of dofs in device memory, entry k belongs to element k / div (div = 1: the lists name the entries themselves);
 // lists are kept for the dofs < m, an entry outside [0, ncols) is refused in the words "<who>: a dof of an element is out of range" -- except, with

@@ -1037,6 +1037,174 @@ extern "C" int fh_mat_block_system(fh_mat_t S, int m, fh_mat_t* out) { return bl
 extern "C" int fh_mat_block_diagonal(fh_mat_t P, int m, fh_mat_t* out) { return block_matrix("fh_mat_block_diagonal", P, m, true, out); }
 
 // ------------------------------------------------------------------------------------------------
+// Block matrices of m stacked variables of different sizes n_0 .. n_{m-1} (unknown (k, i) = off_k + i, off_k = n_0 + .. + n_{k-1}):
+//   block_system_families(S, n) : block (k, l) is S[:n_k, :n_l], values zero.  The columns of a row of S ascend, so the columns < n_l of row i are its first
+//                                 cnt_l(i) entries: row (k, i) holds cnt_0(i) + .. + cnt_{m-1}(i) entries, block l after the blocks before it
+//   block_diagonal_of(P_0 ..)   : blkdiag of rectangular matrices with their values
+// The counts are taken by a kernel (a binary search per row and size); they come to the host, where the row table is scanned, and go back as the row table.
+// ------------------------------------------------------------------------------------------------
+struct BlockSizes {
+  int m, n[4], off[5];
+};
+
+__device__ __forceinline__ int prefix_count(const int* __restrict__ c, int len, int bound) {   // columns < bound among the ascending c[0 .. len)
+  int lo = 0, hi = len;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (c[mid] < bound) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void k_prefix_counts(int rows, BlockSizes bs, const int* __restrict__ rowptr, const int* __restrict__ col, int* __restrict__ out) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;      // (l, i)
+  if (idx >= (long long)rows * bs.m) return;
+  const int l = (int)(idx / rows), i = (int)(idx - (long long)l * rows);
+  const int rs = rowptr[i];
+  out[idx] = prefix_count(col + rs, rowptr[i + 1] - rs, bs.n[l]);
+}
+
+__global__ __launch_bounds__(256) void k_block_families_cols(int nrows, BlockSizes bs, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                             const int* __restrict__ orp, int* __restrict__ out) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;      // (system row, l)
+  if (idx >= (long long)nrows * bs.m) return;
+  const int R = (int)(idx / bs.m), l = (int)(idx - (long long)R * bs.m);
+  int k = 0;
+  while (k + 1 < bs.m && R >= bs.off[k + 1]) k++;
+  const int i = R - bs.off[k];
+  const int rs = rowptr[i], len = rowptr[i + 1] - rs;
+  int at = orp[R], cnt = 0, nl = 0, ol = 0;
+#pragma unroll
+  for (int q = 0; q < 4; q++)                                            // the blocks before l, then l's own count
+    if (q <= l) {
+      at += cnt;
+      nl = bs.n[q], ol = bs.off[q];
+      cnt = prefix_count(col + rs, len, nl);
+    }
+  const int room = orp[R + 1] - at;                                      // the row table was scanned from the same counts: never less than cnt
+  for (int t = 0; t < cnt && t < room; t++) out[at + t] = ol + col[rs + t];
+}
+
+__global__ __launch_bounds__(256) void k_block_diagonal_of_fill(long long nnz, int coloff, const int* __restrict__ col, const double* __restrict__ val,
+                                                                int* __restrict__ ocol, double* __restrict__ oval) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= nnz) return;
+  ocol[e] = coloff + col[e];
+  oval[e] = val[e];
+}
+
+int fh_mat_prefix_counts(const char* who, fh_mat_t S, int cnt, const int* n, std::vector<int>& out) {
+  BlockSizes bs{};
+  bs.m = cnt;
+  for (int l = 0; l < cnt; l++) bs.n[l] = n[l];
+  const size_t total = (size_t)S->m * cnt;
+  out.assign(total, 0);
+  if (!total) return 0;
+  int* d = nullptr;
+  FH_REQUIRE(hipMalloc(&d, total * sizeof(int)) == hipSuccess, "%s: out of device memory", who);
+  hipStream_t st = S->ctx->stream;
+  hipLaunchKernelGGL(k_prefix_counts, dim3(fh_div_up((long long)total, 256)), dim3(256), 0, st, S->m, bs, S->d_rowptr, S->d_col, d);
+  const bool ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(out.data(), d, total * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                  hipStreamSynchronize(st) == hipSuccess;
+  hipFree(d);
+  FH_REQUIRE(ok, "%s: the counting kernel failed", who);
+  return 0;
+}
+
+extern "C" int fh_mat_block_system_families(fh_mat_t S, int m, const int* n, fh_mat_t* out) {
+  FH_GUARD_BEGIN
+  const char* who = "fh_mat_block_system_families";
+  FH_REQUIRE(S && out && n, "%s: null argument", who);
+  FH_REQUIRE(m >= 1 && m <= 4, "%s: %d variables, 1 .. 4 are served", who, m);
+  FH_REQUIRE((int)S->h_rowptr.size() == S->m + 1, "%s: the matrix has no host row table", who);
+  BlockSizes bs{};
+  bs.m = m;
+  for (int k = 0; k < m; k++) {
+    FH_REQUIRE(n[k] >= 1 && n[k] <= S->m, "%s: variable %d has %d unknowns, 1 .. %d are served by this matrix", who, k, n[k], S->m);
+    bs.n[k] = n[k];
+    bs.off[k + 1] = bs.off[k] + n[k];
+  }
+  *out = nullptr;
+  const int rows = S->m, N = bs.off[m];
+  std::vector<int> cnt;
+  FH_TRY(fh_mat_prefix_counts(who, S, m, n, cnt));
+  std::vector<int> rp((size_t)N + 1);
+  long long total = 0;
+  for (int k = 0; k < m; k++)
+    for (int i = 0; i < n[k]; i++) {
+      rp[(size_t)bs.off[k] + i] = (int)total;
+      for (int l = 0; l < m; l++) total += cnt[(size_t)l * rows + i];
+      FH_REQUIRE(total < 2147483647ll, "%s: the block matrix overflows int32", who);
+    }
+  rp[N] = (int)total;
+  fh_ctx_t c = S->ctx;
+  fh_mat_t B = nullptr;
+  if (fh_mat_alloc_device_pattern(c, N, N, std::move(rp), &B)) {
+    fh_mat_destroy(B);
+    return 2;
+  }
+  hipLaunchKernelGGL(k_block_families_cols, dim3(fh_div_up((long long)N * m, 256)), dim3(256), 0, c->stream, N, bs, S->d_rowptr, S->d_col, B->d_rowptr, B->d_col);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess || fh_spmv_build_rowblocks(B)) {
+    fh_mat_destroy(B);
+    fh_set_error("%s: the fill kernel failed", who);
+    return 1;
+  }
+  *out = B;
+  return 0;
+  FH_GUARD_END("fh_mat_block_system_families")
+}
+
+extern "C" int fh_mat_block_diagonal_of(int m, const fh_mat_t* P, fh_mat_t* out) {
+  FH_GUARD_BEGIN
+  const char* who = "fh_mat_block_diagonal_of";
+  FH_REQUIRE(P && out, "%s: null argument", who);
+  FH_REQUIRE(m >= 1 && m <= 4, "%s: %d variables, 1 .. 4 are served", who, m);
+  long long rows = 0, cols = 0, total = 0;
+  for (int k = 0; k < m; k++) {
+    FH_REQUIRE(P[k], "%s: matrix %d is null", who, k);
+    FH_REQUIRE(P[k]->ctx == P[0]->ctx, "%s: matrix %d lives on another context", who, k);
+    FH_REQUIRE((int)P[k]->h_rowptr.size() == P[k]->m + 1, "%s: matrix %d has no host row table", who, k);
+    rows += P[k]->m, cols += P[k]->n, total += P[k]->nnz;
+  }
+  FH_REQUIRE(total < 2147483647ll && rows < 2147483647ll && cols < 2147483647ll, "%s: the block matrix overflows int32", who);
+  *out = nullptr;
+  std::vector<int> rp((size_t)rows + 1);
+  {
+    size_t r = 0;
+    long long base = 0;
+    for (int k = 0; k < m; k++) {
+      for (int i = 0; i < P[k]->m; i++) rp[r++] = (int)(base + P[k]->h_rowptr[i]);
+      base += P[k]->nnz;
+    }
+    rp[r] = (int)base;
+  }
+  fh_ctx_t c = P[0]->ctx;
+  fh_mat_t B = nullptr;
+  if (fh_mat_alloc_device_pattern(c, (int)rows, (int)cols, std::move(rp), &B)) {
+    fh_mat_destroy(B);
+    return 2;
+  }
+  long long base = 0;
+  int coloff = 0;
+  for (int k = 0; k < m; k++) {
+    const long long nnz = P[k]->nnz;
+    if (nnz)
+      hipLaunchKernelGGL(k_block_diagonal_of_fill, dim3(fh_div_up(nnz, 256)), dim3(256), 0, c->stream, nnz, coloff, P[k]->d_col, P[k]->d_val, B->d_col + base,
+                         B->d_val + base);
+    base += nnz, coloff += P[k]->n;
+  }
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess || fh_spmv_build_rowblocks(B)) {
+    fh_mat_destroy(B);
+    fh_set_error("%s: the fill kernel failed", who);
+    return 1;
+  }
+  *out = B;
+  return 0;
+  FH_GUARD_END("fh_mat_block_diagonal_of")
+}
+
+// ------------------------------------------------------------------------------------------------
 // norms (l1 = max column sum, linfty = max row sum) -- setup/diagnostic only: via the host
 // ------------------------------------------------------------------------------------------------
 extern "C" int fh_mat_norm(fh_mat_t A, int kind, double* out) {

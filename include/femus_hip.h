@@ -179,6 +179,14 @@ int fh_mat_transpose(fh_mat_t A, fh_mat_t* At);                  /* get_transpos
  * block_diagonal: kron(I_m, P) with P's values (the transfers of a system of one family). */
 int fh_mat_block_system(fh_mat_t S, int m, fh_mat_t* out);
 int fh_mat_block_diagonal(fh_mat_t P, int m, fh_mat_t* out);
+/* The same for variables of DIFFERENT sizes n[0 .. m), unknown (k, i) = off_k + i with off_k = n[0] + .. + n[k-1]; both are device-built (fh_mat_built_on: 1).
+ * block_system_families: 1 <= n[k] <= S.m; the matrix is sum n_k square, block (k, l) is the pattern of S[:n_k, :n_l] with zero values -- row off_k + i holds,
+ * for l = 0 .. m-1 in turn, the columns off_l + j of every j < n_l of row i of S, which are the first entries of that row as its columns ascend.  The counts of
+ * those entries are taken by a kernel and come to the host as the row table; with every n[k] = S.m the integers are fh_mat_block_system's.
+ * block_diagonal_of: blkdiag(P[0] .. P[m-1]) of rectangular matrices of any sizes on one context, with their value bits (m times the same P: the bits of
+ * fh_mat_block_diagonal).  Refused: m outside 1 .. 4, a NULL matrix, n[k] out of range. */
+int fh_mat_block_system_families(fh_mat_t S, int m, const int* n, fh_mat_t* out);
+int fh_mat_block_diagonal_of(int m, const fh_mat_t* P, fh_mat_t* out);
 /* matrix_PtAP(P, A, reuse) :183 (PetscMatrix.cpp:733-751): C = P^T A P.  *C==NULL: symbolic+numeric; else numeric reuse */
 int fh_mat_ptap(fh_mat_t P, fh_mat_t A, fh_mat_t* C);
 /* general sparse product C = A*B (symbolic + numeric); matrix_ABC :186 (PetscMatrix.cpp:833-856), matrix_RightMatMult :189,
@@ -197,7 +205,8 @@ int fh_mat_abc(fh_mat_t A, fh_mat_t B, fh_mat_t C, fh_mat_t* D);
  * most 2000; the searching kernel serves everything else, option "spgemm_slot_map" 0, and fh_mat_matmul. */
 int fh_mat_product_info(fh_mat_t C, int* products, int* pattern /* [2] */, long long* map /* [10] */);
 /* Who made the pattern of a matrix, from the library's host bookkeeping (nothing is launched): *how = 0 the caller's arrays (fh_mat_create_csr), 1 a device
- * builder (fh_mat_create_from_elements / _from_mesh, fh_mat_transpose and the cached transpose, fh_mat_block_system / _diagonal), 2 the host loop such a builder
+ * builder (fh_mat_create_from_elements / _from_mesh, fh_mat_transpose and the cached transpose, fh_mat_block_system / _diagonal and their siblings
+ * _system_families / _diagonal_of), 2 the host loop such a builder
  * hands the WHOLE matrix to: a row of more than 1024 candidate columns (pattern from elements), a column of more than 1024 entries (transpose), or a source
  * without non-zeros (transpose: nothing to launch over). */
 int fh_mat_built_on(fh_mat_t A, int* how);
